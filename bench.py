@@ -2,7 +2,7 @@
 """Benchmark of the hot path: conv-VAE train step (encoder -> reparameterise -> decoder -> ELBO -> backward -> Adam)
 on synthetic 20x64x64 Moving-MNIST clips (BASELINE.json configs[1]: 256 clips = 5120 frames per GPU, z=128, bf16).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
       N>1: one rank per GPU over RCCL.  Under torch.distributed.run (WORLD_SIZE set) this process is one of the N ranks;
       started plainly, it launches `python -m torch.distributed.run --nproc-per-node N ... bench.py` as a child BEFORE
       touching the GPU itself and exits with the child's code (fails loudly when fewer than N GPUs are visible).
@@ -11,11 +11,16 @@ A "step" is one pass of this repo's ``train`` loop body (main.py:371-399 restate
 resident in HBM: labels -> normalise -> forward -> loss -> zero_grad -> backward -> FusedAdam.step.  The four scalars of
 every step (loss, nll, kl, mmd) stay on the device and are read back once, inside the timed region, when ``train``
 returns its per-step lists -- the host never waits for the GPU in the middle of a step.  Prints ONE JSON line (rank 0).
-Besides the contract's keys the line carries ``roofline`` (the largest kernel family of the step by GPU time -- wgrad2_kernel -- at its
-slowest layer, isolated launches timed with events on the launch stream), ``roofline_largest_launch`` (the single longest launch of the
-step, join_bwd_stream_kernel, same method), ``top_kernels`` (the committed per-family table: ms per step, algorithmic and measured bytes),
-``step_hbm_roofline`` (whole step against the ideal-fusion byte count), ``config4_deeper`` / ``config5_fp8`` (short runs of BASELINE
-configs[3] / [4]) and ``cpu_baseline`` (the CPU oracle on a bounded sample).
+
+A plain run only sets up, warms up (W steps), times the K steps, writes the outputs (--dump-outputs DIR: the last timed step's
+loss / nll / kl / mmd and the model's state after it, as DIR/<name>.npy) and prints the line: the headline keys plus figures derived
+from them (``step_hbm_roofline``: whole step against the ideal-fusion byte count).  ``--full`` adds the records that take runs or
+files of their own: ``roofline`` (the largest kernel family of the step by GPU time in the committed profile, at its slowest launch,
+isolated launches timed with events on the launch stream), ``roofline_largest_launch`` (the single longest launch of the step,
+join_bwd_stream_kernel, same method), ``top_kernels`` (the committed per-family table: ms per step, algorithmic and measured bytes),
+``step_traffic_ratio`` (the committed PMC bytes of the step), ``batch256_frames``, ``config4_deeper`` / ``config5_fp8`` / ``pixelvae``
+(short runs of BASELINE configs[3] / [4] and of the PixelVAE), ``elbo_rel_err_vs_cpu_oracle`` and ``cpu_baseline`` (the CPU oracle
+on a bounded sample); ``--no-roofline`` / ``--no-cpu-baseline`` leave parts of it out.
 """
 import argparse
 import importlib
@@ -38,6 +43,7 @@ MFMA_PEAK_TFLOPS = 2500.0      # MI355X_MICROARCH.md: ~2.5 PFLOP/s dense bf16
 TRAIN_BYTES_PER_FRAME = 3.40e6  # ideal-fusion bf16 activation traffic of one train step, per frame
 TRAIN_FLOP_PER_FRAME = 227409920  # z=128, SURVEY.md section 8(d)
 C4_TRAIN_FLOP_PER_FRAME = {512: 409862144}   # tools/count_flops.py: z=512, 2 blocks per stage (forward 137 166 848)
+DUMP_BYTES_MAX = 64 << 20      # --dump-outputs: at most this much in all (config 2: 8.3 MB, config 4: 17.3 MB)
 
 
 def synthetic_clips(clips, seed, device):
@@ -504,6 +510,31 @@ def step_traffic(N):
     return {"hbm_bytes_per_step": total, "ideal_fusion_bytes_per_step": ideal, "ratio": total / ideal, "source": src}
 
 
+def dump_outputs(path, model, scalars):
+    """--dump-outputs DIR: what the timed path hands its caller after its last step -- that step's four scalars (``train``'s per-step
+    lists: loss, nll, kl, mmd; float64) and the model's state after it (every parameter and BatchNorm running statistic in float32, the
+    BatchNorm step counters in float64) -- as DIR/<name>.npy.  Inputs, noise and initial weights follow from the arguments alone, so two
+    builds run with the same arguments can be compared output for output.  Past DUMP_BYTES_MAX in all, the largest arrays are cut to a
+    fixed, seeded sample of their elements (flattened, ascending index order)."""
+    import numpy as np
+    arrays = {name: np.asarray(vals[-1], dtype=np.float64) for name, vals in zip(("loss", "nll", "kl", "mmd"), scalars)}
+    for k, v in model.state_dict().items():
+        v = v.detach().cpu()
+        arrays[k] = (v.float() if v.is_floating_point() else v.double()).numpy()
+    total = sum(x.nbytes for x in arrays.values())
+    for k in sorted(arrays, key=lambda k: -arrays[k].nbytes):
+        if total <= DUMP_BYTES_MAX:
+            break
+        x = arrays[k].reshape(-1)
+        keep = max(1, x.size - (total - DUMP_BYTES_MAX) // x.itemsize - 1)
+        arrays[k] = x[np.sort(np.random.default_rng(0).choice(x.size, keep, replace=False))]
+        total -= x.nbytes - arrays[k].nbytes
+    os.makedirs(path, exist_ok=True)
+    for k, x in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), x)
+    print(f"[bench] outputs of the last timed step: {len(arrays)} arrays, {total / 2**20:.1f} MB -> {path}", file=sys.stderr, flush=True)
+
+
 def spawn_ranks(n, argv):
     """Started without torch.distributed.run: launch the N ranks as a child job (this process has not touched the GPU and
     never will) and return the child's exit code."""
@@ -532,13 +563,20 @@ def main():
     ap.add_argument("--z", type=int, default=None)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32", "fp8"],
                     help="fp8 = BASELINE configs[4]: bf16 storage, fp8 (e4m3) MFMA in the forward pass of the deep layers (tests/test_fp8_gpu.py)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the records beyond the headline (roofline probes, committed profile tables, 256-frame / config 4 / fp8 / PixelVAE "
+                         "sub-records, ELBO check against the CPU oracle, CPU baseline); off: the plain run times the steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, nll, kl, mmd and the model state after it) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: leave out the roofline probes and the sub-records")
     ap.add_argument("--sync-bn", action="store_true", help="BatchNorm statistics over the global batch (default: per rank)")
     ap.add_argument("--comm", default="torch", choices=["torch", "rccl"],
                     help="gradient exchange through torch.distributed's nccl(=RCCL) backend, or through the library's own RCCL "
                          "communicator (mmvae_comm_*)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     blocks = 2 if a.config == "c4" else 1
     if a.clips is None:
         a.clips = 512 if a.config == "c4" else 256
@@ -585,9 +623,12 @@ def main():
         run(a.warmup)
     fence()
     t0 = time.perf_counter()
-    losses = run(a.steps)[0]
+    scalars = run(a.steps)
     fence()
     dt = time.perf_counter() - t0
+    losses = scalars[0]
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, model, scalars)
     ranks_seen = world
     if dist is not None:
         tt = torch.tensor([dt], device=device, dtype=torch.float64)
@@ -623,8 +664,9 @@ def main():
             out["step_hbm_roofline"] = None
             out["step_mfma_roofline"] = None if fl is None else {"train_flop_per_frame": fl, "achieved_TFLOPs": value / world * fl / 1e12,
                                                                  "frac_of_2.5PF": value / world * fl / 2.5e15}
-        out["step_traffic_ratio"] = step_traffic(frames) if a.config == "c2" else None
-    if world == 1 and not a.no_roofline and a.config == "c2":
+        if a.full:
+            out["step_traffic_ratio"] = step_traffic(frames) if a.config == "c2" else None
+    if a.full and world == 1 and not a.no_roofline and a.config == "c2":
         # the other reading of "batch 256" (SURVEY 8): 256 FRAMES per step, same model -- a latency-bound point, for reference
         b256 = (torch.rand((256, 64, 64), generator=torch.Generator().manual_seed(99)) < P_ON).long().to(device)
         run(3, b256)
@@ -634,8 +676,8 @@ def main():
         torch.cuda.synchronize()
         d256 = (time.perf_counter() - t1) / 20
         out["batch256_frames"] = {"frames_per_sec": 256 / d256, "ms_per_step": 1e3 * d256, "note": "256 frames (not clips) per step"}
-    if world == 1 and not a.no_roofline and a.config == "c2" and a.dtype == "bf16":
-        # compact records of BASELINE configs[3] (deeper net, z = 512, 512 clips) and configs[4] (fp8 mode of config 2) in the default line,
+    if a.full and world == 1 and not a.no_roofline and a.config == "c2" and a.dtype == "bf16":
+        # compact records of BASELINE configs[3] (deeper net, z = 512, 512 clips) and configs[4] (fp8 mode of config 2) in the --full line,
         # a few steps each (the full runs: --config c4, --dtype fp8)
         del model, opt
         torch.cuda.empty_cache()
@@ -695,7 +737,7 @@ def main():
         except Exception as ex:  # noqa: BLE001 -- a sub-record must never take the headline down
             out["pixelvae"] = {"error": repr(ex)[:300]}
     if rank == 0:
-        if not a.no_roofline and a.config == "c2":
+        if a.full and not a.no_roofline and a.config == "c2":
             out["roofline"] = dominant_kernel_roofline(M, device, frames)
             if a.dtype == "bf16":
                 out["roofline_largest_launch"] = largest_launch_roofline(M, device, frames)
@@ -703,7 +745,7 @@ def main():
             out["top_kernels"] = None if top is None else {"source": top["source"], "same_build": top["same_build"], "step_ms_traced": top["step_ms_traced"],
                                                            "hbm_GB": top.get("hbm_GB"), "families": top["families"][:12], "largest": top["largest"][:6]}
             out["elbo_rel_err_vs_cpu_oracle"] = elbo_check(M, device, a.dtype)
-        if world == 1 and not a.no_cpu_baseline and a.config == "c2":
+        if a.full and world == 1 and not a.no_cpu_baseline and a.config == "c2":
             out["cpu_baseline"] = cpu_baseline(a.z)
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -24,10 +24,10 @@ python tools/pmc_summary.py $OUT/pmc_m/p_counter_collection.csv > $OUT/pmc_mfma_
 R=${ROUND_TAG:-r04}
 cp $OUT/top_kernels.json profiles/${R}_top_kernels.json
 cp $OUT/pmc_hbm.csv profiles/${R}_pmc_hbm.csv
-python bench.py > $OUT/bench_n1.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+python bench.py --full > $OUT/bench_n1.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
 cut -c1-300 $OUT/bench_n1.json
-python bench.py --config c4 --no-cpu-baseline > $OUT/bench_c4.json 2> $OUT/bench_c4.err
-python bench.py --dtype fp8 --no-cpu-baseline > $OUT/bench_fp8.json 2> $OUT/bench_fp8.err
+python bench.py --full --config c4 --no-cpu-baseline > $OUT/bench_c4.json 2> $OUT/bench_c4.err
+python bench.py --full --dtype fp8 --no-cpu-baseline > $OUT/bench_fp8.json 2> $OUT/bench_fp8.err
 python tools/deep_probe.py > $OUT/deep_layers.txt 2>&1
 python tools/wgrad_probe.py > $OUT/wgrad_layers.txt 2>&1
 cat $OUT/pmc_hbm.csv

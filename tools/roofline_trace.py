@@ -1,4 +1,4 @@
-"""Developer tool: the isolated roofline launches of `python bench.py` in a rocprofv3 kernel trace of that very command.
+"""Developer tool: the isolated roofline launches of `python bench.py --full` in a rocprofv3 kernel trace of that very command.
 bench.py times 20 isolated launches (after warm-up ones) of the roofline kernel (convT4_stream_kernel<32, ..> at decoder.uplayer5.0.conv2's
 shape) and 10 of the largest launch (tail_apply_mfma_kernel) with events on the launch stream AFTER its timed steps; this prints the
 profiler's durations of exactly those dispatches (the last 20 / 10 of each kernel in the trace) next to the in-step ones.
