@@ -169,26 +169,39 @@ MMVAE_API int mmvae_net_set_sync_bn_comm2(mmvae_net* net, mmvae_comm* comm_main,
 MMVAE_API int mmvae_rsample_fwd(const float* mu, const float* logvar, const float* eps, float* enc, int64_t n, void* stream);
 MMVAE_API int mmvae_rsample_bwd(const float* d_enc, const float* logvar, const float* eps, float* d_mu, float* d_logvar, int64_t n,
                       void* stream);
-/* acc[0] += -0.5*sum(logvar - exp(logvar) - mu^2 + 1)   (VAE.kl_divergence, model.py:364-365); acc is f64, caller-zeroed */
+/* The loss sums (kl_fwd, gauss_nll_fwd, ce_fwd, mmd_fwd) add into the f64 acc[0] with a reduction whose bits do not depend on
+ * block arrival order, at any magnitude.  The *_ex forms take `partials`: device scratch of MMVAE_SUM_PARTIALS doubles whose first
+ * word is zero before the first call (zero-fill it once).  Each block writes its f64 partial there and the last block to finish sums
+ * them in block order and resets the first word, so the buffer is ready for the next call on the same stream (or a captured graph's
+ * replay); calls that may run concurrently need buffers of their own.  The plain forms take no scratch and run the same sum in ONE
+ * block: the same exactness and determinism, for small inputs (the train step uses the *_ex forms). */
+#define MMVAE_SUM_PARTIALS 1025
+/* acc[0] += -0.5*sum(logvar - exp(logvar) - mu^2 + 1)   (VAE.kl_divergence, model.py:364-365) */
 MMVAE_API int mmvae_kl_fwd(const float* mu, const float* logvar, int64_t n, double* acc, void* stream);
+MMVAE_API int mmvae_kl_fwd_ex(const float* mu, const float* logvar, int64_t n, double* acc, double* partials, void* stream);
 /* d_mu = c*mu ; d_logvar = c*0.5*(exp(logvar)-1), c = coef * (gscale ? gscale[0] : 1).  In every *_bwd below `gscale` is an
  * optional DEVICE scalar (the upstream d(loss), so loss.backward() needs no host sync). */
 MMVAE_API int mmvae_kl_bwd(const float* mu, const float* logvar, float coef, const float* gscale, float* d_mu, float* d_logvar, int64_t n,
                  void* stream);
-/* acc[0] += -sum log N(target; recon, sigma)   (model.py:403) */
+/* acc[0] += -sum log N(target; recon, sigma)   (model.py:403); recon and target 16-byte aligned (else MMVAE_ERR_ARG) */
 MMVAE_API int mmvae_gauss_nll_fwd(const float* recon, const float* target, int64_t n, float sigma, double* acc, void* stream);
+MMVAE_API int mmvae_gauss_nll_fwd_ex(const float* recon, const float* target, int64_t n, float sigma, double* acc, double* partials,
+                                     void* stream);
 MMVAE_API int mmvae_gauss_nll_bwd(const float* recon, const float* target, int64_t n, float sigma, float coef, const float* gscale,
                         float* d_recon, void* stream);
 /* acc[0] += sum w[t]*CE(recon[:, :, p], t)   (F.cross_entropy(reduction='none', weight).sum(), model.py:400-401);
  * recon [N,Q,HW] f32, target [N,HW] int64, weight [Q] f32 or NULL */
 MMVAE_API int mmvae_ce_fwd(const float* recon, const int64_t* target, const float* weight, int N, int Q, int HW, double* acc, void* stream);
+MMVAE_API int mmvae_ce_fwd_ex(const float* recon, const int64_t* target, const float* weight, int N, int Q, int HW, double* acc,
+                              double* partials, void* stream);
 MMVAE_API int mmvae_ce_bwd(const float* recon, const int64_t* target, const float* weight, int N, int Q, int HW, float coef,
                  const float* gscale, float* d_recon, void* stream);
 /* acc[0] += sum k(x,x) + sum k(y,y) - 2 sum k(x,y),  k(a,b) = exp(-|a-b|^2 / d^2)   (compute_mmd, model.py:367-383);
  * x = true_samples, y = encoding, both [n,d] f32.  Never materialises (n,n,d).  scratch: 2n floats (row norms) selects the
- * exact-f32 MFMA path |x|^2+|y|^2-2x.y; NULL the direct (x-y)^2 VALU path. */
+ * exact-f32 MFMA path |x|^2+|y|^2-2x.y (x and y 16-byte aligned, else MMVAE_ERR_ARG); NULL the direct (x-y)^2 VALU path. */
 MMVAE_API int mmvae_mmd_fwd(const float* x, const float* y, int n, int d, float* scratch, double* acc, void* stream);
-/* d_y += coef * d(mmd)/dy */
+MMVAE_API int mmvae_mmd_fwd_ex(const float* x, const float* y, int n, int d, float* scratch, double* acc, double* partials, void* stream);
+/* d_y += coef * d(mmd)/dy; d <= 512 (else MMVAE_ERR_UNSUPPORTED) */
 MMVAE_API int mmvae_mmd_bwd(const float* x, const float* y, int n, int d, float coef, const float* gscale, float* d_y, void* stream);
 /* k[i][j] = exp(-mean_d((x_i - y_j)^2) / d), out (n, m) f32   (VAE.compute_kernel, model.py:367-376) */
 MMVAE_API int mmvae_rbf_kernel(const float* x, const float* y, int n, int m, int d, float* out, void* stream);

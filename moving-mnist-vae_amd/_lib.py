@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MMVAE_LIB_PATH") or os.path.join(_HERE, "libmmvae_hip.so")
 _lib = None
 ABI_VERSION = 3            # MMVAE_ABI_VERSION of include/mmvae.h
+SUM_PARTIALS = 1025        # MMVAE_SUM_PARTIALS: f64 scratch of each loss sum (mmvae_kl_fwd_ex, ...)
 
 P = c_void_p
 
@@ -43,12 +44,16 @@ PROTOTYPES = {
     "mmvae_rsample_fwd": (c_int, [P, P, P, P, c_int64, P]),
     "mmvae_rsample_bwd": (c_int, [P, P, P, P, P, c_int64, P]),
     "mmvae_kl_fwd": (c_int, [P, P, c_int64, P, P]),
+    "mmvae_kl_fwd_ex": (c_int, [P, P, c_int64, P, P, P]),
     "mmvae_kl_bwd": (c_int, [P, P, c_float, P, P, P, c_int64, P]),
     "mmvae_gauss_nll_fwd": (c_int, [P, P, c_int64, c_float, P, P]),
+    "mmvae_gauss_nll_fwd_ex": (c_int, [P, P, c_int64, c_float, P, P, P]),
     "mmvae_gauss_nll_bwd": (c_int, [P, P, c_int64, c_float, c_float, P, P, P]),
     "mmvae_ce_fwd": (c_int, [P, P, P, c_int, c_int, c_int, P, P]),
+    "mmvae_ce_fwd_ex": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P]),
     "mmvae_ce_bwd": (c_int, [P, P, P, c_int, c_int, c_int, c_float, P, P, P]),
     "mmvae_mmd_fwd": (c_int, [P, P, c_int, c_int, P, P, P]),
+    "mmvae_mmd_fwd_ex": (c_int, [P, P, c_int, c_int, P, P, P, P]),
     "mmvae_mmd_bwd": (c_int, [P, P, c_int, c_int, c_float, P, P, P]),
     "mmvae_loss_finish": (c_int, [P, P, c_float, c_float, c_float, c_float, P]),
     "mmvae_normalise_labels": (c_int, [P, c_int64, c_float, c_float, P, P]),
@@ -104,15 +109,19 @@ def lib():
             "Run `python -c 'import __graft_entry__ as g; g.build()'` (or `make -C moving-mnist-vae_amd/csrc`). "
             "There is no CPU fallback for the product path.")
     l = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in PROTOTYPES.items():
-        fn = getattr(l, name)
-        fn.restype = res
-        fn.argtypes = args
-    # include/mmvae.h: "bindings check mmvae_abi_version() at load time" -- a stale or foreign build would be called with shifted arguments
+    # include/mmvae.h: "bindings check mmvae_abi_version() at load time" -- a stale or foreign build would be called with shifted
+    # arguments.  Checked before the table is bound: a stale build may lack a symbol, and it should get this message, not an AttributeError.
+    l.mmvae_abi_version.restype, l.mmvae_abi_version.argtypes = c_int, []
     got = l.mmvae_abi_version()
     if got != ABI_VERSION:
         raise MmvaeError(f"{LIB_PATH} has C ABI version {got}, this binding expects {ABI_VERSION}: rebuild the library "
                          "(make -C moving-mnist-vae_amd/csrc)")
+    for name, (res, args) in PROTOTYPES.items():
+        fn = getattr(l, name, None)
+        if fn is None:            # (a build of the same ABI version from before an export was added)
+            raise MmvaeError(f"{LIB_PATH} lacks {name}: rebuild the library (make -C moving-mnist-vae_amd/csrc)")
+        fn.restype = res
+        fn.argtypes = args
     _lib = l
     return l
 

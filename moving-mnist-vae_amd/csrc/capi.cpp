@@ -212,27 +212,57 @@ int mmvae_rsample_fwd(const float* mu, const float* lv, const float* eps, float*
 int mmvae_rsample_bwd(const float* d_enc, const float* lv, const float* eps, float* d_mu, float* d_lv, int64_t n, void* st) {
   return launch_rsample_bwd(d_enc, lv, eps, d_mu, d_lv, (long)n, S(st));
 }
-int mmvae_kl_fwd(const float* mu, const float* lv, int64_t n, double* acc, void* st) { return launch_kl_fwd(mu, lv, (long)n, acc, S(st)); }
+static bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+// The loss sums: *_ex takes the ordered-reduction scratch (required); the plain form passes none and runs the sum in one block.
+int mmvae_kl_fwd_ex(const float* mu, const float* lv, int64_t n, double* acc, double* partials, void* st) {
+  if (n > 0 && (!mu || !lv || !acc || !partials)) { set_error("kl_fwd: bad argument"); return MMVAE_ERR_ARG; }
+  return launch_kl_fwd(mu, lv, (long)n, acc, partials, S(st));
+}
+int mmvae_kl_fwd(const float* mu, const float* lv, int64_t n, double* acc, void* st) {
+  if (n > 0 && (!mu || !lv || !acc)) { set_error("kl_fwd: bad argument"); return MMVAE_ERR_ARG; }
+  return launch_kl_fwd(mu, lv, (long)n, acc, nullptr, S(st));
+}
 int mmvae_kl_bwd(const float* mu, const float* lv, float coef, const float* gscale, float* d_mu, float* d_lv, int64_t n, void* st) {
   return launch_kl_bwd(mu, lv, coef, gscale, d_mu, d_lv, (long)n, S(st));
 }
-int mmvae_gauss_nll_fwd(const float* r, const float* t, int64_t n, float sigma, double* acc, void* st) {
+static int gauss_nll_fwd(const float* r, const float* t, int64_t n, float sigma, double* acc, double* partials, bool need_partials, void* st) {
   if (!(sigma > 0.f)) { set_error("gauss_nll: sigma must be > 0"); return MMVAE_ERR_ARG; }
-  return launch_gauss_nll_fwd(r, t, (long)n, sigma, acc, S(st));
+  if (n > 0 && (!r || !t || !acc || (need_partials && !partials))) { set_error("gauss_nll_fwd: bad argument"); return MMVAE_ERR_ARG; }
+  if (n > 0 && (!aligned16(r) || !aligned16(t))) { set_error("gauss_nll_fwd: recon and target must be 16-byte aligned"); return MMVAE_ERR_ARG; }
+  return launch_gauss_nll_fwd(r, t, (long)n, sigma, acc, partials, S(st));
+}
+int mmvae_gauss_nll_fwd_ex(const float* r, const float* t, int64_t n, float sigma, double* acc, double* partials, void* st) {
+  return gauss_nll_fwd(r, t, n, sigma, acc, partials, true, st);
+}
+int mmvae_gauss_nll_fwd(const float* r, const float* t, int64_t n, float sigma, double* acc, void* st) {
+  return gauss_nll_fwd(r, t, n, sigma, acc, nullptr, false, st);
 }
 int mmvae_gauss_nll_bwd(const float* r, const float* t, int64_t n, float sigma, float coef, const float* gscale, float* d_r, void* st) {
   if (!(sigma > 0.f)) { set_error("gauss_nll: sigma must be > 0"); return MMVAE_ERR_ARG; }
   return launch_gauss_nll_bwd(r, t, (long)n, sigma, coef, gscale, d_r, S(st));
 }
+int mmvae_ce_fwd_ex(const float* r, const int64_t* t, const float* w, int N, int Q, int HW, double* acc, double* partials, void* st) {
+  if ((long)N * HW > 0 && (!r || !t || !acc || !partials || Q < 1)) { set_error("ce_fwd: bad argument"); return MMVAE_ERR_ARG; }
+  return launch_ce_fwd(r, reinterpret_cast<const long long*>(t), w, N, Q, HW, acc, partials, S(st));
+}
 int mmvae_ce_fwd(const float* r, const int64_t* t, const float* w, int N, int Q, int HW, double* acc, void* st) {
-  return launch_ce_fwd(r, reinterpret_cast<const long long*>(t), w, N, Q, HW, acc, S(st));
+  if ((long)N * HW > 0 && (!r || !t || !acc || Q < 1)) { set_error("ce_fwd: bad argument"); return MMVAE_ERR_ARG; }
+  return launch_ce_fwd(r, reinterpret_cast<const long long*>(t), w, N, Q, HW, acc, nullptr, S(st));
 }
 int mmvae_ce_bwd(const float* r, const int64_t* t, const float* w, int N, int Q, int HW, float coef, const float* gscale, float* d_r,
                  void* st) {
   return launch_ce_bwd(r, reinterpret_cast<const long long*>(t), w, N, Q, HW, coef, gscale, d_r, S(st));
 }
+static int mmd_fwd(const float* x, const float* y, int n, int d, float* scratch, double* acc, double* partials, bool need_partials, void* st) {
+  if (n > 0 && (!x || !y || !acc || (need_partials && !partials) || d < 1)) { set_error("mmd_fwd: bad argument"); return MMVAE_ERR_ARG; }
+  if (n > 0 && scratch && (!aligned16(x) || !aligned16(y))) { set_error("mmd_fwd: x and y must be 16-byte aligned"); return MMVAE_ERR_ARG; }
+  return scratch ? launch_mmd_fwd_mfma(x, y, n, d, scratch, acc, partials, S(st)) : launch_mmd_fwd(x, y, n, d, acc, partials, S(st));
+}
+int mmvae_mmd_fwd_ex(const float* x, const float* y, int n, int d, float* scratch, double* acc, double* partials, void* st) {
+  return mmd_fwd(x, y, n, d, scratch, acc, partials, true, st);
+}
 int mmvae_mmd_fwd(const float* x, const float* y, int n, int d, float* scratch, double* acc, void* st) {
-  return scratch ? launch_mmd_fwd_mfma(x, y, n, d, scratch, acc, S(st)) : launch_mmd_fwd(x, y, n, d, acc, S(st));
+  return mmd_fwd(x, y, n, d, scratch, acc, nullptr, false, st);
 }
 int mmvae_mmd_bwd(const float* x, const float* y, int n, int d, float coef, const float* gscale, float* d_y, void* st) {
   return launch_mmd_bwd(x, y, n, d, coef, gscale, d_y, S(st));

@@ -344,19 +344,21 @@ int launch_planar_to_nhwc16(int dt, const void* in, int in_dt, void* o16, int N,
 int launch_rsample_fwd(int dt, const float* mu, const float* logvar, const float* eps, float* enc_f32, void* enc_t, long n,
                        hipStream_t s);
 int launch_rsample_bwd(const float* d_enc, const float* logvar, const float* eps, float* d_mu, float* d_logvar, long n, hipStream_t s);
-int launch_kl_fwd(const float* mu, const float* logvar, long n, double* out, hipStream_t s);
+// Every loss sum below adds into the f64 out[0] through `part` (MMVAE_SUM_PARTIALS doubles, part[0] zero between calls): a
+// block-ordered reduction whose bits do not depend on block arrival order (latent_loss.hip); part == nullptr runs it in one block
+int launch_kl_fwd(const float* mu, const float* logvar, long n, double* out, double* part, hipStream_t s);
 // d_mu += coef*mu ; d_logvar += coef*0.5*(exp(lv)-1)   (coef = kl_weight * upstream / N)
 int launch_kl_bwd(const float* mu, const float* logvar, float coef, const float* gscale, float* d_mu, float* d_logvar, long n, hipStream_t s);
 // Gaussian NLL: out[0] += sum 0.5*((t-r)/sigma)^2 + log(sigma) + 0.5*log(2pi);  d_r = coef*(r-t)/sigma^2
-int launch_gauss_nll_fwd(const float* r, const float* t, long n, float sigma, double* out, hipStream_t s);
+int launch_gauss_nll_fwd(const float* r, const float* t, long n, float sigma, double* out, double* part, hipStream_t s);
 int launch_gauss_nll_bwd(const float* r, const float* t, long n, float sigma, float coef, const float* gscale, float* d_r, hipStream_t s);
-// weighted cross entropy over NCHW logits [N][Q][HW], int64 targets [N][HW]: out += sum w[t]*(lse - r[t])
-int launch_ce_fwd(const float* r, const long long* t, const float* w, int N, int Q, int HW, double* out, hipStream_t s);
+// weighted cross entropy over NCHW logits [N][Q][HW], int64 targets [N][HW]: out += sum w[t]*(log sum_q exp(r[q]-max) - (r[t]-max))
+int launch_ce_fwd(const float* r, const long long* t, const float* w, int N, int Q, int HW, double* out, double* part, hipStream_t s);
 int launch_ce_bwd(const float* r, const long long* t, const float* w, int N, int Q, int HW, float coef, const float* gscale, float* d_r,
                   hipStream_t s);
 // MMD (sums): out += sum_ij k(x_i,x_j) + sum_ij k(y_i,y_j) - 2 sum_ij k(x_i,y_j), k = exp(-|a-b|^2/d^2)
-int launch_mmd_fwd(const float* x, const float* y, int n, int d, double* out, hipStream_t s);
-int launch_mmd_fwd_mfma(const float* x, const float* y, int n, int d, float* scratch /*2n floats*/, double* out, hipStream_t s);
+int launch_mmd_fwd(const float* x, const float* y, int n, int d, double* out, double* part, hipStream_t s);
+int launch_mmd_fwd_mfma(const float* x, const float* y, int n, int d, float* scratch /*2n floats*/, double* out, double* part, hipStream_t s);
 // k[i][j] = exp(-|x_i - y_j|^2 / d^2), (n, m) f32  (VAE.compute_kernel, model.py:367-376)
 int launch_rbf_matrix(const float* x, const float* y, int n, int m, int d, float* out, hipStream_t s);
 // d_y[j] += coef * d(mmd)/d(y_j)

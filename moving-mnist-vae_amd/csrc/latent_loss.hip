@@ -1,8 +1,9 @@
 // Latent-space and loss kernels: reparameterisation, KL, Gaussian NLL / weighted cross-entropy, RBF-MMD,
-// plus the flat Adam step and small conversion helpers.  All scalar reductions accumulate in f64 through one
-// atomicAdd per block into a caller-zeroed accumulator.  Every block's contribution is first rounded to a multiple of 2^-16: all
-// running sums (< 2^37) are then exactly representable, the f64 additions are exact and the total is the same bits in ANY arrival
-// order -- the step stays bit-reproducible without a second reduction pass (rounding: <= 8e-6 per block, 1e-10 of a loss sum).
+// plus the flat Adam step and small conversion helpers.  All scalar reductions accumulate in f64 and are reduced in a fixed order:
+// every block writes its f64 partial to caller-provided scratch, and the last block to finish (a ticket counter in the scratch, which
+// it resets, so the next call on the stream and a captured graph's replays find it at zero) sums the partials in block order and adds
+// the total to the accumulator with one atomicAdd.  The result is the same bits in any block arrival order, at every magnitude, with
+// no second launch.  Without scratch (the C ABI's plain, pre-_ex entry points) the same sum runs in a single block.
 #include "kernels.hpp"
 
 namespace mmvae {
@@ -14,17 +15,42 @@ static int rblocks(long n, int cap = 1024) {
   return (int)b;
 }
 
-__device__ __forceinline__ double exact_quantum(double s) { return rint(s * 65536.0) * (1.0 / 65536.0); }
-__device__ __forceinline__ void block_atomic_add_d(double v, double* out) {
+// part: MMVAE_SUM_PARTIALS doubles; part[0]'s low word is the ticket (zero between calls), part[1 + b] block b's partial.
+// gridDim.x <= kSumBlocks.  part == nullptr: a one-block launch (sum_grid), whose own fixed-order sum is the total.
+// `extra` (uniform) joins the total before the one add into *out.
+constexpr int kSumBlocks = MMVAE_SUM_PARTIALS - 1;
+static unsigned sum_grid(long blocks, const double* part) { return part ? (unsigned)(blocks < kSumBlocks ? blocks : kSumBlocks) : 1u; }
+__device__ __forceinline__ void block_sum_ordered(double v, double* out, double* part, double extra = 0.0) {
   __shared__ double sred[4];
+  __shared__ int last;
   v = wave_sum_d(v);
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   if (lane == 0) sred[wid] = v;
   __syncthreads();
+  unsigned* ticket = reinterpret_cast<unsigned*>(part);
   if (threadIdx.x == 0) {
     double s = 0.0;
     for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s += sred[w];
-    atomicAdd(out, exact_quantum(s));
+    if (!part) {
+      atomicAdd(out, s + extra);
+    } else {
+      // The partial is written through to the device-coherent level (an agent-scope atomic store) and has completed there before the
+      // ticket is taken; the last block reads the partials with agent-scope atomic loads.  No acquire / release fence: on this part a
+      // device-scope fence writes back / invalidates the whole L2, which slows the kernels running beside these on the other stream.
+      __hip_atomic_store(part + 1 + blockIdx.x, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __builtin_amdgcn_s_waitcnt(0x0F70);              // vmcnt(0) (expcnt, lgkmcnt: no wait)
+      last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
+    }
+  }
+  __syncthreads();                                     // (every thread: `part` is uniform)
+  if (part && last && threadIdx.x < 64) {
+    double s = 0.0;                                    // lane l: blocks l, l + 64, ... in order; then the fixed shuffle tree
+    for (int b = threadIdx.x; b < (int)gridDim.x; b += 64) s += __hip_atomic_load(part + 1 + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s = wave_sum_d(s);
+    if (threadIdx.x == 0) {
+      atomicAdd(out, s + extra);
+      __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
   }
 }
 
@@ -59,17 +85,17 @@ int launch_rsample_bwd(const float* d_enc, const float* logvar, const float* eps
 }
 
 // ---------------------------------------------------------------- KL (model.py:364-365)
-__global__ void kl_fwd_kernel(const float* __restrict__ mu, const float* __restrict__ lv, long n, double* out) {
+__global__ void kl_fwd_kernel(const float* __restrict__ mu, const float* __restrict__ lv, long n, double* out, double* part) {
   double acc = 0.0;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const float l = lv[i], m = mu[i];
     acc += (double)(l - expf(l) - m * m + 1.0f);
   }
-  block_atomic_add_d(-0.5 * acc, out);
+  block_sum_ordered(-0.5 * acc, out, part);
 }
-int launch_kl_fwd(const float* mu, const float* logvar, long n, double* out, hipStream_t s) {
+int launch_kl_fwd(const float* mu, const float* logvar, long n, double* out, double* part, hipStream_t s) {
   if (n <= 0) return MMVAE_OK;
-  hipLaunchKernelGGL(kl_fwd_kernel, dim3(rblocks(n, 256)), dim3(256), 0, s, mu, logvar, n, out);
+  hipLaunchKernelGGL(kl_fwd_kernel, dim3(sum_grid(rblocks(n, 256), part)), dim3(256), 0, s, mu, logvar, n, out, part);
   return check_launch("kl_fwd");
 }
 __global__ void kl_bwd_kernel(const float* __restrict__ mu, const float* __restrict__ lv, float coef, const float* __restrict__ gs,
@@ -88,7 +114,7 @@ int launch_kl_bwd(const float* mu, const float* logvar, float coef, const float*
 
 // ---------------------------------------------------------------- Gaussian NLL (model.py:403)
 __global__ void gauss_nll_fwd_kernel(const float* __restrict__ r, const float* __restrict__ t, long n, float inv2var, float cst,
-                                     double* out) {
+                                     double* out, double* part) {
   double acc = 0.0;
   const long n4 = n >> 2;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
@@ -98,14 +124,14 @@ __global__ void gauss_nll_fwd_kernel(const float* __restrict__ r, const float* _
   }
   if (blockIdx.x == 0 && threadIdx.x == 0)
     for (long i = n4 << 2; i < n; ++i) { const float d = t[i] - r[i]; acc += (double)(d * d); }
-  block_atomic_add_d(acc * (double)inv2var, out);
-  if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(out, exact_quantum((double)cst * (double)n));
+  block_sum_ordered(acc * (double)inv2var, out, part, (double)cst * (double)n);
 }
-int launch_gauss_nll_fwd(const float* r, const float* t, long n, float sigma, double* out, hipStream_t s) {
+// r and t 16-byte aligned (float4 loads; checked by the C ABI)
+int launch_gauss_nll_fwd(const float* r, const float* t, long n, float sigma, double* out, double* part, hipStream_t s) {
   if (n <= 0) return MMVAE_OK;
   const float var = sigma * sigma;
   const float cst = logf(sigma) + (float)log(sqrt(2.0 * 3.14159265358979323846));
-  hipLaunchKernelGGL(gauss_nll_fwd_kernel, dim3(rblocks(n / 4 + 1)), dim3(256), 0, s, r, t, n, 1.0f / (2.0f * var), cst, out);
+  hipLaunchKernelGGL(gauss_nll_fwd_kernel, dim3(sum_grid(rblocks(n / 4 + 1), part)), dim3(256), 0, s, r, t, n, 1.0f / (2.0f * var), cst, out, part);
   return check_launch("gauss_nll_fwd");
 }
 __global__ void gauss_nll_bwd_kernel(const float* __restrict__ r, const float* __restrict__ t, long n, float k, const float* __restrict__ gs,
@@ -122,7 +148,7 @@ int launch_gauss_nll_bwd(const float* r, const float* t, long n, float sigma, fl
 // ---------------------------------------------------------------- weighted cross entropy (model.py:400-401)
 template <bool BWD>
 __global__ void ce_kernel(const float* __restrict__ r, const long long* __restrict__ t, const float* __restrict__ w, int N, int Q, int HW,
-                          float coef, const float* __restrict__ gs, double* out, float* __restrict__ d_r) {
+                          float coef, const float* __restrict__ gs, double* out, double* part, float* __restrict__ d_r) {
   double acc = 0.0;
   if (BWD && gs) coef *= gs[0];
   const long total = (long)N * HW;
@@ -134,76 +160,86 @@ __global__ void ce_kernel(const float* __restrict__ r, const long long* __restri
     for (int q = 1; q < Q; ++q) mx = fmaxf(mx, rp[(long)q * HW]);
     float se = 0.f;
     for (int q = 0; q < Q; ++q) se += expf(rp[(long)q * HW] - mx);
-    const float lse = mx + logf(se);
+    // max-shifted, as log_softmax: -log p_tg = log(se) - (x_tg - mx).  (mx + log(se) would round to ulp(|mx|) and quantise
+    // a confident pixel's loss and gradient to it: the result would depend on a shift of all logits.)
+    const float lse = logf(se);
     const float wt = w ? w[tg] : 1.f;
     if (!BWD) {
-      acc += (double)(wt * (lse - rp[(long)tg * HW]));
+      acc += (double)(wt * (lse - (rp[(long)tg * HW] - mx)));
     } else {
       float* dp = d_r + (long)n * Q * HW + p;
       for (int q = 0; q < Q; ++q) {
-        const float sm = expf(rp[(long)q * HW] - lse);
+        const float sm = expf((rp[(long)q * HW] - mx) - lse);
         dp[(long)q * HW] = coef * wt * (sm - (q == tg ? 1.f : 0.f));
       }
     }
   }
-  if (!BWD) block_atomic_add_d(acc, out);
+  if (!BWD) block_sum_ordered(acc, out, part);
 }
-int launch_ce_fwd(const float* r, const long long* t, const float* w, int N, int Q, int HW, double* out, hipStream_t s) {
+int launch_ce_fwd(const float* r, const long long* t, const float* w, int N, int Q, int HW, double* out, double* part, hipStream_t s) {
   if ((long)N * HW <= 0) return MMVAE_OK;
-  hipLaunchKernelGGL((ce_kernel<false>), dim3(rblocks((long)N * HW)), dim3(256), 0, s, r, t, w, N, Q, HW, 0.f, (const float*)nullptr, out, (float*)nullptr);
+  hipLaunchKernelGGL((ce_kernel<false>), dim3(sum_grid(rblocks((long)N * HW), part)), dim3(256), 0, s, r, t, w, N, Q, HW, 0.f, (const float*)nullptr, out, part,
+                     (float*)nullptr);
   return check_launch("ce_fwd");
 }
 int launch_ce_bwd(const float* r, const long long* t, const float* w, int N, int Q, int HW, float coef, const float* gscale, float* d_r,
                   hipStream_t s) {
   if ((long)N * HW <= 0) return MMVAE_OK;
-  hipLaunchKernelGGL((ce_kernel<true>), dim3(rblocks((long)N * HW, 2048)), dim3(256), 0, s, r, t, w, N, Q, HW, coef, gscale, (double*)nullptr, d_r);
+  hipLaunchKernelGGL((ce_kernel<true>), dim3(rblocks((long)N * HW, 2048)), dim3(256), 0, s, r, t, w, N, Q, HW, coef, gscale, (double*)nullptr, (double*)nullptr, d_r);
   return check_launch("ce_bwd");
 }
 
 // ---------------------------------------------------------------- RBF MMD (model.py:367-383), never materialises (N,N,d)
-// 64x64 pair tile per block, 4x4 pairs per thread, d staged through LDS in chunks of 32.
-__global__ __launch_bounds__(256) void mmd_fwd_kernel(const float* __restrict__ x, const float* __restrict__ y, int n, int d, double* out) {
+// 64x64 pair tile per step, 4x4 pairs per thread, d staged through LDS in chunks of 32; the blocks walk the 3 x tiles^2 tiles
+// (xx, yy, xy) with stride gridDim.x (<= kSumBlocks: one ordered partial each).
+__global__ __launch_bounds__(256) void mmd_fwd_kernel(const float* __restrict__ x, const float* __restrict__ y, int n, int d, int tiles,
+                                                      double* out, double* part) {
   __shared__ float sA[64][33];
   __shared__ float sB[64][33];
-  const int which = blockIdx.z;     // 0: xx, 1: yy, 2: xy
-  const float* A = which == 1 ? y : x;
-  const float* B = which == 0 ? x : y;
-  const int i0 = blockIdx.y * 64, j0 = blockIdx.x * 64;
   const int ti = threadIdx.x >> 4, tj = threadIdx.x & 15;
-  float acc[4][4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = 0.f;
-  for (int k0 = 0; k0 < d; k0 += 32) {
-    __syncthreads();
-    for (int v = threadIdx.x; v < 64 * 32; v += 256) {
-      const int rr = v >> 5, kk = v & 31;
-      sA[rr][kk] = (i0 + rr < n && k0 + kk < d) ? A[(long)(i0 + rr) * d + k0 + kk] : 0.f;
-      sB[rr][kk] = (j0 + rr < n && k0 + kk < d) ? B[(long)(j0 + rr) * d + k0 + kk] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll 8
-    for (int kk = 0; kk < 32; ++kk) {
-      float av[4], bv[4];
-#pragma unroll
-      for (int a = 0; a < 4; ++a) av[a] = sA[ti + 16 * a][kk];
-#pragma unroll
-      for (int b = 0; b < 4; ++b) bv[b] = sB[tj + 16 * b][kk];
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) { const float df = av[a] - bv[b]; acc[a][b] += df * df; }
-    }
-  }
   const float inv = 1.0f / ((float)d * (float)d);
-  double sum = 0.0;
+  double total = 0.0;
+  for (int e = blockIdx.x; e < 3 * tiles * tiles; e += gridDim.x) {
+    const int which = e / (tiles * tiles);       // 0: xx, 1: yy, 2: xy
+    const int rem = e - which * tiles * tiles;
+    const float* A = which == 1 ? y : x;
+    const float* B = which == 0 ? x : y;
+    const int i0 = (rem / tiles) * 64, j0 = (rem % tiles) * 64;
+    float acc[4][4];
 #pragma unroll
-  for (int a = 0; a < 4; ++a)
+    for (int a = 0; a < 4; ++a)
 #pragma unroll
-    for (int b = 0; b < 4; ++b)
-      if (i0 + ti + 16 * a < n && j0 + tj + 16 * b < n) sum += (double)expf(-acc[a][b] * inv);
-  block_atomic_add_d(which == 2 ? -2.0 * sum : sum, out);
+      for (int b = 0; b < 4; ++b) acc[a][b] = 0.f;
+    for (int k0 = 0; k0 < d; k0 += 32) {
+      __syncthreads();
+      for (int v = threadIdx.x; v < 64 * 32; v += 256) {
+        const int rr = v >> 5, kk = v & 31;
+        sA[rr][kk] = (i0 + rr < n && k0 + kk < d) ? A[(long)(i0 + rr) * d + k0 + kk] : 0.f;
+        sB[rr][kk] = (j0 + rr < n && k0 + kk < d) ? B[(long)(j0 + rr) * d + k0 + kk] : 0.f;
+      }
+      __syncthreads();
+#pragma unroll 8
+      for (int kk = 0; kk < 32; ++kk) {
+        float av[4], bv[4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) av[a] = sA[ti + 16 * a][kk];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) bv[b] = sB[tj + 16 * b][kk];
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+          for (int b = 0; b < 4; ++b) { const float df = av[a] - bv[b]; acc[a][b] += df * df; }
+      }
+    }
+    double sum = 0.0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+        if (i0 + ti + 16 * a < n && j0 + tj + 16 * b < n) sum += (double)expf(-acc[a][b] * inv);
+    total += which == 2 ? -2.0 * sum : sum;
+  }
+  block_sum_ordered(total, out, part);
 }
 // VAE.compute_kernel (model.py:367-376): the (n, m) matrix k[i][j] = exp(-mean_d((x_i - y_j)^2) / d) itself (a helper of the
 // reference surface; the loss never materialises it).  Same 64x64 tile / 4x4 pairs per thread scheme as mmd_fwd_kernel.
@@ -287,7 +323,7 @@ __device__ __forceinline__ MmdEntry mmd_entry(int e, int tiles, int S) {
 
 __global__ __launch_bounds__(256) void mmd_fwd_mfma_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                            const float* __restrict__ nx, const float* __restrict__ ny, int n, int d,
-                                                           int tiles, double* out) {
+                                                           int tiles, double* out, double* part) {
   constexpr int kPitch = 40;                        // bf16 per row: 32 + 8 pad = 80 B, 16-byte fragment reads hit all banks once
   __shared__ __attribute__((aligned(16))) uint16_t sT[4][64 * kPitch];      // A hi, A lo, B hi, B lo
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, g = lane >> 4, r = lane & 15;
@@ -384,23 +420,24 @@ __global__ __launch_bounds__(256) void mmd_fwd_mfma_kernel(const float* __restri
     const double w = m.which == 2 ? -2.0 : ((m.jt > m.it) ? 2.0 : 1.0);
     sum += w * (double)tsum;
   }
-  block_atomic_add_d(sum, out);
+  block_sum_ordered(sum, out, part);
 }
 
-int launch_mmd_fwd(const float* x, const float* y, int n, int d, double* out, hipStream_t s) {
+int launch_mmd_fwd(const float* x, const float* y, int n, int d, double* out, double* part, hipStream_t s) {
   if (n <= 0) return MMVAE_OK;
   const int tiles = (n + 63) / 64;
-  hipLaunchKernelGGL(mmd_fwd_kernel, dim3(tiles, tiles, 3), dim3(256), 0, s, x, y, n, d, out);
+  const long total = 3L * tiles * tiles;
+  hipLaunchKernelGGL(mmd_fwd_kernel, dim3(sum_grid(total, part)), dim3(256), 0, s, x, y, n, d, tiles, out, part);
   return check_launch("mmd_fwd");
 }
-// scratch: 2*n floats (row squared norms of x and y)
-int launch_mmd_fwd_mfma(const float* x, const float* y, int n, int d, float* scratch, double* out, hipStream_t s) {
+// scratch: 2*n floats (row squared norms of x and y); x, y 16-byte aligned (float4 loads; checked by the C ABI)
+int launch_mmd_fwd_mfma(const float* x, const float* y, int n, int d, float* scratch, double* out, double* part, hipStream_t s) {
   if (n <= 0) return MMVAE_OK;
   const int tiles = (n + 63) / 64;
   hipLaunchKernelGGL(row_sqnorm_kernel, dim3((n + 3) / 4), dim3(256), 0, s, x, n, d, scratch);
   hipLaunchKernelGGL(row_sqnorm_kernel, dim3((n + 3) / 4), dim3(256), 0, s, y, n, d, scratch + n);
   const int total = 2 * ((tiles + 1) / 2) * (tiles + 1) + tiles * tiles;
-  hipLaunchKernelGGL(mmd_fwd_mfma_kernel, dim3(total < 1024 ? total : 1024), dim3(256), 0, s, x, y, scratch, scratch + n, n, d, tiles, out);
+  hipLaunchKernelGGL(mmd_fwd_mfma_kernel, dim3(sum_grid(total, part)), dim3(256), 0, s, x, y, scratch, scratch + n, n, d, tiles, out, part);
   return check_launch("mmd_fwd_mfma");
 }
 

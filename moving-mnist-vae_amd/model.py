@@ -21,7 +21,7 @@ from typing import List, Optional
 import torch
 from torch import nn
 
-from ._lib import MmvaeError, check, lib, ptr
+from ._lib import SUM_PARTIALS, MmvaeError, check, lib, ptr
 
 _DTYPES = {"f32": 0, "fp32": 0, "float32": 0, "bf16": 1, "bfloat16": 1, "fp8": 2}
 
@@ -288,7 +288,9 @@ class _LossFn(torch.autograd.Function):
         L = lib()
         N = target.shape[0]
         dev = recon.device
-        acc = torch.zeros(4, dtype=torch.float64, device=dev)      # px, kl, mmd
+        # px, kl, mmd, (pad), then the sums' ordered-reduction scratch (mmvae.h MMVAE_SUM_PARTIALS): the sums run one after another on
+        # one stream, and each leaves the scratch's ticket at zero for the next
+        acc = torch.zeros(4 + SUM_PARTIALS, dtype=torch.float64, device=dev)
         out = torch.empty(4, dtype=torch.float32, device=dev)      # loss, px/N, kl/N, mmd/N
         # `model._loss_side` (set by VAE.loss(deferred=True) inside a train step): the loss scalars are logged values -- no gradient kernel
         # reads them -- so their kernels (KL, MMD, NLL / CE sums, the combine) leave the critical stream: they are enqueued on the net's side
@@ -300,6 +302,7 @@ class _LossFn(torch.autograd.Function):
         model.__dict__["_loss_side"] = False
         model._flush_pending_loss()
         base = acc.data_ptr()
+        part = base + 32
         recon = recon.contiguous()
         categorical = model.pixelcnn is not None or model.decoder_out_channels > model.in_channels      # model.py:398
         if mu is not None and logvar is not None:
@@ -317,14 +320,14 @@ class _LossFn(torch.autograd.Function):
 
         def launch(st):
             if k_mu is not None and k_lv is not None:
-                check(L.mmvae_kl_fwd(ptr(k_mu), ptr(k_lv), k_mu.numel(), base + 8, st), "mmvae_kl_fwd")
+                check(L.mmvae_kl_fwd_ex(ptr(k_mu), ptr(k_lv), k_mu.numel(), base + 8, part, st), "mmvae_kl_fwd_ex")
             if k_enc is not None:
-                check(L.mmvae_mmd_fwd(ptr(k_ts), ptr(k_enc), N, k_enc.shape[1], ptr(scratch), base + 16, st), "mmvae_mmd_fwd")
+                check(L.mmvae_mmd_fwd_ex(ptr(k_ts), ptr(k_enc), N, k_enc.shape[1], ptr(scratch), base + 16, part, st), "mmvae_mmd_fwd_ex")
             if categorical:
                 Q, HW = k_rec.shape[1], k_rec.shape[2] * k_rec.shape[3]
-                check(L.mmvae_ce_fwd(ptr(k_rec), ptr(k_tgt), ptr(k_w), N, Q, HW, base, st), "mmvae_ce_fwd")
+                check(L.mmvae_ce_fwd_ex(ptr(k_rec), ptr(k_tgt), ptr(k_w), N, Q, HW, base, part, st), "mmvae_ce_fwd_ex")
             else:
-                check(L.mmvae_gauss_nll_fwd(ptr(k_rec), ptr(k_tgt), k_rec.numel(), sigma, base, st), "mmvae_gauss_nll_fwd")
+                check(L.mmvae_gauss_nll_fwd_ex(ptr(k_rec), ptr(k_tgt), k_rec.numel(), sigma, base, part, st), "mmvae_gauss_nll_fwd_ex")
             check(L.mmvae_loss_finish(base, ptr(out), nll_c, kl_c, mmd_c, float(N), st), "mmvae_loss_finish")
             _ = acc                     # (referenced: the accumulator lives as long as the closure)
 
@@ -766,9 +769,9 @@ class VAE(nn.Module):
         return self.run_pixelcnn(torch.cat([decoder_output, sample.to(decoder_output.dtype)], dim=1))
 
     def kl_divergence(self, encoding_mu, encoding_logvar):     # model.py:364-365
-        acc = torch.zeros(1, dtype=torch.float64, device=encoding_mu.device)
+        acc = torch.zeros(1 + SUM_PARTIALS, dtype=torch.float64, device=encoding_mu.device)       # the sum, then its scratch
         mu, lv = encoding_mu.contiguous().float(), encoding_logvar.contiguous().float()
-        check(lib().mmvae_kl_fwd(ptr(mu), ptr(lv), mu.numel(), ptr(acc), _stream()), "mmvae_kl_fwd")
+        check(lib().mmvae_kl_fwd_ex(ptr(mu), ptr(lv), mu.numel(), ptr(acc), ptr(acc) + 8, _stream()), "mmvae_kl_fwd_ex")
         return acc[0].float()
 
     def compute_kernel(self, x, y):                            # model.py:367-376
@@ -781,9 +784,9 @@ class VAE(nn.Module):
         return out
 
     def compute_mmd(self, x, y):                               # model.py:378-383
-        acc = torch.zeros(1, dtype=torch.float64, device=x.device)
+        acc = torch.zeros(1 + SUM_PARTIALS, dtype=torch.float64, device=x.device)                # the sum, then its scratch
         x, y = x.contiguous().float(), y.contiguous().float()
-        check(lib().mmvae_mmd_fwd(ptr(x), ptr(y), x.shape[0], x.shape[1], None, ptr(acc), _stream()), "mmvae_mmd_fwd")
+        check(lib().mmvae_mmd_fwd_ex(ptr(x), ptr(y), x.shape[0], x.shape[1], None, ptr(acc), ptr(acc) + 8, _stream()), "mmvae_mmd_fwd_ex")
         return acc[0].float()
 
     def _flush_pending_loss(self, only=None):
