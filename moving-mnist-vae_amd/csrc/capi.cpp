@@ -315,7 +315,7 @@ int mmvae_conv2d_fwd(int dt, int transposed, const void* x, const float* w, void
     return launch_conv3_stream(dt, s, x, scratch, nullptr, y, nullptr, ps, pb, relu, stats, nullptr, N, Ho, S(st));
   }
   if (!transposed) {
-    q.wfrag = op_frag_down(dt, g, H, W);
+    q.wfrag = op_deep2_down_ok(dt, g, H, W);
     if (w) { int rc = op_pack_down(dt, g, w, scratch, S(st), 1.f, 0, q.wfrag); if (rc < 0) return rc; }
     return op_run_down(dt, dt, g, scratch, N, x, H, W, y, Ho, Wo, ps, pb, relu, stats, 0, S(st), q);
   }
@@ -323,7 +323,7 @@ int mmvae_conv2d_fwd(int dt, int transposed, const void* x, const float* w, void
     if (w) { int rc = op_pack_up(dt, g, w, scratch, S(st)); if (rc < 0) return rc; }
     return launch_convT4_stream(dt, x, scratch, y, ps, pb, relu, stats, N, H, S(st));
   }
-  q.wfrag = op_frag_up(dt, g, Ho, Wo);
+  q.wfrag = op_deep2_up_ok(dt, g, Ho, Wo);
   if (w) { int rc = op_pack_up(dt, g, w, scratch, S(st), 1.f, 0, q.wfrag); if (rc < 0) return rc; }
   return op_run_up(dt, g, scratch, N, x, H, W, y, Ho, Wo, ps, pb, relu, stats, 0, S(st), q);
 }
@@ -342,11 +342,11 @@ int mmvae_conv2d_dgrad(int dt, int transposed, const void* dy, const float* w, v
     return rc < 0 ? rc : MMVAE_OK;
   }
   if (!transposed) {
-    q.wfrag = op_frag_up(dt, g, H, W);
+    q.wfrag = op_deep2_up_ok(dt, g, H, W);
     int rc = op_pack_up(dt, g, w, scratch, S(st), 1.f, 0, q.wfrag); if (rc < 0) return rc;
     return op_run_up(dt, g, scratch, N, dy, Ho, Wo, dx, H, W, nullptr, nullptr, 0, nullptr, 0, S(st), q);
   }
-  q.wfrag = op_frag_down(dt, g, Ho, Wo);
+  q.wfrag = op_deep2_down_ok(dt, g, Ho, Wo);
   int rc = op_pack_down(dt, g, w, scratch, S(st), 1.f, 0, q.wfrag); if (rc < 0) return rc;
   return op_run_down(dt, dt, g, scratch, N, dy, Ho, Wo, dx, H, W, nullptr, nullptr, 0, nullptr, 0, S(st), q);
 }
@@ -483,7 +483,6 @@ int mmvae_upblock_bwd_fused(const float* d_raw, const float* tw, const void* y2,
   if (!scratch || !d_raw || !tw || !y2 || !ys || !y1 || !xin || !w2 || !wu || !dw2 || !dwu || !da1 || !gin || !bn1_sums || N < 1 || ((sx != nullptr) != (bx != nullptr))) {
     set_error("upblock_bwd_fused: bad argument"); return MMVAE_ERR_ARG;
   }
-  if (!join_bwd_stream_ok(DT_BF16, 1, 16, 32, 64)) { set_error("upblock_bwd_fused: disabled (MMVAE_JOIN_BWD_STREAM=0)"); return MMVAE_ERR_UNSUPPORTED; }
   char* sc = static_cast<char*>(scratch);
   const ConvGeom g = geom_for(1, 16, 16, 4, 2, 1);
   int rc = op_pack_down(DT_BF16, g, w2, sc, S(st)); if (rc < 0) return rc;
@@ -512,7 +511,6 @@ int mmvae_upblock_tail_fwd(const void* y1, const float* s1, const float* b1, con
   if (!scratch || !y1 || !s1 || !b1 || !w2 || !xin || !wu || !s2 || !b2 || !ss || !bs || !tw || !r_raw || N < 1 || ((sx != nullptr) != (bx != nullptr))) {
     set_error("upblock_tail_fwd: bad argument"); return MMVAE_ERR_ARG;
   }
-  if (!up5_tail_fwd_ok(DT_BF16, 1, 16, 16, 32, 64)) { set_error("upblock_tail_fwd: disabled (MMVAE_TAIL_RECOMPUTE=0)"); return MMVAE_ERR_UNSUPPORTED; }
   char* sc = static_cast<char*>(scratch);
   const ConvGeom g = geom_for(1, 16, 16, 4, 2, 1);
   int rc = op_pack_up(DT_BF16, g, w2, sc, S(st)); if (rc < 0) return rc;

@@ -58,13 +58,6 @@ __device__ __forceinline__ void deep2_conv_body(const DeepArgs& a) {
   const bool has_pro = a.pro_scale != nullptr, has_bias = a.bias != nullptr, has_stats = a.stats != nullptr;
   const float relu_lo = a.pro_relu ? 0.f : -__builtin_inff();
   const int HqWq = a.Hq * a.Wq;
-#ifdef MMVAE_DEEP2_TS   // developer build (make EXTRA=-DMMVAE_DEEP2_TS): cycle stamps of wave 0 of every block -> a.ts[block][16]
-  long long* TS = (a.ts && t == 0 && blockIdx.y == 0) ? a.ts + (long)blockIdx.x * 16 : nullptr; int tsi = 0;
-#define TSMARK() do { if (TS && tsi < 16) TS[tsi++] = __builtin_readcyclecounter(); } while (0)
-#else
-#define TSMARK() do {} while (0)
-#endif
-  TSMARK();
 
   const int cv = t % cin_vecs, pix0 = t / cin_vecs, PS = nthr / cin_vecs;
   // ---- per-block tables (tile-invariant), one pass over the q-pixel slots:
@@ -94,7 +87,6 @@ __device__ __forceinline__ void deep2_conv_body(const DeepArgs& a) {
   for (int i = t; i < pitch / 16; i += nthr) reinterpret_cast<Vec16*>(sPatch + (size_t)npix_in * pitch)[i] = Vec16{{0, 0, 0, 0}};
   sStat[lane] = 0.f;
 
-  TSMARK();
   for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
     const int n0 = tile * a.ipt;
     const int nimg = min(a.ipt, a.N - n0);
@@ -141,9 +133,7 @@ __device__ __forceinline__ void deep2_conv_body(const DeepArgs& a) {
         }
       }
     }
-    TSMARK();
     __syncthreads();
-    TSMARK();
     for (int ph = 0; ph < a.nphase; ++ph) {
       const DeepPhase P = a.phases[ph];
       const long rowbytes = (long)P.ntaps * a.Cin * LES;
@@ -228,7 +218,6 @@ __device__ __forceinline__ void deep2_conv_body(const DeepArgs& a) {
           __builtin_amdgcn_sched_barrier(0);
         }
       }
-      TSMARK();
       // ---- epilogue of this phase: lane holds couts c0 + 8gq + 4m + j of its q-pixel of column tile pt
       float bv[8], st1[8], st2[8];
 #pragma unroll
@@ -266,7 +255,6 @@ __device__ __forceinline__ void deep2_conv_body(const DeepArgs& a) {
       }
     }
   }
-  TSMARK();
   if (has_stats) {
     // lane l: sum (l < 32) or sum of squares of channel c0 + (l & 31); parked by lanes r == 0 of this wave only
     a.stats[(long)blockIdx.x * 2 * a.Cout + (long)(lane >> 5) * a.Cout + c0 + (lane & 31)] = sStat[lane];
@@ -338,5 +326,4 @@ int launch_deep2_conv_bf16(const DeepArgs& a, int gx, hipStream_t s) { return la
 int launch_deep2_conv_bf16_f32(const DeepArgs& a, int gx, hipStream_t s) { return launch_deep2_t<bf16_t, float>(a, DT_BF16, gx, s); }
 #endif
 
-#undef TSMARK
 }  // namespace mmvae

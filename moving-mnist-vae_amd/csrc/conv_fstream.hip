@@ -196,8 +196,7 @@ __global__ __launch_bounds__(256, 2) void conv3_stream_kernel(Conv3StreamArgs a)
 }
 
 bool conv3_stream_ok(int dt, int Cin, int Cout, int k, int s, int p, int Hin, int Win) {
-  constexpr bool env = true;
-  return env && dt == DT_BF16 && Cin == 32 && Cout == 32 && k == 3 && p == 1 && (s == 1 || s == 2) && Hin == Win && Win == 16 * s;
+  return dt == DT_BF16 && Cin == 32 && Cout == 32 && k == 3 && p == 1 && (s == 1 || s == 2) && Hin == Win && Win == 16 * s;
 }
 
 // y [N][Ho][16][32] = conv3x3(x [N][s*Ho][s*16][32], stride s, pad 1) with the packed [32][9][32] weights; wsc / ysc / stats_sc (optional, s = 2):
@@ -762,8 +761,7 @@ __global__ __launch_bounds__(256, 2) void up5_tail_fwd_kernel(Up5TailFwdArgs a) 
 }
 
 bool up5_tail_fwd_ok(int dt, int OC, int C, int Cin, int Hin, int Hout) {
-  constexpr bool env = true;
-  return env && dt == DT_BF16 && OC == 1 && C == 16 && Cin == 16 && Hin == 32 && Hout == 64;
+  return dt == DT_BF16 && OC == 1 && C == 16 && Cin == 16 && Hin == 32 && Hout == 64;
 }
 // returns the number of partial rows [rows][2] (> 0) or an error
 int launch_up5_tail_fwd(const void* y1, const float* p1s, const float* p1b, const void* w2_up, const void* xin, const float* pxs, const float* pxb,
@@ -791,8 +789,7 @@ int launch_up5_tail_fwd(const void* y1, const float* p1s, const float* p1b, cons
 }
 
 bool convT4_stream_ok(int dt, int Cin, int Cout, int k, int s, int p, int Hin, int Win) {
-  constexpr bool env = true;
-  return env && dt == DT_BF16 && Cin == 16 && Cout == 16 && k == 4 && s == 2 && p == 1 && Hin == Win && (Win == 32 || Win == 16);
+  return dt == DT_BF16 && Cin == 16 && Cout == 16 && k == 4 && s == 2 && p == 1 && Hin == Win && (Win == 32 || Win == 16);
 }
 // y [N][2H][2H][16] = conv_transpose2d(x [N][H][H][16]) with the packed per-phase "up" weights; returns stats rows (> 0) or an error
 int launch_convT4_stream(int dt, const void* x, const void* w_up, void* y, const float* pro_scale, const float* pro_shift, int pro_relu, float* stats,
@@ -817,8 +814,7 @@ int launch_convT4_stream(int dt, const void* x, const void* w_up, void* y, const
 }
 
 bool tail_fwd_stream_ok(int dt, int OC, int H, int W) {
-  constexpr bool env = true;
-  return env && dt == DT_BF16 && OC == 1 && W == 64 && H == 64;
+  return dt == DT_BF16 && OC == 1 && W == 64 && H == 64;
 }
 // returns the number of partial rows [rows][2][1] (> 0) or an error
 int launch_tail_fwd_stream(int dt, const void* y2, const float* s2, const float* b2, const void* ys, const float* ss, const float* bs, const float* w,

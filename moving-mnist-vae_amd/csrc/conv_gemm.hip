@@ -251,17 +251,6 @@ static int launch_gather_t(GatherArgs& a, int gx, hipStream_t s) {
   return rc ? rc : gx * a.nphase;
 }
 
-int conv_xcd_walk() {
-  return 1;      // XCD-aware tile order (measured neutral to slightly positive; the switch is gone)
-}
-
-// (round 4, all sixteen channel-heavy layers through gather_gemm_kernel again for reference: 1.1-5.7x slower than the kernel each runs on
-// today, forward and data gradient, except uplayer3.conv1's forward -- 19.6 vs 24.1 us; the switch stays a constant)
-bool conv_force_v1() {
-  constexpr int v = 0;
-  return v != 0;
-}
-
 bool make_tile_geom(TileGeom& g, int N, int Hq, int Wq, int Hi, int Wi, int SI, int oh, int ow, int span_h, int span_w, int TP, int sub) {
   if (Hq <= 0 || Wq <= 0 || Wq > TP || N <= 0) return false;
   if (sub > 1 && (TP != 128 || (Hq * Wq >= 128 ? 128 % Wq != 0 : 128 % (Hq * Wq) != 0))) return false;   // sub-tiles must be whole rows / images
@@ -287,8 +276,7 @@ constexpr size_t kV2MaxLds = 60 * 1024;
 // Pipelined all-phases patch kernel: eligible when the weights of every phase together with one patch fit LDS.
 // Returns >0 (stats rows) when it ran, 0 when not eligible, <0 on error.
 static int try_patch(int dt, int out_dt, const GatherArgs& a, hipStream_t s) {
-  constexpr int enabled = 1;
-  if (!enabled || a.Cout > 64 || a.Cin > 256) return 0;
+  if (a.Cout > 64 || a.Cin > 256) return 0;
   if (a.x2 && (a.x_planar || a.y_planes || a.accumulate || out_dt != dt || a.Cin2 % (dt == DT_F32 ? 4 : 8) != 0 || a.Cin2 > 128 || a.Cout > 32)) return 0;
   if ((long)a.N * a.Ho * a.Wo * (a.y_planes ? a.y_planes : a.Cout) >= (1L << 30)) return 0;     // 32-bit output offsets
   if (!a.x_planar && (long)a.N * a.Hi * a.Wi * a.Cin * (long)dtype_size(dt) >= (1L << 31)) return 0;   // buffer-load range
@@ -337,12 +325,10 @@ static int try_patch(int dt, int out_dt, const GatherArgs& a, hipStream_t s) {
   }
   // tile size: 128 q-pixels, or 256 / 512 (whole rows, power-of-two width >= 16) for the 16- and 32-channel layers:
   // bigger tiles amortise barriers, tile decode and the patch halo
-  constexpr int sub_env = 0, uni_env = 1;
-  int max_sub = ct16 == 1 ? (a.x_planar ? 4 : 2) : 1;       // measured per layer class (tools/sweep_env.sh MMVAE_PATCH_SUB)
-  if (sub_env > 0) { const int inst = ct16 == 1 ? 4 : (ct16 == 2 ? 2 : 1); max_sub = sub_env < inst ? sub_env : inst; }
+  const int max_sub = ct16 == 1 ? (a.x_planar ? 4 : 2) : 1;       // measured per layer class
   // uniform geometry (whole rows, power-of-two width >= 16, every (ph, pw) phase present and full-size): LDS epilogue
   const bool pow2w = Wq >= 16 && (Wq & (Wq - 1)) == 0;
-  bool uni_ok = uni_env && pow2w && Hq * Wq >= 128 && a.nphase == a.SO * a.SO && a.SO <= 2 && (!a.y_planes || a.SO == 1);
+  bool uni_ok = pow2w && Hq * Wq >= 128 && a.nphase == a.SO * a.SO && a.SO <= 2 && (!a.y_planes || a.SO == 1);
   for (int i = 0; i < 4; ++i) b.phase_of[i] = -1;
   for (int p = 0; p < a.nphase && uni_ok; ++p) {
     const Phase& ph = a.phases[p];
@@ -394,8 +380,6 @@ static int try_patch(int dt, int out_dt, const GatherArgs& a, hipStream_t s) {
   if (gx > b.g.ntiles) gx = b.g.ntiles;
   if (gx > kGatherMaxGridX) gx = kGatherMaxGridX;
   if (gx >= 8) gx &= ~7;
-  b.xcd_walk = conv_xcd_walk();
-  b.dbg = 0;
   b.x_bytes = a.x_planar ? 0u : (unsigned)((long)a.N * a.Hi * a.Wi * a.Cin * (long)dtype_size(dt));
   if (a.x2) {
     if (ct16 > 2) return 0;
@@ -405,11 +389,7 @@ static int try_patch(int dt, int out_dt, const GatherArgs& a, hipStream_t s) {
   return launch_patch_conv(dt, out_dt, b, gx, s);
 }
 
-// deep2_conv_kernel (conv_deep2.inc): weights from L2 straight into MFMA fragments, no barrier in the K loop.  MMVAE_DEEP2=0: off
-static bool deep2_enabled() {
-  constexpr int enabled = 1;
-  return enabled != 0 && !conv_force_v1();
-}
+// deep2_conv_kernel (conv_deep2.inc): weights from L2 straight into MFMA fragments, no barrier in the K loop.
 // LDS bytes of a tile of npt*16 q-pixels (whole images)
 static size_t deep2_lds_for(int dt, int Cin, int Cout, int hw, int HiWi, int ntaps_all, int npt, int fp8 = 0) {
   DeepArgs b; memset(&b, 0, sizeof(b));
@@ -418,7 +398,6 @@ static size_t deep2_lds_for(int dt, int Cin, int Cout, int hw, int HiWi, int nta
   return deep2_conv_lds_bytes(b, dt);
 }
 bool deep2_shape_ok(int dt, int Cin, int Cout, int Hq, int Wq, int Hi, int Wi, int ntaps_all, int fp8) {
-  if (!deep2_enabled()) return false;
   if (fp8 && dt != DT_BF16) return false;
   const int ES = fp8 ? 1 : dt == DT_F32 ? 4 : 2;
   const int cpt = Cin * ES / 64;
@@ -435,7 +414,6 @@ bool deep2_shape_ok(int dt, int Cin, int Cout, int Hq, int Wq, int Hi, int Wi, i
   return deep2_lds_for(dt, Cin, Cout, hw, Hi * Wi, ntaps_all, npt_min, fp8) <= 150 * 1024;
 }
 static int try_deep2(int dt, int out_dt, const GatherArgs& a, hipStream_t s) {
-  constexpr int npt_env = 0;
   if (a.x_planar || a.y_planes || a.x2) return 0;
   if (a.fp8 && (!a.wfrag || a.accumulate || dt != DT_BF16 || out_dt != DT_BF16)) return 0;
   int Hq = 0, Wq = 0, ntaps_all = 0;
@@ -461,9 +439,7 @@ static int try_deep2(int dt, int out_dt, const GatherArgs& a, hipStream_t s) {
   }
   for (int t = 0; t < kMaxTaps; ++t) b.taps[t] = a.taps[t];
   for (b.cpt_log2 = 0; (1 << b.cpt_log2) < cpt; ++b.cpt_log2) {}
-  constexpr int nw_env = 0;
   b.nw = a.Cout / 32 < 8 ? a.Cout / 32 : 8;
-  if (nw_env && nw_env <= b.nw && (a.Cout / 32) % nw_env == 0) b.nw = nw_env;
   if ((64 * b.nw) % (a.Cin / VE) != 0) return 0;
   const int gy = a.Cout / (32 * b.nw);
   const int hw = Hq * Wq;
@@ -472,15 +448,14 @@ static int try_deep2(int dt, int out_dt, const GatherArgs& a, hipStream_t s) {
   int best = 0;
   for (int pass = 0; pass < 2 && !best; ++pass)
     for (int npt = 8; npt >= 2 && !best; npt >>= 1) {
-      if (npt_env && npt != npt_env && pass == 0) continue;
       if (hw > npt * 16) break;
       const size_t lds = deep2_lds_for(dt, a.Cin, a.Cout, hw, a.Hi * a.Wi, ntaps_all, npt, a.fp8);
       int ipt = npt * 16 / hw; if (ipt > a.N) ipt = a.N;
       const long ntiles = (a.N + ipt - 1) / ipt;
       if (pass == 0) {
         if (lds > 80 * 1024) continue;
-        // measured (tools/deep_sweep.sh): below one wave per SIMD a smaller tile wins, above it the larger tile's halved weight traffic does
-        if (!npt_env && npt > 2 && ntiles * gy * b.nw < 256 * 4) continue;
+        // measured: below one wave per SIMD a smaller tile wins, above it the larger tile's halved weight traffic does
+        if (npt > 2 && ntiles * gy * b.nw < 256 * 4) continue;
       } else if (lds > 150 * 1024) continue;
       best = npt;
     }
@@ -489,33 +464,12 @@ static int try_deep2(int dt, int out_dt, const GatherArgs& a, hipStream_t s) {
   if (b.ipt > a.N) b.ipt = a.N;
   b.ntiles = (a.N + b.ipt - 1) / b.ipt;
   int gx = b.ntiles < kGatherMaxGridX ? b.ntiles : kGatherMaxGridX;
-#ifdef MMVAE_DEEP2_TS
-  {
-    static long long* tsbuf = nullptr; static int tscount = 0;
-    if (!tsbuf && hipMalloc(&tsbuf, kGatherMaxGridX * 16 * 8) != hipSuccess) return MMVAE_ERR_HIP;
-    (void)hipMemsetAsync(tsbuf, 0, kGatherMaxGridX * 16 * 8, s);
-    b.ts = tsbuf;
-    const int rc = launch_deep2_conv(dt, out_dt, b, gx, s);
-    if (++tscount % 22 == 3) {
-      (void)hipStreamSynchronize(s);
-      static long long h[kGatherMaxGridX * 16];
-      (void)hipMemcpy(h, tsbuf, sizeof(h), hipMemcpyDeviceToHost);
-      fprintf(stderr, "DEEP2TS Cin=%d Cout=%d taps=%d Hi=%d ipt=%d npt=%d nw=%d ntiles=%d gx=%d lds=%zu frag=%d\n", b.Cin, b.Cout, b.ntaps_all, b.Hi, b.ipt, b.npt, b.nw, b.ntiles, gx, deep2_conv_lds_bytes(b, dt), b.wfrag);
-      for (int blk : {0, 1, gx / 2, gx - 1}) {
-        fprintf(stderr, "  blk %4d:", blk);
-        for (int i = 1; i < 16 && h[blk * 16 + i]; ++i) fprintf(stderr, " %7lld", h[blk * 16 + i] - h[blk * 16 + i - 1]);
-        fprintf(stderr, "\n");
-      }
-    }
-    return rc;
-  }
-#endif
   return launch_deep2_conv(dt, out_dt, b, gx, s);
 }
 
 // pos_conv_kernel (conv_pos.inc): q-grids up to 4x4, MFMA columns = images, padded (position, tap) pairs not computed
 static int try_pos(int dt, int out_dt, const GatherArgs& a, hipStream_t s) {
-  if (conv_force_v1() || dt != DT_BF16 || out_dt != DT_BF16 || !a.wfrag || a.fp8 || a.gup == 0) return 0;
+  if (dt != DT_BF16 || out_dt != DT_BF16 || !a.wfrag || a.fp8 || a.gup == 0) return 0;
   if (a.x_planar || a.y_planes || a.x2 || a.bias || a.Hi != a.Wi || a.Ho != a.Wo || a.Cout % 32 != 0) return 0;
   const int up = a.gup == 2 ? 1 : 0;
   if (!pos_conv_takes(a.gk, a.gs, a.gp, up, a.Hi, a.Ho, a.Cin)) return 0;
@@ -559,8 +513,7 @@ int launch_gather_gemm(int dt, int out_dt, GatherArgs a, hipStream_t s) {
   }
   if (a.x2) {
     // fragment-major weights are read by deep2_conv_kernel only, which takes one source: two launches then
-    constexpr bool merge = true;
-    int rc = (merge && !conv_force_v1() && !a.wfrag && !a.wfrag2) ? try_patch(dt, out_dt, a, s) : 0;
+    int rc = (!a.wfrag && !a.wfrag2) ? try_patch(dt, out_dt, a, s) : 0;
     if (rc != 0) return rc;
     GatherArgs m = a; m.x2 = nullptr; m.w2 = nullptr; m.Cin2 = 0; m.wfrag2 = 0;
     rc = launch_gather_gemm(dt, out_dt, m, s);
@@ -584,25 +537,20 @@ int launch_gather_gemm(int dt, int out_dt, GatherArgs a, hipStream_t s) {
   }
   if (ntap > kMaxTaps) { set_error("gather_gemm: %d taps > %d", ntap, kMaxTaps); return MMVAE_ERR_UNSUPPORTED; }
   if (max_tiles <= 0) return 1;
-  if (a.wfrag && conv_force_v1()) { set_error("gather_gemm: fragment-major weights with MMVAE_CONV_V1"); return MMVAE_ERR_UNSUPPORTED; }
-  if (!conv_force_v1()) {
-    const int rcp = a.wfrag ? 0 : try_patch(dt, out_dt, a, s);
-    if (rcp != 0) return rcp;
-    const int rcq = try_pos(dt, out_dt, a, s);
-    if (rcq != 0) return rcq;
-    const int rcd2 = try_deep2(dt, out_dt, a, s);
-    if (rcd2 != 0) return rcd2;
-    if (a.wfrag) { set_error("gather_gemm: fragment-major weights (Cin=%d Cout=%d) need the deep2 kernel, which does not take this launch", a.Cin, a.Cout); return MMVAE_ERR_UNSUPPORTED; }
-  }
+  const int rcp = a.wfrag ? 0 : try_patch(dt, out_dt, a, s);
+  if (rcp != 0) return rcp;
+  const int rcq = try_pos(dt, out_dt, a, s);
+  if (rcq != 0) return rcq;
+  const int rcd2 = try_deep2(dt, out_dt, a, s);
+  if (rcd2 != 0) return rcd2;
+  if (a.wfrag) { set_error("gather_gemm: fragment-major weights (Cin=%d Cout=%d) need the deep2 kernel, which does not take this launch", a.Cin, a.Cout); return MMVAE_ERR_UNSUPPORTED; }
   {
     // thin layers: barrier-free streaming kernel (weights in LDS, pixels straight from global memory)
     constexpr int g3_maxk = 160;
-    constexpr int g3_dbg = 0;
-    a.dbg = g3_dbg;
     int maxk = 0;
     for (int p = 0; p < a.nphase; ++p) if (a.phases[p].ntaps * a.Cin > maxk) maxk = a.phases[p].ntaps * a.Cin;
     const bool fits32 = (long)a.N * a.Hi * a.Wi * a.Cin < (1L << 31) && (long)a.N * a.Ho * a.Wo * a.Cout < (1L << 31);   // 32-bit element offsets
-    if (!conv_force_v1() && !a.x_planar && !a.y_planes && !a.bias && out_dt == dt && a.Cout <= 64 && maxk <= g3_maxk && fits32) {
+    if (!a.x_planar && !a.y_planes && !a.bias && out_dt == dt && a.Cout <= 64 && maxk <= g3_maxk && fits32) {
       int ct16 = (a.Cout + 15) / 16; if (ct16 == 3) ct16 = 4;
       if (gather3_lds_bytes(a, dt, ct16 * 16) <= kV2MaxLds) {
         long wt = 0;
@@ -778,17 +726,16 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs a) {
 
 // Returns 1 when the v2 kernel ran, 0 when not eligible, <0 on error.
 static int try_wgrad2(int dt, const WgradArgs& a, hipStream_t s) {
-  if ((conv_force_v1() && !a.P_planar && !a.G_planar) || a.Ca % 16 || a.Cb % 16 || a.ntaps > 25) return 0;
+  if (a.Ca % 16 || a.Cb % 16 || a.ntaps > 25) return 0;
   if (a.proP_scale && a.proG_scale) return 0;          // one prologue register set in the kernel
   if (a.P_planar && (a.Ca != 16 || a.P_planes > 16 || a.proP_scale)) return 0;
-  if (a.G_planar && (a.Cb != 16 || a.Ca != 32 || a.proG_scale || a.ntaps < 4)) return 0;
   auto pick = [](int c) { return c >= 64 ? 64 : c; };
   int TA = pick(a.Ca), TB = pick(a.Cb);
   if (!(TA == 16 || TA == 32 || TA == 64) || !(TB == 16 || TB == 32 || TB == 64)) return 0;
   if (a.Ca % TA || a.Cb % TB) return 0;
   // a 1x1 stride-2 layer on 4x4 maps (encoder.layer3's shortcut): the 128-pixel tile's G patch is 8 images x 7x7 pixels, 50 KB at 64
   // channels -- it fits with a 32-channel G tile (the k-split mode cannot shrink the pixel tile instead)
-  if (a.ntaps < 4 && TB == 64 && !a.P_planar && !a.G_planar) {
+  if (a.ntaps < 4 && TB == 64 && !a.P_planar) {
     Wgrad2Args probe; memset(&probe, 0, sizeof(probe));
     probe.TG = wgrad2_taps_per_block(TA / 16, 4, a.ntaps); probe.nw = 4;
     if (make_tile_geom(probe.g, a.N, a.Hp, a.Wp, a.Hg, a.Wg, a.stride, -a.pad, -a.pad, a.ksz, a.ksz, 128, 1) &&
@@ -796,19 +743,18 @@ static int try_wgrad2(int dt, const WgradArgs& a, hipStream_t s) {
   }
   const int ta16 = TA / 16, tb16 = TB / 16;
   Wgrad2Args b; memset(&b, 0, sizeof(b));
-  b.P = a.P; b.G = a.G; b.dW = a.dW;
+  b.P = a.P; b.G = a.G;
   b.proP_scale = a.proP_scale; b.proP_shift = a.proP_shift; b.proP_relu = a.proP_relu;
   b.proG_scale = a.proG_scale; b.proG_shift = a.proG_shift; b.proG_relu = a.proG_relu;
   b.TG = wgrad2_taps_per_block(ta16, tb16, a.ntaps);
   b.nw = 4;
   // deep layers (>= 32x64 channel tiles, 3x3 / 4x4 kernels): one tap per wave, every tap in one block -> the tile is
   // staged once instead of once per tap group
-  constexpr int nw_env = 1;
   // (only where the 4-wave block needs several tap groups, and not for 64x64 tiles with 16 waves: 128 VGPRs spill)
-  if (nw_env && !a.P_planar && !a.G_planar && ta16 >= 2 && tb16 >= 2 && (a.ntaps == 9 || a.ntaps == 16) && b.TG < a.ntaps &&
+  if (!a.P_planar && ta16 >= 2 && tb16 >= 2 && (a.ntaps == 9 || a.ntaps == 16) && b.TG < a.ntaps &&
       !(a.ntaps == 16 && ta16 * tb16 >= 16)) {
     b.nw = a.ntaps; b.TG = a.ntaps;
-  } else if (nw_env && !a.P_planar && !a.G_planar && a.ntaps == 16 && ta16 == 4 && tb16 == 4) {
+  } else if (!a.P_planar && a.ntaps == 16 && ta16 == 4 && tb16 == 4) {
     b.nw = 8; b.TG = 16;               // 64x64 tiles, 16 taps: 8 waves x 2 taps (16 waves would spill at 128 VGPRs)
   }
   bool fits = false;
@@ -820,10 +766,9 @@ static int try_wgrad2(int dt, const WgradArgs& a, hipStream_t s) {
     fits = lds <= kV2MaxLds && wgrad2_patch_slots(b, dt, TB) <= (b.nw == 4 ? 16 : 8);
   }
   if (!fits) return 0;
-  // ("big" 256 / 512-pixel tiles for the 16x16 channel tile were measured in round 2 without a gain; the kernel keeps the template
-  // parameter for the planar-P tail weight gradient, which uses it)
+  // ("big" 256 / 512-pixel tiles for the 16x16 channel tile were measured in round 2 without a gain)
   b.Ca = a.Ca; b.Cb = a.Cb; b.Cb_valid = a.Cb_valid; b.Ca_valid = a.Ca_valid; b.ksz = a.ksz; b.ntaps = a.ntaps;
-  b.sA = a.sA; b.sB = a.sB; b.scale = a.scale; b.P_planar = a.P_planar; b.P_planes = a.P_planes; b.G_planar = a.G_planar;
+  b.sA = a.sA; b.sB = a.sB; b.scale = a.scale; b.P_planar = a.P_planar; b.P_planes = a.P_planes;
   for (int t = 0; t < 25; ++t) b.tap_off[t] = a.tap_off[t];
   const int tiles_ab = (a.Ca / TA) * (a.Cb / TB);
   const int zg = (a.ntaps + b.TG - 1) / b.TG;
@@ -838,36 +783,25 @@ static int try_wgrad2(int dt, const WgradArgs& a, hipStream_t s) {
   int occ = (int)((160 * 1024) / lds); if (occ > 6) occ = 6; if (occ < 1) occ = 1;
   long gx = (op_bytes < (200L << 20) ? 176L : 256L * occ) / ((long)tiles_ab * zg); if (gx < 1) gx = 1;
   if (!a.scratch) { set_error("wgrad: the partial-image scratch is required (no atomic flush path)"); return MMVAE_ERR_ARG; }
-  const bool partial = true;
-  if (partial) {
+  {
     // keep the partial images (written once, read once) below the bytes of the operands themselves
-    const long in_bytes = ((long)a.N * a.Hp * a.Wp * a.Ca + (long)a.N * a.Hg * a.Wg * a.Cb) * (long)dtype_size(dt);
-    long budget = in_bytes > (8L << 20) ? in_bytes : (8L << 20);
+    long budget = op_bytes > (8L << 20) ? op_bytes : (8L << 20);
     if (budget > (long)kWgradScratchBytes) budget = (long)kWgradScratchBytes;
     const long cap = budget / (wsize * 4);
     if (cap < 1) return 0;
     if (gx > cap) gx = cap;
-  } else {                                              // direct flush: keep the scattered atomics of a launch below ~3M
-    long cap = (3L << 20) / (wsize > 0 ? wsize : 1);
-    if (cap < 2) cap = 2;
-    if (gx > cap) gx = cap;
   }
   if (gx > b.g.ntiles) gx = b.g.ntiles;
   if (gx >= 8) gx &= ~7L;
-  b.xcd_walk = conv_xcd_walk();
-  b.dbg = 0;
-  if (partial) { b.dW = a.scratch; b.partial = 1; }
+  b.dW = a.scratch; b.partial = 1;
   const int rc = launch_wgrad2(dt, b, (int)gx, tiles_ab, zg, ta16, tb16, s);
   if (rc < 0) return rc;
-  if (partial) {
-    WgradReduceArgs u; memset(&u, 0, sizeof(u));
-    u.part = a.scratch; u.dW = a.dW; u.Ca = a.Ca; u.Cb = a.Cb; u.ntaps = a.ntaps; u.nparts = (int)gx;
-    u.Ca_valid = a.Ca_valid; u.Cb_valid = a.Cb_valid; u.sA = a.sA; u.sB = a.sB; u.scale = a.scale;
-    for (int t = 0; t < 25; ++t) u.tap_off[t] = a.tap_off[t];
-    const int rc2 = launch_wgrad_reduce(u, s);
-    if (rc2 < 0) return rc2;
-  }
-  return 1;
+  WgradReduceArgs u; memset(&u, 0, sizeof(u));
+  u.part = a.scratch; u.dW = a.dW; u.Ca = a.Ca; u.Cb = a.Cb; u.ntaps = a.ntaps; u.nparts = (int)gx;
+  u.Ca_valid = a.Ca_valid; u.Cb_valid = a.Cb_valid; u.sA = a.sA; u.sB = a.sB; u.scale = a.scale;
+  for (int t = 0; t < 25; ++t) u.tap_off[t] = a.tap_off[t];
+  const int rc2 = launch_wgrad_reduce(u, s);
+  return rc2 < 0 ? rc2 : 1;
 }
 
 #define MM_CHECK_RC(expr) do { const int rc__ = (expr); if (rc__ < 0) return rc__; } while (0)
@@ -879,7 +813,7 @@ int launch_wgrad(int dt, WgradArgs a, hipStream_t s) {
   }
   a.M = a.N * a.Hp * a.Wp;
   note_launch_bytes((double)a.N * ((double)a.Hp * a.Wp * (a.P_planar ? a.P_planes * 4.0 : a.Ca * (double)dtype_size(dt)) +
-                                   (double)a.Hg * a.Wg * (a.G_planar ? 1 : a.Cb) * (double)dtype_size(dt)));
+                                   (double)a.Hg * a.Wg * a.Cb * (double)dtype_size(dt)));
   if (a.Cb_valid <= 0 || a.Cb_valid > a.Cb) a.Cb_valid = a.Cb;
   if (a.Ca_valid <= 0 || a.Ca_valid > a.Ca) a.Ca_valid = a.Ca;
   if (a.M <= 0) return MMVAE_OK;
@@ -890,7 +824,7 @@ int launch_wgrad(int dt, WgradArgs a, hipStream_t s) {
     if (rcp != 0) return rcp < 0 ? rcp : MMVAE_OK;
     const int rc2 = try_wgrad2(dt, a, s);
     if (rc2 != 0) return rc2 < 0 ? rc2 : MMVAE_OK;
-    if (a.P_planar || a.G_planar) { set_error("wgrad: planar operands need the patch-tile kernel"); return MMVAE_ERR_UNSUPPORTED; }
+    if (a.P_planar) { set_error("wgrad: planar operands need the patch-tile kernel"); return MMVAE_ERR_UNSUPPORTED; }
   }
   const int TA = a.Ca >= 64 ? 64 : ((a.Ca + 15) / 16) * 16;
   const int TB = a.Cb >= 64 ? 64 : ((a.Cb + 15) / 16) * 16;

@@ -365,8 +365,7 @@ __global__ __launch_bounds__(128 * PAIRS, 2) void join_bwd_stream_kernel(JoinBwd
 }
 
 bool join_bwd_stream_ok(int dt, int OC, int C, int Hp, int Hg) {
-  constexpr int enabled = 1;
-  return enabled != 0 && dt == DT_BF16 && OC == 1 && C == 16 && Hp == 32 && Hg == 64;
+  return dt == DT_BF16 && OC == 1 && C == 16 && Hp == 32 && Hg == 64;
 }
 
 // Returns the number of blocks (= partial images per conv = rows of bn_part), <0 on error.

@@ -64,11 +64,6 @@ int op_pack_up(int dt, const ConvGeom& g, const float* w, void* dst, hipStream_t
   return MMVAE_OK;
 }
 
-// MMVAE_DEEP2_FRAG=0: keep the row-major [cout][tap][cin] packing for deep2_conv_kernel too (A/B of the layout; both are read correctly)
-static bool frag_enabled() {
-  constexpr bool v = true;
-  return v;
-}
 // does deep2_conv_kernel take this conv's down / up form at this place (large-side map Hl x Wl)?  fp8: its e4m3 form
 int op_deep2_down_ok(int dt, const ConvGeom& g, int Hl, int Wl, int fp8) {
   const int Hs = conv_down_size(Hl, g.k, g.s, g.p), Ws = conv_down_size(Wl, g.k, g.s, g.p);
@@ -94,11 +89,6 @@ bool op_pos_fwd_takes(const ConvGeom& g, int Hl, bool transposed) {
   const int nw = Cout / 32 < 8 ? Cout / 32 : 8;
   if ((Cout / 32) % nw != 0 || (64 * nw) % (Cin / 8) != 0) return false;
   return pos_conv_takes(g.k, g.s, g.p, transposed ? 1 : 0, Hi, Ho, Cin);
-}
-
-int op_frag_down(int dt, const ConvGeom& g, int Hl, int Wl, int fp8) { return frag_enabled() ? op_deep2_down_ok(dt, g, Hl, Wl, fp8) : 0; }
-int op_frag_up(int dt, const ConvGeom& g, int Hl, int Wl, int allow_empty_phases, int fp8) {
-  return frag_enabled() ? op_deep2_up_ok(dt, g, Hl, Wl, allow_empty_phases, fp8) : 0;
 }
 
 int op_run_down(int dt, int out_dt, const ConvGeom& g, const void* packed, int N, const void* L, int Hl, int Wl, void* S, int Hs, int Ws,

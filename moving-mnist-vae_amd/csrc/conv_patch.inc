@@ -315,15 +315,20 @@ __global__ __launch_bounds__(256, (MAXG <= 4 ? (CT16 == 1 ? 4 : (CT16 == 2 ? 3 :
     for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(bv[c][j]));
 #pragma unroll
   for (int j = 0; j < VE; ++j) { asm volatile("" ::"v"(psc[j])); asm volatile("" ::"v"(psh[j])); }
-  const TileWalk walk = xcd_tile_walk(g.ntiles, a.xcd_walk);
+  const TileWalk walk = xcd_tile_walk(g.ntiles);
+  // An always-true uniform test the compiler cannot see through, between the prefetch and the MFMA phase: the MFMA phase and the
+  // epilogue then do not count as executed on every trip, and their tile-invariant values are not hoisted out of the tile loop --
+  // hoisted, they stay live across it and the larger instantiations spill (second-source SO = 2 form: 5 -> 35 spilled VGPRs; 4x12: 20 -> 114)
+  int live = 1;
+  asm volatile("" : "+s"(live));
   int tile = walk.first;
   if (tile < walk.end) issue(tile);
   for (; tile < walk.end; tile += walk.step) {
     __syncthreads();                 // previous tile's fragment reads are done (also orders the block prologue)
-    if (!(a.dbg & 2)) commit(tile);
+    commit(tile);
     __syncthreads();
-    if (tile + walk.step < walk.end && !(a.dbg & 1)) issue(tile + walk.step);     // in flight during the MFMA phase
-    if (a.dbg & 4) continue;
+    if (tile + walk.step < walk.end) issue(tile + walk.step);     // in flight during the MFMA phase
+    if (!live) continue;
     int n_t, hq0_t;
     tile_origin(g, tile, 0, n_t, hq0_t);
     const unsigned cmul = a.y_planes > 0 ? 1u : (unsigned)a.Cout;
@@ -336,7 +341,7 @@ __global__ __launch_bounds__(256, (MAXG <= 4 ? (CT16 == 1 ? 4 : (CT16 == 2 ? 3 :
       for (int c = 0; c < CT16; ++c)
 #pragma unroll
         for (int pt = 0; pt < NPT; ++pt) acc[c][pt] = (f32x4){0, 0, 0, 0};
-      for (int ks = 0; ks < ((a.dbg & 32) ? 0 : nks); ++ks) {
+      for (int ks = 0; ks < nks; ++ks) {
         const int kv = 4 * ks + gq;
         const int koff = sK[kv];
         Vec16 af[CT16];
@@ -396,7 +401,7 @@ __global__ __launch_bounds__(256, (MAXG <= 4 ? (CT16 == 1 ? 4 : (CT16 == 2 ? 3 :
         for (int pt = 0; pt < NPT; ++pt) {
           const int hq = ohq[pt], wq = pwq[pt];
           const unsigned ob = obase[pt] + ph_off;
-          if (hq < P.Hq && wq < P.Wq && !(a.dbg & 8)) {
+          if (hq < P.Hq && wq < P.Wq) {
             if (a.y_planes > 0) {
               // NCHW f32 output with y_planes (<= 16) real channels: the reconstruction layout of the reference
               if (gq * 4 < a.y_planes) {
@@ -461,7 +466,7 @@ __global__ __launch_bounds__(256, (MAXG <= 4 ? (CT16 == 1 ? 4 : (CT16 == 2 ? 3 :
               // channel-quad planes [pt][pw][c][gq] of 16 q x 4 channels: the 16 lanes of one gq write 16 consecutive
               // quads (conflict-free), the 16-byte skew of the plane pitch spreads the read-back over the banks
               TO* dst = reinterpret_cast<TO*>(sOutW + (((pt * a.SO + pw) * CT16) * 4 + gq) * kOutPitch) + r * 4;
-              const bool rowok = has_stats && !(a.dbg & 64) && hq0_t + col_row(pt) < g.Hq;
+              const bool rowok = has_stats && hq0_t + col_row(pt) < g.Hq;
 #pragma unroll
               for (int c = 0; c < CT16; ++c) {
                 if (16 * c < a.Cout) {                     // Cout is a multiple of 16 here: uniform
@@ -476,7 +481,7 @@ __global__ __launch_bounds__(256, (MAXG <= 4 ? (CT16 == 1 ? 4 : (CT16 == 2 ? 3 :
 #pragma unroll
                     for (int jj = 0; jj < 4; ++jj) { st1[c][jj] += v[jj]; st2[c][jj] += v[jj] * v[jj]; }
                   }
-                  if (!(a.dbg & 16)) pstore4<TO>(reinterpret_cast<TO*>(reinterpret_cast<char*>(dst) + c * 4 * kOutPitch), v, false);
+                  pstore4<TO>(reinterpret_cast<TO*>(reinterpret_cast<char*>(dst) + c * 4 * kOutPitch), v, false);
                 }
               }
             }
@@ -485,53 +490,51 @@ __global__ __launch_bounds__(256, (MAXG <= 4 ? (CT16 == 1 ? 4 : (CT16 == 2 ? 3 :
         // ---- wave-private LDS -> global, 16 bytes per lane (LDS operations of one wave complete in order)
         __builtin_amdgcn_wave_barrier();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (!(a.dbg & 8)) {
-          if (a.y_planes > 0) {
-            // the wave's NPT*16 pixels are consecutive in memory (whole rows of one image plane)
-            float* Yp = reinterpret_cast<float*>(a.y);
-            const unsigned hw = (unsigned)a.Ho * a.Wo;
-            const unsigned pix0o = ((unsigned)n_t * a.y_planes * a.Ho + (unsigned)(hq0_t + col_row(0))) * a.Wo + col_wq0(0);
-            const int nrows_ok = g.Hq - (hq0_t + col_row(0));                         // rows of this wave inside the image
-            const int npx = min(NPT * 16, nrows_ok * g.Wq);
-            // (no real loop here: a loop with stores would make the compiler wait for the prefetch in its preheader)
-            const int i = lane * 4;                   // NPT*16 <= 128 pixels: one float4 per lane covers the run
+        if (a.y_planes > 0) {
+          // the wave's NPT*16 pixels are consecutive in memory (whole rows of one image plane)
+          float* Yp = reinterpret_cast<float*>(a.y);
+          const unsigned hw = (unsigned)a.Ho * a.Wo;
+          const unsigned pix0o = ((unsigned)n_t * a.y_planes * a.Ho + (unsigned)(hq0_t + col_row(0))) * a.Wo + col_wq0(0);
+          const int nrows_ok = g.Hq - (hq0_t + col_row(0));                         // rows of this wave inside the image
+          const int npx = min(NPT * 16, nrows_ok * g.Wq);
+          // (no real loop here: a loop with stores would make the compiler wait for the prefetch in its preheader)
+          const int i = lane * 4;                   // NPT*16 <= 128 pixels: one float4 per lane covers the run
 #pragma unroll
-            for (int pl = 0; pl < 16; ++pl) {
-              if (pl < a.y_planes && i < npx)
-                *reinterpret_cast<float4*>(Yp + pix0o + pl * hw + i) = *reinterpret_cast<const float4*>(sOutW + (pl * (NPT * 16) + i) * 4);
-            }
-          } else {
-            const int pt_bytes = a.SO * CT16 * 4 * kOutPitch;                          // LDS bytes of one column tile
+          for (int pl = 0; pl < 16; ++pl) {
+            if (pl < a.y_planes && i < npx)
+              *reinterpret_cast<float4*>(Yp + pix0o + pl * hw + i) = *reinterpret_cast<const float4*>(sOutW + (pl * (NPT * 16) + i) * 4);
+          }
+        } else {
+          const int pt_bytes = a.SO * CT16 * 4 * kOutPitch;                          // LDS bytes of one column tile
 #pragma unroll
-            for (int pt = 0; pt < NPT; ++pt) {
-              const int hq = hq0_t + col_row(pt);
-              if (hq < g.Hq) {
-                const unsigned ob = (((unsigned)n_t * a.Ho + (unsigned)(hq * a.SO + ph)) * a.Wo + (unsigned)col_wq0(pt) * a.SO) * (unsigned)a.Cout;
-                char* gdst = reinterpret_cast<char*>(Y + ob);
-                const char* lsrc = sOutW + pt * pt_bytes;
+          for (int pt = 0; pt < NPT; ++pt) {
+            const int hq = hq0_t + col_row(pt);
+            if (hq < g.Hq) {
+              const unsigned ob = (((unsigned)n_t * a.Ho + (unsigned)(hq * a.SO + ph)) * a.Wo + (unsigned)col_wq0(pt) * a.SO) * (unsigned)a.Cout;
+              char* gdst = reinterpret_cast<char*>(Y + ob);
+              const char* lsrc = sOutW + pt * pt_bytes;
 #pragma unroll
-                for (int it = 0; it < kOutIters; ++it) {
-                  const int i = lane + 64 * it;
-                  if (i < run16) {
-                    Vec16 q;
-                    if constexpr (sizeof(TO) == 2) {
-                      const uint2 lo = *reinterpret_cast<const uint2*>(lsrc + rb_off[it]);
-                      const uint2 hi = *reinterpret_cast<const uint2*>(lsrc + rb_off[it] + kOutPitch);
-                      q.w[0] = lo.x; q.w[1] = lo.y; q.w[2] = hi.x; q.w[3] = hi.y;
-                    } else {
-                      q = *reinterpret_cast<const Vec16*>(lsrc + rb_off[it]);
-                    }
-                    if constexpr (ACC) {
-                      const Vec16 e = *reinterpret_cast<const Vec16*>(gdst + i * 16);
-                      constexpr int VO = 16 / sizeof(TO);
-                      float fa[VO], fb[VO];
-                      Elem<TO>::unpack(q, fa); Elem<TO>::unpack(e, fb);
-#pragma unroll
-                      for (int j = 0; j < VO; ++j) fa[j] += fb[j];
-                      q = Elem<TO>::pack(fa);
-                    }
-                    *reinterpret_cast<Vec16*>(gdst + i * 16) = q;
+              for (int it = 0; it < kOutIters; ++it) {
+                const int i = lane + 64 * it;
+                if (i < run16) {
+                  Vec16 q;
+                  if constexpr (sizeof(TO) == 2) {
+                    const uint2 lo = *reinterpret_cast<const uint2*>(lsrc + rb_off[it]);
+                    const uint2 hi = *reinterpret_cast<const uint2*>(lsrc + rb_off[it] + kOutPitch);
+                    q.w[0] = lo.x; q.w[1] = lo.y; q.w[2] = hi.x; q.w[3] = hi.y;
+                  } else {
+                    q = *reinterpret_cast<const Vec16*>(lsrc + rb_off[it]);
                   }
+                  if constexpr (ACC) {
+                    const Vec16 e = *reinterpret_cast<const Vec16*>(gdst + i * 16);
+                    constexpr int VO = 16 / sizeof(TO);
+                    float fa[VO], fb[VO];
+                    Elem<TO>::unpack(q, fa); Elem<TO>::unpack(e, fb);
+#pragma unroll
+                    for (int j = 0; j < VO; ++j) fa[j] += fb[j];
+                    q = Elem<TO>::pack(fa);
+                  }
+                  *reinterpret_cast<Vec16*>(gdst + i * 16) = q;
                 }
               }
             }

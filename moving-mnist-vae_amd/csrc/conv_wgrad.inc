@@ -15,8 +15,7 @@
 //
 // Accumulators persist in registers across the block's tiles.  Flush: every block stores its partial image
 // [part = blockIdx.x][tap][a][b] with plain coalesced stores and wgrad_reduce_kernel sums the parts into the PyTorch
-// weight layout (no atomics on the hot path, grid sized by occupancy).  Without a scratch buffer the block falls back
-// to global float atomics.
+// weight layout (no atomics, grid sized by occupancy).
 //
 // LDS carve: [P tile: TP x TA][G patch: npatch x TB][sToff: 32 ints]; the flush staging image aliases the front.
 // Work split over the 4 waves of a block:
@@ -44,16 +43,12 @@ __device__ __forceinline__ Vec16 apply_pro(const Vec16& q, const float* sc, cons
   return Elem<T>::pack(f);
 }
 
-// BIG (tap-split mode only): tiles of 256 / 512 P-pixels = whole rows of a P grid whose width is a power of two >= 32
-// and whose height is a multiple of the tile's rows.  Every 32-pixel k-step then lies in one row, its LDS offsets are
-// a wave-uniform term plus a per-lane constant, and the k-loop is a runtime loop (TP / 32 steps).
 // NW = waves per block.  4: the default.  9 / 16 (deep layers, 3x3 / 4x4 kernels): ONE tap per wave, so the block covers every
 // tap of its (a, b) tile and the P tile / G patch are staged once instead of once per tap group.
-template <typename T, int TA16, int TB16, bool TS, int MAXG, bool PPL, bool BIG, bool GPL = false, int NW = 4>
+template <typename T, int TA16, int TB16, bool TS, int MAXG, bool PPL, int NW = 4>
 __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : (NW == 9 ? 3 : (NW == 8 ? 2 : (MAXG <= 8 ? 3 : 2) - (TA16 * TB16 > 2 ? 1 : 0)))) void wgrad2_kernel(Wgrad2Args a) {
   static_assert(NW == 4 || TS, "one-tap-per-wave blocks are tap-split");
   constexpr int NT = 64 * NW;
-  static_assert(!BIG || TS, "big tiles need the tap-split mode");
   constexpr int VE = Elem<T>::kVec;
   constexpr int ES = sizeof(T);
   constexpr int TA = TA16 * 16, TB = TB16 * 16;
@@ -61,7 +56,7 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : (NW == 9 ? 3 : (NW == 8 ? 2
   constexpr int NKS = TS ? 4 : 1;
   constexpr int CVG = TB / VE, PSG = NT / CVG;          // 16-byte vectors per G pixel; patch pixels per slot round
   constexpr int CVP = TA / VE, PSP = NT / CVP;
-  constexpr int MAXP = ((BIG ? 512 : 128) + PSP - 1) / PSP;   // P-tile slots per thread (TP <= 128, BIG: <= 512)
+  constexpr int MAXP = (128 + PSP - 1) / PSP;       // P-tile slots per thread (TP <= 128)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const TileGeom g = a.g;
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6, gq = lane >> 4, r = lane & 15;
@@ -82,9 +77,7 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : (NW == 9 ? 3 : (NW == 8 ? 2
     sToff[t] = (kh * g.PW + kw) * TB * ES;          // patch origin is (q*SI - pad): tap (kh,kw) sits at +kh rows, +kw cols
   }
   // ---- this thread's staging slots (tile-invariant)
-  // (GPL: G is planar T [N][1][Hi][Wi], the 1-channel image: slot k = patch pixel t + 256k, staged as TB zero-padded channels)
-  const int cvp = t % CVP, pp0 = t / CVP, cvg = GPL ? 0 : t % CVG, gp0 = GPL ? t : t / CVG;
-  constexpr int PSGe = GPL ? NT : PSG;
+  const int cvp = t % CVP, pp0 = t / CVP, cvg = t % CVG, gp0 = t / CVG;
   float xsc[VE], xsh[VE];      // BN scale / shift of the ONE operand that has a load prologue (never both: see the launcher)
 #pragma unroll
   for (int j = 0; j < VE; ++j) {
@@ -94,7 +87,7 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : (NW == 9 ? 3 : (NW == 8 ? 2
   int goff[MAXG], gchk[MAXG];
 #pragma unroll
   for (int k = 0; k < MAXG; ++k) {
-    const int pp = gp0 + k * PSGe;
+    const int pp = gp0 + k * PSG;
     goff[k] = 0; gchk[k] = kSlotInvalid;
     if (pp < npatch) {
       const int row = pp / g.PW, pc = pp - row * g.PW;
@@ -102,14 +95,11 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : (NW == 9 ? 3 : (NW == 8 ? 2
       const int wi = g.ow + pc;
       bool ok = wi >= 0 && wi < g.Wi;
       if (multi) ok = ok && g.oh + pr >= 0 && g.oh + pr < g.Hi;       // whole-image tiles: the row check is static too
-      goff[k] = GPL ? (seg * g.Hi + pr) * g.Wi + wi : ((seg * g.Hi + pr) * g.Wi + wi) * a.Cb + b0 + cvg * VE;
+      goff[k] = ((seg * g.Hi + pr) * g.Wi + wi) * a.Cb + b0 + cvg * VE;
       if (ok) gchk[k] = multi ? seg : pr;
     }
   }
   const unsigned lim = multi ? g.N : g.Hi;
-  if constexpr (GPL) {
-    for (int v = t; v < npatch * CVG; v += NT) reinterpret_cast<Vec16*>(sG)[v] = Vec16{{0, 0, 0, 0}};
-  }
   f32x4 acc[MAXT][TA16][TB16];
 #pragma unroll
   for (int tl = 0; tl < MAXT; ++tl)
@@ -120,14 +110,7 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : (NW == 9 ? 3 : (NW == 8 ? 2
   const int npix_tile = g.segs * g.qr * g.Wq;       // pixel slots of one tile
   // tile-independent LDS offsets of this lane's fragment pixels (bf16: 2 four-pixel blocks per k-step)
   int offP[NKS][2], offG[NKS][2];
-  int lanePb[2], laneGb[2];                          // BIG: per-lane constants of the two 4-pixel blocks
-#pragma unroll
-  for (int b = 0; b < 2; ++b) {
-    const int lp = 16 * b + 4 * gq + (r >> 2);
-    lanePb[b] = lp * TA * ES + (r & 3) * 8;
-    laneGb[b] = lp * g.SI * TB * ES + (r & 3) * 8;
-  }
-  if constexpr (sizeof(T) == 2 && !BIG) {
+  if constexpr (sizeof(T) == 2) {
 #pragma unroll
     for (int i = 0; i < NKS; ++i)
 #pragma unroll
@@ -155,14 +138,11 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : (NW == 9 ? 3 : (NW == 8 ? 2
     nv_c = (int)(mend - m0);
     const int h_base = hq0 * g.SI + g.oh;
     tb_c = multi ? n : h_base;
-    const T* gsrc = Gp + ((long)n * g.Hi + h_base) * g.Wi * (GPL ? 1 : a.Cb);
+    const T* gsrc = Gp + ((long)n * g.Hi + h_base) * g.Wi * a.Cb;
 #pragma unroll
     for (int k = 0; k < MAXG; ++k) {
       gv[k] = Vec16{{0, 0, 0, 0}};
-      if ((unsigned)(tb_c + gchk[k]) < lim) {
-        if constexpr (GPL) gv[k].w[0] = __float_as_uint(Elem<T>::load(gsrc + goff[k]));
-        else gv[k] = *reinterpret_cast<const Vec16*>(gsrc + goff[k]);
-      }
+      if ((unsigned)(tb_c + gchk[k]) < lim) gv[k] = *reinterpret_cast<const Vec16*>(gsrc + goff[k]);
     }
     if constexpr (!PPL) {
       const T* psrc = Pp + m0 * a.Ca + a0 + cvp * VE;
@@ -192,20 +172,11 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : (NW == 9 ? 3 : (NW == 8 ? 2
   auto commit = [&]() {
 #pragma unroll
     for (int k = 0; k < MAXG; ++k) {
-      const int pp = gp0 + k * PSGe;
+      const int pp = gp0 + k * PSG;
       if (pp < npatch) {
-        if constexpr (GPL) {
-          // channel 0 = the image value, channels 1.. of the first vector zero; the other vectors were zeroed once
-          float f[VE];
-#pragma unroll
-          for (int j = 0; j < VE; ++j) f[j] = 0.f;
-          f[0] = __uint_as_float(gv[k].w[0]);
-          reinterpret_cast<Vec16*>(sG)[pp * CVG] = Elem<T>::pack(f);
-        } else {
-          Vec16 q = gv[k];
-          if (proG && (unsigned)(tb_c + gchk[k]) < lim) q = apply_pro<T, VE>(q, xsc, xsh, a.proG_relu);   // padding stays exactly zero
-          reinterpret_cast<Vec16*>(sG)[pp * CVG + cvg] = q;
-        }
+        Vec16 q = gv[k];
+        if (proG && (unsigned)(tb_c + gchk[k]) < lim) q = apply_pro<T, VE>(q, xsc, xsh, a.proG_relu);   // padding stays exactly zero
+        reinterpret_cast<Vec16*>(sG)[pp * CVG + cvg] = q;
       }
     }
 #pragma unroll
@@ -241,7 +212,7 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : (NW == 9 ? 3 : (NW == 8 ? 2
   for (int j = 0; j < VE; ++j) {
     asm volatile("" ::"v"(xsc[j])); asm volatile("" ::"v"(xsh[j]));
   }
-  const TileWalk walk = xcd_tile_walk(g.ntiles, a.xcd_walk);
+  const TileWalk walk = xcd_tile_walk(g.ntiles);
   int tile = walk.first;
   if (tile < walk.end) issue(tile);
   for (; tile < walk.end; tile += walk.step) {
@@ -249,27 +220,7 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : (NW == 9 ? 3 : (NW == 8 ? 2
     commit();
     __syncthreads();
     if (tile + walk.step < walk.end) issue(tile + walk.step);     // in flight during the MFMA phase
-    if constexpr (sizeof(T) == 2 && BIG) {
-      for (int i = 0; i < nks_tile; ++i) {
-        const int uP = i * 32 * TA * ES;
-        const int uG = ((((32 * i) >> a.wq_shift) * g.SI) * g.PW + ((32 * i) & (g.Wq - 1)) * g.SI) * TB * ES;
-        Vec16 af[TA16];
-#pragma unroll
-        for (int ta = 0; ta < TA16; ++ta) af[ta] = FragOps<bf16_t>::load(sP, uP + lanePb[0] + ta * 32, uP + lanePb[1] + ta * 32);
-#pragma unroll
-        for (int tl = 0; tl < MAXT; ++tl) {
-          if (my_tap[tl] < tg_n) {
-            const int toff = sToff[my_tap[tl]] + uG;
-#pragma unroll
-            for (int tb = 0; tb < TB16; ++tb) {
-              const Vec16 bf = FragOps<bf16_t>::load(sG, laneGb[0] + toff + tb * 32, laneGb[1] + toff + tb * 32);
-#pragma unroll
-              for (int ta = 0; ta < TA16; ++ta) acc[tl][ta][tb] = mma_bf16(af[ta], bf, acc[tl][ta][tb]);
-            }
-          }
-        }
-      }
-    } else if constexpr (sizeof(T) == 2) {
+    if constexpr (sizeof(T) == 2) {
 #pragma unroll
       for (int i = 0; i < NKS; ++i) {
         if (TS && i >= nks_tile) break;
@@ -291,7 +242,7 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : (NW == 9 ? 3 : (NW == 8 ? 2
       }
     } else {
       // ---- f32 (validation mode): 8 MFMA 16x16x4 steps per 32-pixel k-step; pixel of (step j, group gq): 32ks + 4j + gq
-      for (int i = 0; i < (BIG ? nks_tile : NKS); ++i) {
+      for (int i = 0; i < NKS; ++i) {
         if (TS && i >= nks_tile) break;
         const int ks = TS ? i : wv;
         for (int j = 0; j < 8; ++j) {
@@ -359,10 +310,8 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? 4 : (NW == 9 ? 3 : (NW == 8 ? 2
         }
         __syncthreads();
       }
-      {   // (the launcher always provides the partial-image scratch: a.partial == 1)
-        float* dst = a.dW + (((long)blockIdx.x * a.ntaps + tap0 + tap_l) * a.Ca + a0) * a.Cb + b0;
-        for (int i = t; i < TA * TB; i += NT) dst[(long)(i / TB) * a.Cb + (i % TB)] = sAcc[i];
-      }
+      float* dst = a.dW + (((long)blockIdx.x * a.ntaps + tap0 + tap_l) * a.Ca + a0) * a.Cb + b0;
+      for (int i = t; i < TA * TB; i += NT) dst[(long)(i / TB) * a.Cb + (i % TB)] = sAcc[i];
       __syncthreads();
     }
   }
@@ -376,17 +325,17 @@ static int launch_wgrad2_t(Wgrad2Args a, int dt, dim3 grid, int ta16, int tb16, 
   if (a.nw != 4) {
     // one tap per wave (deep layers): 64x64, 64x32, 32x64 tiles, 9 or 16 waves
     if (a.nw == 8) {
-      if (ta16 != 4 || tb16 != 4 || a.P_planar || a.G_planar || a.big || !ts || maxg > 8) { set_error("wgrad2: nw=8 needs the 64x64 tile"); return MMVAE_ERR_UNSUPPORTED; }
-      if (maxg <= 4) hipLaunchKernelGGL((wgrad2_kernel<T, 4, 4, true, 4, false, false, false, 8>), grid, block, lds, s, a);
-      else hipLaunchKernelGGL((wgrad2_kernel<T, 4, 4, true, 8, false, false, false, 8>), grid, block, lds, s, a);
+      if (ta16 != 4 || tb16 != 4 || a.P_planar || !ts || maxg > 8) { set_error("wgrad2: nw=8 needs the 64x64 tile"); return MMVAE_ERR_UNSUPPORTED; }
+      if (maxg <= 4) hipLaunchKernelGGL((wgrad2_kernel<T, 4, 4, true, 4, false, 8>), grid, block, lds, s, a);
+      else hipLaunchKernelGGL((wgrad2_kernel<T, 4, 4, true, 8, false, 8>), grid, block, lds, s, a);
       return check_launch("wgrad2");
     }
-    if (a.P_planar || a.G_planar || a.big || !ts || maxg > 8 || (a.nw != 9 && a.nw != 16)) { set_error("wgrad2: nw=%d unsupported here", a.nw); return MMVAE_ERR_UNSUPPORTED; }
+    if (a.P_planar || !ts || maxg > 8 || (a.nw != 9 && a.nw != 16)) { set_error("wgrad2: nw=%d unsupported here", a.nw); return MMVAE_ERR_UNSUPPORTED; }
 #define MMVAE_W2N(A_, B_) do { \
-    if (a.nw == 9) { if (maxg <= 4) hipLaunchKernelGGL((wgrad2_kernel<T, A_, B_, true, 4, false, false, false, 9>), grid, block, lds, s, a); \
-                     else hipLaunchKernelGGL((wgrad2_kernel<T, A_, B_, true, 8, false, false, false, 9>), grid, block, lds, s, a); } \
-    else { if (maxg <= 4) hipLaunchKernelGGL((wgrad2_kernel<T, A_, B_, true, 4, false, false, false, 16>), grid, block, lds, s, a); \
-           else hipLaunchKernelGGL((wgrad2_kernel<T, A_, B_, true, 8, false, false, false, 16>), grid, block, lds, s, a); } } while (0)
+    if (a.nw == 9) { if (maxg <= 4) hipLaunchKernelGGL((wgrad2_kernel<T, A_, B_, true, 4, false, 9>), grid, block, lds, s, a); \
+                     else hipLaunchKernelGGL((wgrad2_kernel<T, A_, B_, true, 8, false, 9>), grid, block, lds, s, a); } \
+    else { if (maxg <= 4) hipLaunchKernelGGL((wgrad2_kernel<T, A_, B_, true, 4, false, 16>), grid, block, lds, s, a); \
+           else hipLaunchKernelGGL((wgrad2_kernel<T, A_, B_, true, 8, false, 16>), grid, block, lds, s, a); } } while (0)
     if (ta16 == 4 && tb16 == 4) MMVAE_W2N(4, 4);
     else if (ta16 == 4 && tb16 == 2) MMVAE_W2N(4, 2);
     else if (ta16 == 2 && tb16 == 4) MMVAE_W2N(2, 4);
@@ -395,26 +344,13 @@ static int launch_wgrad2_t(Wgrad2Args a, int dt, dim3 grid, int ta16, int tb16, 
 #undef MMVAE_W2N
     return check_launch("wgrad2");
   }
-#define MMVAE_W2G(A_, B_, G_) do { if (ts) hipLaunchKernelGGL((wgrad2_kernel<T, A_, B_, true, G_, false, false>), grid, block, lds, s, a); \
-                                   else hipLaunchKernelGGL((wgrad2_kernel<T, A_, B_, false, G_, false, false>), grid, block, lds, s, a); } while (0)
+#define MMVAE_W2G(A_, B_, G_) do { if (ts) hipLaunchKernelGGL((wgrad2_kernel<T, A_, B_, true, G_, false>), grid, block, lds, s, a); \
+                                   else hipLaunchKernelGGL((wgrad2_kernel<T, A_, B_, false, G_, false>), grid, block, lds, s, a); } while (0)
 #define MMVAE_W2(A_, B_) do { if (maxg <= 8) MMVAE_W2G(A_, B_, 8); else MMVAE_W2G(A_, B_, 16); } while (0)
-  if (a.G_planar) {
-    if (ta16 != 2 || tb16 != 1 || !ts || a.big || a.P_planar) { set_error("wgrad2: planar G needs the 32x16 tap-split tile"); return MMVAE_ERR_UNSUPPORTED; }
-    if (maxg <= 8) hipLaunchKernelGGL((wgrad2_kernel<T, 2, 1, true, 8, false, false, true>), grid, block, lds, s, a);
-    else hipLaunchKernelGGL((wgrad2_kernel<T, 2, 1, true, 16, false, false, true>), grid, block, lds, s, a);
-  } else if (a.P_planar) {
+  if (a.P_planar) {
     if (ta16 != 1 || tb16 != 1 || !ts) { set_error("wgrad2: planar P needs the 16x16 tap-split tile"); return MMVAE_ERR_UNSUPPORTED; }
-    if (a.big) {
-      if (maxg <= 8) hipLaunchKernelGGL((wgrad2_kernel<T, 1, 1, true, 8, true, true>), grid, block, lds, s, a);
-      else hipLaunchKernelGGL((wgrad2_kernel<T, 1, 1, true, 16, true, true>), grid, block, lds, s, a);
-    } else {
-      if (maxg <= 8) hipLaunchKernelGGL((wgrad2_kernel<T, 1, 1, true, 8, true, false>), grid, block, lds, s, a);
-      else hipLaunchKernelGGL((wgrad2_kernel<T, 1, 1, true, 16, true, false>), grid, block, lds, s, a);
-    }
-  } else if (a.big) {
-    if (ta16 != 1 || tb16 != 1 || !ts) { set_error("wgrad2: big tiles need the 16x16 tap-split tile"); return MMVAE_ERR_UNSUPPORTED; }
-    if (maxg <= 8) hipLaunchKernelGGL((wgrad2_kernel<T, 1, 1, true, 8, false, true>), grid, block, lds, s, a);
-    else hipLaunchKernelGGL((wgrad2_kernel<T, 1, 1, true, 16, false, true>), grid, block, lds, s, a);
+    if (maxg <= 8) hipLaunchKernelGGL((wgrad2_kernel<T, 1, 1, true, 8, true>), grid, block, lds, s, a);
+    else hipLaunchKernelGGL((wgrad2_kernel<T, 1, 1, true, 16, true>), grid, block, lds, s, a);
   } else if (ta16 == 1 && tb16 == 1) MMVAE_W2(1, 1);
   else if (ta16 == 1 && tb16 == 2) MMVAE_W2(1, 2);
   else if (ta16 == 2 && tb16 == 1) MMVAE_W2(2, 1);

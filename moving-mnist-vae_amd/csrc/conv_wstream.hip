@@ -518,17 +518,13 @@ static int launch_wstream_t(const WStreamArgs& a, int gx, hipStream_t s) {
   return check_launch("wgrad_stream");
 }
 
-static bool wstream_enabled() {
-  constexpr int enabled = 1;
-  return enabled != 0;
-}
 // The geometries with an instantiation (kind):
 //   1  ConvTranspose2d k4 s2 p1 on 32-wide P rows, G 16 channels, P 16 / 32 channels      (decoder.uplayer5.conv2 / .upsample)
 //   2  the same on 16-wide P rows (two rows per step)                                       (decoder.uplayer4.conv2 / .upsample)
 //   3  Conv2d 3x3 s1 p1, 32 -> 32 channels, 16-wide maps                                    (encoder.layer1.conv2)
 //   4  Conv2d 3x3 s2 p1, 32 -> 32 channels, 16-wide P (dy) rows, 32-wide G rows             (encoder.layer1.conv1)
 static int wstream_kind(int dt, const WgradArgs& a) {
-  if (!wstream_enabled() || dt != DT_BF16 || a.P_planar || a.G_planar || !a.scratch) return 0;
+  if (dt != DT_BF16 || a.P_planar || !a.scratch) return 0;
   if (a.ntaps != a.ksz * a.ksz || a.Cb_valid != a.Cb || a.Ca_valid != a.Ca) return 0;
   for (int t = 0; t < a.ntaps; ++t) if (a.tap_off[t] != t) return 0;
   if (a.Wg != a.stride * a.Wp || a.Hg != a.stride * a.Hp || a.Hp != a.Wp) return 0;
@@ -572,7 +568,7 @@ bool wgrad_stream_shape(int dt, const WgradArgs& a) {
   return wstream_kind(dt, a) != 0 && !(a.proP_scale && a.proG_scale);
 }
 
-// Returns 1 when the launch was taken (kernel + reduce enqueued), 0 when the shape is not this kernel's, <0 on error.  MMVAE_WSTREAM=0: off
+// Returns 1 when the launch was taken (kernel + reduce enqueued), 0 when the shape is not this kernel's, <0 on error.
 int try_wgrad_stream(int dt, const WgradArgs& a, hipStream_t s) {
   const int kind = wstream_kind(dt, a);
   if (!kind) return 0;
@@ -623,15 +619,13 @@ int try_wgrad_stream_pair(int dt, const WgradArgs& a, const void* P2, float* dW2
   return rc2 < 0 ? rc2 : 1;
 }
 
-// Weight gradient AND data gradient (w.r.t. P) of a ConvTranspose2d k4 s2 p1 layer with 16 output channels in one pass over G
-// (MMVAE_WSTREAM_DG=0: off).
+// Weight gradient AND data gradient (w.r.t. P) of a ConvTranspose2d k4 s2 p1 layer with 16 output channels in one pass over G.
 //   wd: the conv's packed down form [Ca][16][Cb]; dx [N][Hp][Wp][Ca]; x2 / w2 (optional): the 1x1 shortcut's operand on the P grid and its
 //   packed [Ca][16] matrix; bn_part (optional, needs the prologue, Ca = 16 and no x2): [blocks][2][16] BatchNorm-backward sums of P's BatchNorm.
 //   Returns the number of blocks (> 0) when taken, 0 when the shape is not this kernel's, <0 on error.
 bool dgrad_wgrad_stream_shape(int dt, const WgradArgs& a) {
-  constexpr int enabled = 1;
   const int kind = wstream_kind(dt, a);
-  return enabled != 0 && (kind == 1 || kind == 2) && !a.proG_scale;
+  return (kind == 1 || kind == 2) && !a.proG_scale;
 }
 // jg (optional): G is the join's masked output gradient and dy = jg->A * G + jg->B * jg->y + jg->C is evaluated on load (JG above); the
 // instantiated forms are the two a DeconvBottleneck on 16-wide maps needs: (Ca 16, prologue, BatchNorm sums) and (Ca 32, second source).

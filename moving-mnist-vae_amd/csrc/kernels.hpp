@@ -29,7 +29,6 @@ struct GatherArgs {
   int cin_vecs;
   // optional boundary layouts (patch-tile kernels only):
   int x_planar, x_planes;  // 1: x is planar f32 [N][x_planes][Hi][Wi], 2: planar T; staged as Cin=16 channels, zero padded
-  int dbg;                 // developer switches (MMVAE_DBG): bit0 skip global loads, bit1 skip stores, bit2 skip MFMA
   int y_planes;            // >0: y is NCHW f32 [N][y_planes][Ho][Wo] (Cout = 16 padded GEMM rows; stats rows have y_planes channels)
   // optional SECOND source (patch-tile kernel only; launch_gather_gemm returns MMVAE_ERR_UNSUPPORTED when it cannot take it):
   // y[q-pixel of phase (x2_ph, x2_pw)] += sum_c2 x2[n, hq, wq, c2] * w2[co][c2] -- a 1x1 convolution of a tensor that lives on the
@@ -57,7 +56,6 @@ struct WgradArgs {
   int Cb_valid;            // b >= Cb_valid is computed but not written (0 -> Cb)
   int Ca_valid;            // likewise for a (0 -> Ca)
   int P_planar, P_planes;  // 1: P is planar f32 [N][P_planes][Hp][Wp] (patch-tile kernel only; Ca = 16, Ca_valid = P_planes)
-  int G_planar;            // 1: G is planar T [N][1][Hg][Wg] (patch-tile kernel only; Cb = 16, Cb_valid = 1)
   float* scratch;          // optional, kWgradScratchBytes: per-block partial images [part][tap][a][b], summed by wgrad_reduce_kernel
   int stride, pad, ksz;
   int sA, sB; int ntaps; int tap_off[25];
@@ -118,19 +116,18 @@ struct TileGeom { int N, Hq, Wq, Hi, Wi, SI, oh, ow, segs, qr, PR, PW, tiles_per
 bool make_tile_geom(TileGeom& g, int N, int Hq, int Wq, int Hi, int Wi, int SI, int oh, int ow, int span_h, int span_w, int TP = 128,
                     int sub = 1);
 struct Wgrad2Args {
-  const void* P; const void* G; float* dW;
+  const void* P; const void* G; float* dW;   // dW: the partial-image scratch [gridDim.x][ntaps][Ca][Cb] (plain stores)
   const float* proP_scale; const float* proP_shift; int proP_relu;
   const float* proG_scale; const float* proG_shift; int proG_relu;
   TileGeom g;
   int Ca, Cb, Cb_valid, Ca_valid, ksz, ntaps, TG;
   int sA, sB; int tap_off[25]; float scale;
   int P_planar, P_planes;  // 1: P is planar f32 [N][P_planes][Hq][Wq] staged as Ca = 16 zero-padded channels
-  int G_planar;            // 1: G is planar T [N][1][Hi][Wi] (the 1-channel image) staged as Cb = 16 zero-padded channels
-  int xcd_walk;            // XCD-aware tile order (tile_common.hpp)
-  int dbg;                 // developer switches (MMVAE_DBG): 1 skip loads, 2 skip LDS commit, 4 skip MFMA phase
   int nw;                  // waves per block: 4, or 9 / 16 = one tap per wave (deep 3x3 / 4x4 layers)
-  int big, wq_shift;       // big tiles (256 / 512 P-pixels, see conv_wgrad.inc); log2(Wq)
-  int partial;             // 1: dW is the partial-image scratch [gridDim.x][ntaps][Ca][Cb] (plain stores); 0: atomics into the weight layout
+  // 1 (what the launcher sets): tap-split blocks store their accumulators straight into the partial image; 0: through the LDS image of the
+  // k-split flush (same result).  Kept as a runtime value: with the test resolved at compile time the 16x16-tile instantiations spill
+  // (0 -> 32..196 bytes of scratch)
+  int partial;
 };
 size_t wgrad2_lds_bytes(const Wgrad2Args& a, int dt, int TA, int TB);
 int wgrad2_patch_slots(const Wgrad2Args& a, int dt, int TB);
@@ -154,10 +151,8 @@ struct PatchArgs {
   int w_vecs, koff_total;      // LDS carve: weight vec16s of all phases, k-offset ints of all phases
   int x_planar, x_planes, y_planes;
   int npt, wq_shift;           // 16-pixel column tiles per wave (2, 4, 8); log2(Wq) when npt > 2
-  int xcd_walk;                // XCD-aware tile order (tile_common.hpp)
   int uni, out_wave_bytes;     // uniform geometry: LDS-staged epilogue, bytes of one wave's staging buffer
   int phase_of[4];             // uni: phase index of output sub-position (ph, pw) = [ph*SO + pw]
-  int dbg;                     // developer switches (MMVAE_DBG): 1 skip loads, 2 skip LDS commit, 4 skip MFMA+epilogue, 8 skip stores
   unsigned x_bytes;            // size of x in bytes (< 2^31): buffer-load range for the NHWC staging
   // second source (see GatherArgs): [N][Hq][Wq][Cin2] on the q grid, weights [Cout][Cin2], added into phase x2_phase
   const void* x2; const void* w2; int Cin2, x2_phase, kvp2, w2_vec0, x2_vec0, x2_slots; unsigned x2_bytes;
@@ -179,7 +174,6 @@ struct DeepArgs {
   int ct16, npt;               // cout tile / 16 (4 or 8), 16-pixel column tiles per wave
   int fp8;                     // w is e4m3 bytes, activations are quantised in LDS: v_mfma_f32_16x16x32_fp8_fp8 (forward convs, bf16 storage)
   int nw, cpt_log2;            // deep2_conv_kernel: waves per block (32 couts each), log2(64-byte chunks per tap of a weight row)
-  long long* ts;               // developer builds only (MMVAE_DEEP2_TS): per-block cycle stamps
   int wfrag;                   // weights are fragment-major (PackArgs::frag)
 };
 size_t deep2_conv_lds_bytes(const DeepArgs& a, int dt);
@@ -198,8 +192,6 @@ struct PosArgs {
 // 0 when no instantiation takes the geometry, < 0 on error.
 int launch_pos_conv(int K, int S, int P, int up, int HI, int HO, int CIN, const PosArgs& a, hipStream_t s);
 bool pos_conv_takes(int K, int S, int P, int up, int HI, int HO, int CIN);
-bool conv_force_v1();
-int conv_xcd_walk();      // MMVAE_XCD (default 1): XCD-aware tile order in the persistent patch-tile kernels   // MMVAE_CONV_V1=1 forces the generic v1 kernels (A/B and coverage)
 
 // ---------------------------------------------------------------- weight packing
 // dst[(col*ntaps + t)*K + k] = T(scale * src[col*s_col + k*s_k + tap_off[t]])

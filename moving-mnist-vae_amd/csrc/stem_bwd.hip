@@ -503,8 +503,7 @@ __global__ __launch_bounds__(256, 4) void stem_fwd_stream_kernel(StemFwdArgs a) 
 }
 
 bool stem_fwd_stream_ok(int dt, int S) {
-  constexpr bool env = true;
-  return env && dt == DT_BF16 && stem_bwd_fusable(S);
+  return dt == DT_BF16 && stem_bwd_fusable(S);
 }
 // y [N][S/2][S/2][32] bf16 = conv1(x), stats (nullable): partial rows [rows][2][32]; returns rows (> 0) or an error
 int launch_stem_fwd_stream(int dt, const void* x, const float* w, void* y, float* stats, int N, int S, hipStream_t s) {

@@ -151,8 +151,7 @@ Net::Net(const NetCfg& c) : cfg(c) {
   // (the same mechanism as an fp8 layer's weight scale).
   if (cfg.fp8 && !dec.empty()) {
     Block& L = dec.back();
-    constexpr bool env = true;
-    if (env && !L.identity && L.C == 16 && L.Cin == 16 && L.Hin == 32 && Sd == 64 && c.out_ch == 1 && convT4_stream_ok(DT_BF16, 16, 16, 4, 2, 1, 32, 32) &&
+    if (!L.identity && L.C == 16 && L.Cin == 16 && L.Hin == 32 && Sd == 64 && c.out_ch == 1 && convT4_stream_ok(DT_BF16, 16, 16, 4, 2, 1, 32, 32) &&
         tail_fwd_stream_ok(DT_BF16, 1, 64, 64) && join_bwd_stream_ok(DT_BF16, 1, 16, 32, 64)) {
       store8 = true;
       L.c2.wscale = 16.f; L.cs.wscale = 16.f;
@@ -245,8 +244,8 @@ static inline ConvGeom geom(const ConvW& w) { return ConvGeom{w.D0, w.D1, w.k, w
 // The up form of a 1x1 stride-2 shortcut has stride phases without a tap: in this net it only ever accumulates into (or rides along
 // with) the main path's data gradient, so those phases are skipped.
 // (an fp8 layer's FORWARD pack is e4m3: fragment-major when the fp8 form of the kernel takes the shape)
-int Net::frag_down(const ConvW& w) const { return w.Hl > 0 ? op_frag_down(dt(), geom(w), w.Hl, w.Hl, (w.fp8 && !w.tr) ? 1 : 0) : 0; }
-int Net::frag_up(const ConvW& w) const { return w.Hl > 0 ? op_frag_up(dt(), geom(w), w.Hl, w.Hl, 1, (w.fp8 && w.tr) ? 1 : 0) : 0; }
+int Net::frag_down(const ConvW& w) const { return w.Hl > 0 ? op_deep2_down_ok(dt(), geom(w), w.Hl, w.Hl, (w.fp8 && !w.tr) ? 1 : 0) : 0; }
+int Net::frag_up(const ConvW& w) const { return w.Hl > 0 ? op_deep2_up_ok(dt(), geom(w), w.Hl, w.Hl, 1, (w.fp8 && w.tr) ? 1 : 0) : 0; }
 int Net::pack_down(const ConvW& w, const float* params, char* base, hipStream_t s) {
   return op_pack_down(dt(), geom(w), params + w.off, base + plan_.packed + w.packD * (long)esz(), s, w.wscale, (w.fp8 && !w.tr) ? 1 : 0,
                       frag_down(w));
@@ -278,13 +277,11 @@ int Net::run_up(const ConvW& w, char* base, int N, const void* S, int Hs, int Ws
 hipStream_t Net::wgrad_stream(hipStream_t s) {
   if (side_state_ == 0) {
     side_state_ = 1;
-    if (side_state_ == 1) {
-      bool ok = hipStreamCreateWithFlags(&side_, hipStreamNonBlocking) == hipSuccess;
-      for (int i = 0; i < kForkEvents && ok; ++i) ok = hipEventCreateWithFlags(&ev_[i], hipEventDisableTiming) == hipSuccess;
-      for (int i = 0; i < 16 && ok; ++i) ok = hipEventCreateWithFlags(&blk_ev_[i], hipEventDisableTiming) == hipSuccess;
-      if (ok) ok = hipEventCreateWithFlags(&gram_ev_, hipEventDisableTiming) == hipSuccess;
-      if (!ok) { (void)hipGetLastError(); side_state_ = -1; }
-    }
+    bool ok = hipStreamCreateWithFlags(&side_, hipStreamNonBlocking) == hipSuccess;
+    for (int i = 0; i < kForkEvents && ok; ++i) ok = hipEventCreateWithFlags(&ev_[i], hipEventDisableTiming) == hipSuccess;
+    for (int i = 0; i < 16 && ok; ++i) ok = hipEventCreateWithFlags(&blk_ev_[i], hipEventDisableTiming) == hipSuccess;
+    if (ok) ok = hipEventCreateWithFlags(&gram_ev_, hipEventDisableTiming) == hipSuccess;
+    if (!ok) { (void)hipGetLastError(); side_state_ = -1; }
   }
   return side_state_ == 1 ? side_ : s;
 }
@@ -304,16 +301,10 @@ int Net::side_join(hipStream_t s) {
   return MMVAE_OK;
 }
 
-// measured: im2col + 1x1 weight gradient 0.39 ms, planar-G patch-tile path 0.42 ms (MMVAE_STEM_PLANAR=1)
-// MMVAE_STEM_FUSED=0 restores reduce -> apply -> im2col -> wgrad
+// the stem's backward in one pass (stem_bwd.hip); where the shape does not fit: reduce -> apply -> im2col -> wgrad
+// (measured: im2col + 1x1 weight gradient 0.39 ms, a planar-G patch-tile path 0.42 ms)
 bool Net::stem_bwd_fused() const {
-  constexpr bool env = true;
-  return env && cfg.in_ch == 1 && stem_bwd_fusable(cfg.S);
-}
-
-static bool stem_im2col_path() {
-  constexpr bool v = true;
-  return v;
+  return cfg.in_ch == 1 && stem_bwd_fusable(cfg.S);
 }
 
 int Net::side_mark(int slot) {
@@ -338,15 +329,13 @@ int Net::run_wgrad(const ConvW& w, int N, const void* P, int Hs, int Ws, const f
 
 // conv1 (3x3 s2) + 1x1 s2 shortcut weight gradients in one stream pass: encoder.layer1's shape (bf16, 32 -> 32 channels, 32x32 -> 16x16)
 static bool wgrad_pair_ok(int dt, const ConvGeom& g, const ConvGeom& gs, int Hout, int Hin) {
-  constexpr bool env = true;
-  return env && dt == DT_BF16 && g.k == 3 && g.s == 2 && g.p == 1 && gs.k == 1 && gs.s == 2 && gs.p == 0 && g.D0 == 32 && g.D1 == 32 && gs.D0 == 32 &&
+  return dt == DT_BF16 && g.k == 3 && g.s == 2 && g.p == 1 && gs.k == 1 && gs.s == 2 && gs.p == 0 && g.D0 == 32 && g.D1 == 32 && gs.D0 == 32 &&
          gs.D1 == 32 && Hout == 16 && Hin == 32;
 }
 
 // encoder.layer1.conv2's data gradient + bn1's backward sums in one stream pass (bf16, 32 -> 32 channels, 16x16 maps, one block per stage)
 bool Net::l1_dgrad_stream() const {
-  constexpr bool env = true;
-  if (!env || enc.empty()) return false;
+  if (enc.empty()) return false;
   const Block& B = enc[0];
   return !B.identity && !B.c2.fp8 && conv3_stream_ok(dt(), B.C, B.C, B.c2.k, B.c2.s, B.c2.p, B.Hout, B.Wout);
 }
@@ -361,10 +350,8 @@ bool Net::stem_dg_fused() const {
 }
 
 bool Net::tail_fwd_fused() const {
-  constexpr bool env = true;
-  constexpr bool bwd_env = true;
   // N does not enter the geometry checks beyond the tile count limit, which the plan's maximum batch already satisfies
-  return env && bwd_env && !dec.empty() && dec.back().C == 16 && tail_fwd_fusable(dt(), cfg.out_ch, 1, Sd, Sd) &&
+  return !dec.empty() && dec.back().C == 16 && tail_fwd_fusable(dt(), cfg.out_ch, 1, Sd, Sd) &&
          tail_join_fusable(dt(), cfg.out_ch, 1, Sd, Sd);
 }
 
@@ -604,13 +591,12 @@ int Net::encoder_fwd(int N, const float* x, const float* params, float* bnbuf, l
     Block& B = enc[i];
     const double cnt = (double)N * B.Hout * B.Wout;
     // shortcut branch (conv + its BatchNorm) on the side stream, concurrently with conv1 -> bn1 -> conv2 -> bn2
-    constexpr bool side_fwd = true;
     // encoder.layer1 (32 -> 32 channels, bf16): conv1 AND the 1x1 shortcut from ONE read of the block input, conv2 likewise a per-wave
     // stream (conv_fstream.hip); both BatchNorms finalise on the caller's stream
     const bool stream1 = !B.identity && !B.c1.fp8 && !B.cs.fp8 && B.cs.k == 1 && B.cs.s == 2 &&
                          conv3_stream_ok(dt(), B.Cin, B.C, B.c1.k, B.c1.s, B.c1.p, B.Hin, B.Win);
     const bool stream2 = !B.c2.fp8 && conv3_stream_ok(dt(), B.C, B.C, B.c2.k, B.c2.s, B.c2.p, B.Hout, B.Wout);
-    const bool fork = side_fwd && !B.identity && !stream1;
+    const bool fork = !B.identity && !stream1;
     int np;
     if (stream1) {
       np = launch_conv3_stream(dt(), 2, xin, base + plan_.packed + B.c1.packD * (long)esz(), base + plan_.packed + B.cs.packD * (long)esz(), base + B.y1,
@@ -694,7 +680,7 @@ int Net::encoder_bwd(int N, const float* d_mu, const float* d_logvar, const floa
       if (side_state_ == 1 && hipEventRecord(gram_ev_, side_) != hipSuccess) { set_error("side stream mark failed"); return MMVAE_ERR_HIP; }
     }
     gram_ready_ = false;            // (consumed: the next backward pass belongs to another forward pass)
-    if (!stem_bwd_fused() && cfg.in_ch == 1 && stem_im2col_path() && wgrad_stream(s) != s) MM_TRY(launch_stem_im2col(dt(), base + P.x_t, base + P.col, N, cfg.S, cfg.S, H1, W1, wgrad_stream(s)));
+    if (!stem_bwd_fused() && cfg.in_ch == 1 && wgrad_stream(s) != s) MM_TRY(launch_stem_im2col(dt(), base + P.x_t, base + P.col, N, cfg.S, cfg.S, H1, W1, wgrad_stream(s)));
     PackArgs pa; std::memset(&pa, 0, sizeof(pa));
     pa.src = params + head_mu.off; pa.dst = base + P.packed + head_pack_dg * (long)esz();
     pa.cols = 256; pa.K = Ch; pa.ntaps = 1; pa.s_col = 1; pa.s_k = 256; pa.scale = 1.0f / nt;
@@ -825,7 +811,6 @@ int Net::encoder_bwd(int N, const float* d_mu, const float* d_logvar, const floa
     MM_TRY(bn_backward_coefs(bn0, params, grads, base, np, 1, 0, (double)npix, s));
     MM_TRY(launch_bn_bwd_apply(dt(), base + P.g[cur], nullptr, bnf(bn0, base, 2), bnf(bn0, base, 3), base + P.y0, bnf(bn0, base, 4),
                                bnf(bn0, base, 5), bnf(bn0, base, 6), base + P.dy1[ds], nullptr, nullptr, nullptr, nullptr, nullptr, npix, 32, s));
-    const bool stem_im2col = stem_im2col_path();
     MM_TRY(side_fork(s));
     hipStream_t wsm = wgrad_stream(s);
     WgradArgs a; std::memset(&a, 0, sizeof(a));
@@ -837,16 +822,11 @@ int Net::encoder_bwd(int N, const float* d_mu, const float* d_logvar, const floa
       a.G = base + P.col; a.Hg = cfg.S; a.Wg = cfg.S; a.Cb = 16; a.Cb_valid = cfg.in_ch;
       a.stride = 2; a.pad = 2; a.ksz = 5; a.sA = 25 * cfg.in_ch; a.sB = 25; a.ntaps = 25;
       for (int t = 0; t < 25; ++t) a.tap_off[t] = t;
-    } else if (stem_im2col) {
+    } else {
       // im2col of the 1-channel image (25 taps padded to 32 columns) + the MFMA weight-gradient kernel as a 1x1 conv
       if (wsm == s) MM_TRY(launch_stem_im2col(dt(), base + P.x_t, base + P.col, N, cfg.S, cfg.S, H1, W1, wsm));   // else: done early
       a.G = base + P.col; a.Hg = H1; a.Wg = W1; a.Cb = 32; a.Cb_valid = 25;
       a.stride = 1; a.pad = 0; a.ksz = 1; a.sA = 25; a.sB = 1; a.ntaps = 1;
-    } else {
-      // dW[co][0][kh][kw]: P = dy (32 channels), G = the planar 1-channel image staged as 16 zero-padded channels in LDS
-      a.G = base + P.x_t; a.G_planar = 1; a.Hg = cfg.S; a.Wg = cfg.S; a.Cb = 16; a.Cb_valid = 1;
-      a.stride = 2; a.pad = 2; a.ksz = 5; a.sA = 25; a.sB = 25; a.ntaps = 25;
-      for (int t = 0; t < 25; ++t) a.tap_off[t] = t;
     }
     MM_TRY(launch_wgrad(dt(), a, wsm));
     MM_TRY(side_join(s));
@@ -887,11 +867,9 @@ int Net::decoder_fwd(int N, const float* encv, const float* params, float* bnbuf
     Block& B = dec[i];
     const double cnt = (double)N * B.Hout * B.Wout;
     // upsample (shortcut) branch on the side stream, concurrently with conv1 -> bn1 -> conv2 -> bn2
-    constexpr bool side_fwd = true;
-    const bool fork = side_fwd && !B.identity;
     if (!B.identity) {
-      if (fork) MM_TRY(side_fork(s));
-      hipStream_t ss = fork ? wgrad_stream(s) : s;
+      MM_TRY(side_fork(s));
+      hipStream_t ss = wgrad_stream(s);
       if (!B.cs.fp8 && convT4_stream_ok(dt(), B.cs.D0, B.cs.D1, B.cs.k, B.cs.s, B.cs.p, B.Hin, B.Win))
         np = launch_convT4_stream(dt(), xin, base + plan_.packed + B.cs.packU * (long)esz(), base + B.ys, xs, xb, 1, stats ? stats + kPartialFloats : nullptr,
                                   N, B.Hin, ss, (store8 && i == nd - 1) ? 1 : 0);
@@ -915,9 +893,9 @@ int Net::decoder_fwd(int N, const float* encv, const float* params, float* bnbuf
         np = run_up(B.c2, base, N, base + B.y1, B.Hin, B.Win, base + B.y2, B.Hout, B.Wout, bnf(B.b1, base, 2), bnf(B.b1, base, 3), 1, stats, 0, s);
     MM_TRY(np);
     MM_TRY(training ? bn_train(B.b2, params, bnbuf, nbt, base, np, cnt, s, 0, B.c2.wscale) : bn_eval(B.b2, params, bnbuf, base, s, B.c2.wscale));
-    if (fork) MM_TRY(side_join(s));
+    if (!B.identity) MM_TRY(side_join(s));
     if (i == nd - 1 && tail_fwd_fused()) break;     // the join of the last block happens inside the tail conv kernel
-    if (i == nd - 1 && store8) { set_error("fp8 storage of the last up-block needs the fused tail kernels (MMVAE_TAIL_FWD_FUSED / MMVAE_TAIL_FUSED)"); return MMVAE_ERR_UNSUPPORTED; }
+    if (i == nd - 1 && store8) { set_error("fp8 storage of the last up-block needs the fused tail kernels"); return MMVAE_ERR_UNSUPPORTED; }
     // the join, fused with the next block's 1x1 conv1 and bn1's statistics where that block's conv1 is 16-wide (uplayer3 -> 4, uplayer4 -> 5):
     // the joined row is the conv's operand while it is in LDS -- one launch and one pass over `out` fewer than join -> conv
     const bool fuse_c1 = i + 1 < nd && !B.identity && !dec[i + 1].identity && !dec[i + 1].c1.fp8 && dec[i + 1].c1.k == 1 && dec[i + 1].c1.s == 1 &&
@@ -968,10 +946,7 @@ int Net::decoder_fwd(int N, const float* encv, const float* params, float* bnbuf
     MM_TRY(np);
     if (training) MM_TRY(bn_train(bn_out, params, bnbuf, nbt, base, np, (double)N * Sd * Sd, s));
   }
-  if (training) {
-  } else {
-    MM_TRY(bn_eval(bn_out, params, bnbuf, base, s));
-  }
+  if (!training) MM_TRY(bn_eval(bn_out, params, bnbuf, base, s));
   MM_TRY(launch_affine_nchw(r_raw, bnf(bn_out, base, 2), bnf(bn_out, base, 3), recon, N, cfg.out_ch, Sd * Sd, s));
   return MMVAE_OK;
 }
@@ -1012,15 +987,12 @@ int Net::decoder_bwd(int N, const float* d_recon, const float* params, float* gr
                                    bnf(bn_out, base, 4), bnf(bn_out, base, 5), bnf(bn_out, base, 6), d_raw, N, cfg.out_ch, HW, s));
   else
     MM_TRY(launch_bn_bwd_apply_nchw(d_recon, r_raw, bnf(bn_out, base, 4), bnf(bn_out, base, 5), bnf(bn_out, base, 6), d_raw, N, cfg.out_ch, HW, s));
-  constexpr bool tail_fused_env = true;
-  const bool tail_fused = tail_fused_env && !dec.empty() && dec.back().C == 16 && tail_join_fusable(dt(), cfg.out_ch, N, Sd, Sd);
+  const bool tail_fused = !dec.empty() && dec.back().C == 16 && tail_join_fusable(dt(), cfg.out_ch, N, Sd, Sd);
   // forward did not store the joined activation: the weight gradient recomputes it inside the join-backward reduce pass (below)
   const bool tail_wg_in_reduce = tail_fwd_fused() && tail_fused;
   if (store8 && !tail_wg_in_reduce) { set_error("fp8 storage of the last up-block needs the fused tail backward"); return MMVAE_ERR_UNSUPPORTED; }
-  if (tail_wg_in_reduce) {
-  } else if (tail_fwd_fused()) {
-    set_error("decoder_bwd: the fused tail forward (no stored join) needs the fused tail backward (MMVAE_TAIL_FUSED)"); return MMVAE_ERR_UNSUPPORTED;
-  } else {
+  if (!tail_wg_in_reduce) {
+    if (tail_fwd_fused()) { set_error("decoder_bwd: the fused tail forward (no stored join) needs the fused tail backward"); return MMVAE_ERR_UNSUPPORTED; }
     // dW[oc][ci][kh][kw]: P = d_raw (planar f32, out_ch planes staged as 16 zero-padded channels), G = the last up-block's output
     WgradArgs a; std::memset(&a, 0, sizeof(a));
     a.P = d_raw; a.P_planar = 1; a.P_planes = cfg.out_ch; a.G = base + dec.back().out; a.dW = grads + tail.off; a.scratch = wscratch_;
@@ -1031,10 +1003,9 @@ int Net::decoder_bwd(int N, const float* d_recon, const float* params, float* gr
     MM_TRY(launch_wgrad(dt(), a, wgrad_stream(s)));
   }
   int cur = 0;
-  // The tail conv's input gradient is not materialised: the last up-block's join backward recomputes it from d_raw
-  // (launch_tail_join_bwd_*; MMVAE_TAIL_FUSED=0 restores the separate dgrad kernel).
-  if (tail_fused) {
-  } else {
+  // The tail conv's input gradient is not materialised where the shape allows: the last up-block's join backward recomputes it from d_raw
+  // (launch_tail_join_bwd_*).  Otherwise the separate dgrad kernel:
+  if (!tail_fused) {
     // dx[n,h,w,ci] = sum dy[n,oc,h+1-kh,w+1-kw] * w[oc][ci][kh][kw]: planar f32 source padded to 8 channels in LDS
     PackArgs pa; std::memset(&pa, 0, sizeof(pa));
     pa.src = params + tail.off; pa.dst = base + P.packed + tail_pack_d * (long)esz();

@@ -103,9 +103,9 @@ class Net {
   Plan plan_;
   float* wscratch_ = nullptr;
   // weight gradients run on a side stream, concurrently with the dgrad / BatchNorm-backward chain of the same block
-  // (the deep-layer kernels are latency-bound and leave most CUs idle); MMVAE_SIDE_STREAM=0 disables it
+  // (the deep-layer kernels are latency-bound and leave most CUs idle)
   static constexpr int kForkEvents = 192;
-  hipStream_t side_ = nullptr; hipEvent_t ev_[kForkEvents] = {}; int evi_ = 0; int side_state_ = 0;   // 0 unknown, 1 on, -1 off
+  hipStream_t side_ = nullptr; hipEvent_t ev_[kForkEvents] = {}; int evi_ = 0; int side_state_ = 0;   // 0 not created yet, 1 on, -1 creation failed
   hipStream_t wgrad_stream(hipStream_t s);      // stream the weight gradients are enqueued on
   int side_fork(hipStream_t s);                 // side stream waits for everything enqueued on s so far
   int side_join(hipStream_t s);                 // s waits for everything enqueued on the side stream so far
@@ -142,7 +142,7 @@ class Net {
   int run_wgrad(const ConvW& w, int N, const void* P, int Hs, int Ws, const float* proP_s, const float* proP_b,
                 const void* G, int Hl, int Wl, const float* proG_s, const float* proG_b, float* grads, hipStream_t s);
   // Last up-block forward as one kernel (join + tail conv, the joined activation is never stored); the backward then needs the
-  // recomputing wgrad and the recomputing join backward.  MMVAE_TAIL_FWD_FUSED=0 restores join -> conv.
+  // recomputing wgrad and the recomputing join backward.  Shapes it does not take keep join -> conv.
   bool tail_fwd_fused() const;
   bool stem_bwd_fused() const;       // stem backward as one pass (stem_bwd.hip)
   bool stem_dg_fused() const;        // ... with encoder.layer1's data gradient recomputed inside it (no stored gradient of the stem's output)
