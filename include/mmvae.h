@@ -364,6 +364,21 @@ MMVAE_API int mmvae_pixelcnn_fwd(mmvae_pixelcnn* net, int N, int S, const float*
                        float* out, void* stream);
 MMVAE_API int mmvae_pixelcnn_bwd(mmvae_pixelcnn* net, int N, int S, const float* x, const float* d_out, const float* params, float* grads,
                        void* workspace, size_t workspace_bytes, float* d_x, void* stream);
+/* Autoregressive sampling (reference main.py:186-202): the whole S x S loop enqueued on `stream`, no host synchronisation.  The net's input is
+ * cond [N, cond_channels, S, S] f32 (the decoder image of a PixelVAE; NULL with 0 channels) followed by sample [N, sample_channels, S, S] f32;
+ * cond_channels + sample_channels must equal the net's in_channels.  For pixel p = i * S + j in row-major order: layers 0 .. layers - 2 run over
+ * the full map (their InstanceNorms see every pixel, so nothing is cached), the last layer is evaluated at pixel p only, and
+ *   label = #{k in [0, out_channels - 2] : cdf_k <= uniforms[n][p]},  cdf = cumulative sums of softmax(logits) in channel order (f32),
+ *   sample[n, c, i, j] = (label - sub_mean) / data_std for every sample channel c
+ * (the distribution of torch.multinomial(probs, 1), from the caller's uniforms in [0, 1)).  The reference's PixelCNN-only loop passes
+ * sub_mean = 0, its PixelVAE loop the data mean.  Optional outputs (NULL: not written): out_logits [N, out, S, S] = the full forward on the sample
+ * as it was before the last pixel was written (what the reference's loop returns), probs [N, S*S, out] f32 and labels [N, S*S] of each draw.
+ * Errors (nothing is enqueued): channel counts, data_std == 0, NULL uniforms / sample: MMVAE_ERR_ARG; workspace too small: MMVAE_ERR_WORKSPACE.
+ * The workspace may be the forward's; a sampling call overwrites what mmvae_pixelcnn_bwd needs. */
+MMVAE_API size_t mmvae_pixelcnn_sample_workspace_bytes(mmvae_pixelcnn* net, int N, int S);
+MMVAE_API int mmvae_pixelcnn_sample(mmvae_pixelcnn* net, int N, int S, const float* cond, int cond_channels, float* sample, int sample_channels,
+                          const float* uniforms, float sub_mean, float data_std, const float* params, void* workspace, size_t workspace_bytes,
+                          float* out_logits, float* probs, int64_t* labels, void* stream);
 
 /* f32 <-> dtype element conversion (n elements) */
 MMVAE_API int mmvae_convert(int dtype_in, int dtype_out, const void* in, void* out, int64_t n, void* stream);

@@ -9,7 +9,7 @@ from .main import (MovingMNISTClips, checkpoint_variant, clips_from_npz_array, g
 
 
 def __getattr__(name):
-    if name in ("VAE", "FusedAdam", "GradSync", "Communicator", "MmvaeError"):
+    if name in ("VAE", "FusedAdam", "GradSync", "Communicator", "MmvaeError", "draw_labels"):
         from . import model as _m
         return getattr(_m, name)
     raise AttributeError(name)

@@ -90,6 +90,8 @@ PROTOTYPES = {
     "mmvae_pixelcnn_workspace_bytes": (c_size_t, [P, c_int, c_int]),
     "mmvae_pixelcnn_fwd": (c_int, [P, c_int, c_int, P, P, P, c_size_t, P, P]),
     "mmvae_pixelcnn_bwd": (c_int, [P, c_int, c_int, P, P, P, P, P, c_size_t, P, P]),
+    "mmvae_pixelcnn_sample_workspace_bytes": (c_size_t, [P, c_int, c_int]),
+    "mmvae_pixelcnn_sample": (c_int, [P, c_int, c_int, P, c_int, P, c_int, P, c_float, c_float, P, P, c_size_t, P, P, P, P]),
     "mmvae_convert": (c_int, [c_int, c_int, P, P, c_int64, P]),
 }
 

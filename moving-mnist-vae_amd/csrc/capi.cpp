@@ -204,6 +204,14 @@ int mmvae_pixelcnn_bwd(mmvae_pixelcnn* h, int N, int S, const float* x, const fl
   if (!h || N <= 0 || S <= 0 || !x || !d_out || !params || !grads || !ws) { set_error("pixelcnn_bwd: bad argument"); return MMVAE_ERR_ARG; }
   return h->net->backward(N, S, x, d_out, params, grads, ws, wsb, d_x, S_(st));
 }
+size_t mmvae_pixelcnn_sample_workspace_bytes(mmvae_pixelcnn* h, int N, int S) { return mmvae_pixelcnn_workspace_bytes(h, N, S); }
+int mmvae_pixelcnn_sample(mmvae_pixelcnn* h, int N, int S, const float* cond, int cond_channels, float* sample, int sample_channels,
+                          const float* uniforms, float sub_mean, float data_std, const float* params, void* ws, size_t wsb, float* out_logits,
+                          float* probs, int64_t* labels, void* st) {
+  if (!h || N <= 0 || S <= 0 || !sample || !uniforms || !params || !ws) { set_error("pixelcnn_sample: bad argument"); return MMVAE_ERR_ARG; }
+  return h->net->sample(N, S, cond, cond_channels, sample, sample_channels, uniforms, sub_mean, data_std, params, ws, wsb, out_logits, probs,
+                        reinterpret_cast<long long*>(labels), S_(st));
+}
 
 // ---- latent / loss
 int mmvae_rsample_fwd(const float* mu, const float* lv, const float* eps, float* enc, int64_t n, void* st) {

@@ -324,12 +324,29 @@ int launch_gauss_tail_apply(const float* raw, const float* target, const float* 
 // InstanceNorm2d (affine = False, eps 1e-5, instance statistics always) forward / backward fused with the ReLU behind it, and the layout
 // changes between NCHW f32 and NHWC storage type with 16 zero-padded channels.  stats: [N][C][2] = (mean, istd).
 int launch_inorm_planar_fwd(int dt, const float* x, void* xn16, float* stats, int N, int C, int HW, hipStream_t s);
+// the same with the C = Ca + Cb channels taken from two tensors, xa [N][Ca][HW] then xb [N][Cb][HW] (either may be empty)
+int launch_inorm_planar2_fwd(int dt, const float* xa, int Ca, const float* xb, int Cb, void* xn16, float* stats, int N, int HW, hipStream_t s);
 int launch_inorm_planar_bwd(int dt, const void* g16, const float* x, const float* stats, float* dx, int N, int C, int HW, hipStream_t s);
 int launch_inorm_nhwc_fwd(int dt, const void* h, void* a, float* stats, int N, int C, int HW, int relu, hipStream_t s);
 int launch_inorm_nhwc_bwd(int dt, const void* g, const void* h, const float* stats, void* dh, int N, int C, int HW, int relu, hipStream_t s);
 int launch_nhwc16_to_planar(int dt, const void* o16, float* out, int N, int C, int HW, hipStream_t s);
 int launch_planar_to_nhwc16(int dt, const float* in, void* o16, int N, int C, int HW, hipStream_t s);
 int launch_planar_to_nhwc16(int dt, const void* in, int in_dt, void* o16, int N, int C, int HW, hipStream_t s);
+
+// One pixel of the autoregressive sampler (main.py:186-202): the last masked convolution at pixel `pix` = i * S + j only, softmax, the draw
+// label = #{k <= Q - 2 : cdf_k <= uniforms[n][pix]} and sample[n][c][pix] = (label - sub_mean) / data_std for every sample channel c.
+struct PixelHeadArgs {
+  const void* a;             // [N][S][S][C] of T: the last layer's input
+  const void* w;             // [>= Q][ntaps][C] of T: the last layer's weights as packed for the forward GEMM
+  const float* bias;         // [Q]
+  const float* uniforms;     // [N][S * S], in [0, 1)
+  float* sample;             // [N][Cs][S][S]
+  float* probs;              // [N][S * S][Q] or null
+  long long* labels;         // [N][S * S] or null
+  int S, C, Q, ntaps, Cs, pix;
+  float sub_mean, data_std;
+};
+int launch_pixel_head(int dt, const PixelHeadArgs& h, int N, hipStream_t s);
 
 // ---------------------------------------------------------------- latent / loss
 // enc = mu + exp(0.5*logvar)*eps (f32 and T copies); kl_partial: -0.5*sum(lv - exp(lv) - mu^2 + 1) (one float, atomically added)

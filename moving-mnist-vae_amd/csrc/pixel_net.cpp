@@ -66,7 +66,7 @@ static void fill_taps(GatherArgs& a, int ntaps, bool mirrored) {
   }
 }
 
-int PixelNet::pack(const float* params, char* base, hipStream_t s) {
+int PixelNet::pack(const float* params, char* base, bool data_grad, hipStream_t s) {
   const PixelPlan& P = plan_;
   const long e = (long)dtype_size(dtype);
   pack_batch_begin();
@@ -76,6 +76,7 @@ int PixelNet::pack(const float* params, char* base, hipStream_t s) {
     f.cols = L.cout_p; f.cols_valid = L.cout; f.K = L.cin_p; f.K_valid = L.cin; f.ntaps = L.ntaps; f.s_col = L.cin * 49; f.s_k = 49; f.scale = 1.f;
     for (int t = 0; t < L.ntaps; ++t) f.tap_off[t] = t;
     MM_TRY(launch_pack(dtype, f, s));
+    if (!data_grad) continue;
     PackArgs b; std::memset(&b, 0, sizeof(b));     // data gradient: [cin_p][tap][cout_p]
     b.src = params + L.w_off; b.dst = base + P.packed + L.packB * e;
     b.cols = L.cin_p; b.cols_valid = L.cin; b.K = L.cout_p; b.K_valid = L.cout; b.ntaps = L.ntaps; b.s_col = 49; b.s_k = L.cin * 49; b.scale = 1.f;
@@ -85,35 +86,85 @@ int PixelNet::pack(const float* params, char* base, hipStream_t s) {
   return pack_batch_flush(dtype, s);
 }
 
+// layer i over the full map: h[i] = conv(x) + bias (model.py:223)
+int PixelNet::conv(int i, int N, int S, const void* x, const float* params, char* base, hipStream_t s) {
+  const PixelPlan& P = plan_;
+  const Layer& L = lay[i];
+  const long e = (long)dtype_size(dtype);
+  float* bias = const_cast<float*>(params) + L.b_off;
+  if (L.cout_p != L.cout) {     // last layer: the bias vector padded with zeros to the GEMM's 16 rows
+    bias = reinterpret_cast<float*>(base + P.bias_pad);
+    MM_TRY(launch_fill_f32(bias, 0.f, 16, s));
+    if (hipMemcpyAsync(bias, params + L.b_off, (size_t)L.cout * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) { set_error("pixelcnn: bias copy failed"); return MMVAE_ERR_HIP; }
+  }
+  GatherArgs a; std::memset(&a, 0, sizeof(a));
+  a.x = x; a.w = base + P.packed + L.packF * e; a.y = base + P.h[i]; a.bias = bias;
+  a.N = N; a.Hi = S; a.Wi = S; a.Cin = L.cin_p; a.Ho = S; a.Wo = S; a.Cout = L.cout_p; a.SI = 1; a.SO = 1;
+  a.nphase = 1; a.phases[0] = Phase{0, 0, S, S, L.ntaps, 0, 0};
+  fill_taps(a, L.ntaps, false);
+  return launch_gather_gemm(dtype, dtype, a, s);
+}
+
+// layers 0 .. layers - 2 on the instance-normalised input in x0; returns the last layer's input
+int PixelNet::trunk(int N, int S, const float* params, char* base, const void** last_in, hipStream_t s) {
+  const PixelPlan& P = plan_;
+  const void* cur = base + P.x0;
+  for (int i = 0; i < layers - 1; ++i) {
+    MM_TRY(conv(i, N, S, cur, params, base, s));
+    MM_TRY(launch_inorm_nhwc_fwd(dtype, base + P.h[i], base + P.a[i], reinterpret_cast<float*>(base + P.st[i]), N, mid, S * S, 1, s));   // model.py:252-253
+    cur = base + P.a[i];
+  }
+  *last_in = cur;
+  return MMVAE_OK;
+}
+
 int PixelNet::forward(int N, int S, const float* x, const float* params, void* ws, size_t ws_bytes, float* out, hipStream_t s) {
   const PixelPlan& P = plan(N, S);
   if (ws_bytes < P.bytes) { set_error("pixelcnn: workspace too small: %zu < %zu", ws_bytes, P.bytes); return MMVAE_ERR_WORKSPACE; }
   char* base = static_cast<char*>(ws);
   const int HW = S * S;
-  const long e = (long)dtype_size(dtype);
-  MM_TRY(pack(params, base, s));
+  MM_TRY(pack(params, base, true, s));
   MM_TRY(launch_inorm_planar_fwd(dtype, x, base + P.x0, reinterpret_cast<float*>(base + P.st0), N, in_ch, HW, s));      // model.py:249
-  const void* cur = base + P.x0;
-  for (int i = 0; i < layers; ++i) {
-    const Layer& L = lay[i];
-    float* bias = const_cast<float*>(params) + L.b_off;
-    if (L.cout_p != L.cout) {     // last layer: the bias vector padded with zeros to the GEMM's 16 rows
-      bias = reinterpret_cast<float*>(base + P.bias_pad);
-      MM_TRY(launch_fill_f32(bias, 0.f, 16, s));
-      if (hipMemcpyAsync(bias, params + L.b_off, (size_t)L.cout * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) { set_error("pixelcnn: bias copy failed"); return MMVAE_ERR_HIP; }
-    }
-    GatherArgs a; std::memset(&a, 0, sizeof(a));
-    a.x = cur; a.w = base + P.packed + L.packF * e; a.y = base + P.h[i]; a.bias = bias;
-    a.N = N; a.Hi = S; a.Wi = S; a.Cin = L.cin_p; a.Ho = S; a.Wo = S; a.Cout = L.cout_p; a.SI = 1; a.SO = 1;
-    a.nphase = 1; a.phases[0] = Phase{0, 0, S, S, L.ntaps, 0, 0};
-    fill_taps(a, L.ntaps, false);
-    MM_TRY(launch_gather_gemm(dtype, dtype, a, s));                                                                       // model.py:223
-    if (i < layers - 1) {
-      MM_TRY(launch_inorm_nhwc_fwd(dtype, base + P.h[i], base + P.a[i], reinterpret_cast<float*>(base + P.st[i]), N, mid, HW, 1, s));   // :252-253
-      cur = base + P.a[i];
-    }
-  }
+  const void* cur = nullptr;
+  MM_TRY(trunk(N, S, params, base, &cur, s));
+  MM_TRY(conv(layers - 1, N, S, cur, params, base, s));
   return launch_nhwc16_to_planar(dtype, base + P.h[layers - 1], out, N, out_ch, HW, s);
+}
+
+// The autoregressive sampling loop of main.py:186-202, enqueued whole: per pixel, InstanceNorm of (cond, sample), layers 0 .. layers - 2
+// over the full map (their InstanceNorms see every pixel, so nothing of them can be cached) and the head kernel, which evaluates the
+// last layer at that pixel, draws and writes the sample in place: 2 (layers - 1) + 2 launches per pixel, no allocation, copy or host
+// read.  The weights are packed once.  out (nullable): the logits of the last full forward, i.e. on the sample as it was before the last
+// pixel was written (what the reference's loop returns).
+int PixelNet::sample(int N, int S, const float* cond, int cond_ch, float* smp, int smp_ch, const float* uniforms, float sub_mean, float data_std,
+                     const float* params, void* ws, size_t ws_bytes, float* out, float* probs, long long* labels, hipStream_t s) {
+  if (cond_ch < 0 || smp_ch < 1 || cond_ch + smp_ch != in_ch) {
+    set_error("pixelcnn_sample: %d conditioning + %d sample channels, the net takes %d", cond_ch, smp_ch, in_ch);
+    return MMVAE_ERR_ARG;
+  }
+  if (cond_ch > 0 && !cond) { set_error("pixelcnn_sample: %d conditioning channels but no conditioning image", cond_ch); return MMVAE_ERR_ARG; }
+  if (!(data_std != 0.f)) { set_error("pixelcnn_sample: data_std must not be zero"); return MMVAE_ERR_ARG; }
+  const PixelPlan& P = plan(N, S);
+  if (ws_bytes < P.bytes) { set_error("pixelcnn_sample: workspace too small: %zu < %zu", ws_bytes, P.bytes); return MMVAE_ERR_WORKSPACE; }
+  char* base = static_cast<char*>(ws);
+  const int HW = S * S;
+  const Layer& L = lay[layers - 1];
+  MM_TRY(pack(params, base, false, s));
+  PixelHeadArgs h; std::memset(&h, 0, sizeof(h));
+  h.w = base + P.packed + L.packF * (long)dtype_size(dtype); h.bias = params + L.b_off; h.uniforms = uniforms;
+  h.sample = smp; h.probs = probs; h.labels = labels;
+  h.S = S; h.C = L.cin_p; h.Q = L.cout; h.ntaps = L.ntaps; h.Cs = smp_ch; h.sub_mean = sub_mean; h.data_std = data_std;
+  for (int pix = 0; pix < HW; ++pix) {
+    MM_TRY(launch_inorm_planar2_fwd(dtype, cond, cond_ch, smp, smp_ch, base + P.x0, reinterpret_cast<float*>(base + P.st0), N, HW, s));
+    MM_TRY(trunk(N, S, params, base, &h.a, s));
+    if (pix == HW - 1 && out) {
+      MM_TRY(conv(layers - 1, N, S, h.a, params, base, s));
+      MM_TRY(launch_nhwc16_to_planar(dtype, base + P.h[layers - 1], out, N, out_ch, HW, s));
+    }
+    h.pix = pix;
+    MM_TRY(launch_pixel_head(dtype, h, N, s));
+  }
+  return MMVAE_OK;
 }
 
 int PixelNet::backward(int N, int S, const float* x, const float* d_out, const float* params, float* grads, void* ws, size_t ws_bytes, float* d_x,

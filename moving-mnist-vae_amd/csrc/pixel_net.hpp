@@ -28,11 +28,18 @@ class PixelNet {
   int forward(int N, int S, const float* x, const float* params, void* ws, size_t ws_bytes, float* out, hipStream_t s);
   // grads (same layout as params) +=; d_x (nullable) [N][in_ch][S][S] f32.  x: the forward's input (its statistics are in the workspace).
   int backward(int N, int S, const float* x, const float* d_out, const float* params, float* grads, void* ws, size_t ws_bytes, float* d_x, hipStream_t s);
+  // Autoregressive sampling (main.py:186-202), all S * S pixels enqueued on s: the net's input is cond [N][cond_ch][S][S] (null with 0 channels)
+  // followed by sample [N][sample_ch][S][S], which is updated in place pixel by pixel with (label - sub_mean) / data_std, label drawn by inverse
+  // CDF from uniforms [N][S*S].  out [N][out_ch][S][S] (logits of the last full forward), probs [N][S*S][out_ch], labels [N][S*S]: nullable.
+  int sample(int N, int S, const float* cond, int cond_ch, float* sample, int sample_ch, const float* uniforms, float sub_mean, float data_std,
+             const float* params, void* ws, size_t ws_bytes, float* out, float* probs, long long* labels, hipStream_t s);
 
  private:
   long n_packed = 0;
   PixelPlan plan_;
-  int pack(const float* params, char* base, hipStream_t s);
+  int pack(const float* params, char* base, bool data_grad, hipStream_t s);
+  int conv(int i, int N, int S, const void* x, const float* params, char* base, hipStream_t s);
+  int trunk(int N, int S, const float* params, char* base, const void** last_in, hipStream_t s);
 };
 
 }  // namespace mmvae

@@ -28,13 +28,19 @@ __device__ __forceinline__ void block_sum_d(double (&v)[NV], double* smem) {
 }
 
 // x [N][C][HW] f32  ->  xn [N][HW][16] of T = instance-normalised x in channels < C, zeros above; stats [N][C][2] = (mean, istd)
+// The C channels may come from two tensors (the sampler's input: conditioning image, then the sample): channels < Ca from xa [N][Ca][HW],
+// the others from xb [N][C - Ca][HW]; a single tensor is Ca = C.
+__device__ __forceinline__ const float* planar_chan(const float* xa, int Ca, const float* xb, int C, int n, int c, int HW) {
+  return c < Ca ? xa + ((long)n * Ca + c) * HW : xb + ((long)n * (C - Ca) + (c - Ca)) * HW;
+}
 template <typename T>
-__global__ __launch_bounds__(256) void inorm_planar_fwd_kernel(const float* __restrict__ x, T* __restrict__ xn, float* __restrict__ stats, int C, int HW) {
+__global__ __launch_bounds__(256) void inorm_planar_fwd_kernel(const float* __restrict__ xa, int Ca, const float* __restrict__ xb, T* __restrict__ xn,
+                                                                float* __restrict__ stats, int C, int HW) {
   __shared__ double sRed[8];
   __shared__ float sCoef[2 * 16];
   const int n = blockIdx.x;
   for (int c = 0; c < C; ++c) {
-    const float* p = x + ((long)n * C + c) * HW;
+    const float* p = planar_chan(xa, Ca, xb, C, n, c, HW);
     double v[2] = {0.0, 0.0};
     for (int i = threadIdx.x; i < HW; i += 256) { const double e = p[i]; v[0] += e; v[1] += e * e; }
     block_sum_d<2>(v, sRed);
@@ -51,7 +57,7 @@ __global__ __launch_bounds__(256) void inorm_planar_fwd_kernel(const float* __re
   for (int i = threadIdx.x; i < HW; i += 256) {
     float f[16];
 #pragma unroll
-    for (int c = 0; c < 16; ++c) f[c] = c < C ? (x[((long)n * C + c) * HW + i] - sCoef[2 * c]) * sCoef[2 * c + 1] : 0.f;
+    for (int c = 0; c < 16; ++c) f[c] = c < C ? (planar_chan(xa, Ca, xb, C, n, c, HW)[i] - sCoef[2 * c]) * sCoef[2 * c + 1] : 0.f;
     T* o = xn + ((long)n * HW + i) * 16;
     constexpr int VE = Elem<T>::kVec;
 #pragma unroll
@@ -218,13 +224,69 @@ __global__ void planar_to_nhwc16_kernel(const TI* __restrict__ in, T* __restrict
   }
 }
 
+// ---- autoregressive sampling head (reference main.py:186-202, one pixel of the loop) ------------------------------------------------
+// The last masked convolution evaluated at ONE pixel, softmax, inverse-CDF draw and the write of the drawn value into the sample: no
+// InstanceNorm follows the last layer, so the sampler needs its output at the pixel being drawn only.  One wave per image (25 * 256 * 16
+// MACs at most: no MFMA, no LDS).  With Qp = Q rounded up to a power of two, lane l owns logit q = l % Qp and slice l / Qp of the
+// ntaps * C / VE 16-byte vectors of the dot product, so a lane carries ONE accumulator; a butterfly over the lane offsets >= Qp sums the
+// slices (every lane then holds its logit), butterflies over the offsets < Qp give the softmax's maximum and sum, and the Q - 1 cdf values
+// are read with wave-uniform shuffles.
+template <typename T>
+__global__ __launch_bounds__(64) void pixel_head_kernel(PixelHeadArgs h) {
+  constexpr int VE = Elem<T>::kVec;
+  const int n = blockIdx.x, lane = threadIdx.x, S = h.S, C = h.C, HW = S * S;
+  const int i = h.pix / S, j = h.pix - i * S;
+  int Qp = 1;
+  while (Qp < h.Q) Qp <<= 1;
+  const int q = lane & (Qp - 1), slice = lane / Qp, nslice = 64 / Qp;
+  const int cvecs = C / VE, nvec = h.ntaps * cvecs;
+  const T* a = static_cast<const T*>(h.a) + (long)n * HW * C;
+  const T* w = static_cast<const T*>(h.w) + (long)q * h.ntaps * C;
+  float acc = 0.f;
+  if (q < h.Q)
+    for (int v = slice; v < nvec; v += nslice) {
+      const int t = v / cvecs, cv = v - t * cvecs;
+      const int y = i + t / 7 - 3, x = j + t % 7 - 3;                // tap t of the 7x7 kernel in row-major order, padding 3
+      if (y < 0 || y >= S || x < 0 || x >= S) continue;              // zero padding
+      float f[VE], g[VE];
+      Elem<T>::unpack(*reinterpret_cast<const Vec16*>(a + ((long)y * S + x) * C + cv * VE), f);
+      Elem<T>::unpack(*reinterpret_cast<const Vec16*>(w + (long)t * C + cv * VE), g);
+#pragma unroll
+      for (int e = 0; e < VE; ++e) acc = fmaf(f[e], g[e], acc);
+    }
+  for (int o = 32; o >= Qp; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  const float logit = q < h.Q ? acc + h.bias[q] : -INFINITY;
+  float mx = logit;
+  for (int o = Qp >> 1; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  const float ex = q < h.Q ? expf(logit - mx) : 0.f;
+  float sum = ex;
+  for (int o = Qp >> 1; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+  const float p = ex / sum;
+  const long np = (long)n * HW + h.pix;
+  const float u = h.uniforms[np];
+  float cdf = 0.f;
+  int label = 0;
+  for (int k = 0; k < h.Q - 1; ++k) {                                // inverse CDF: label = #{k <= Q - 2 : cdf_k <= u}
+    cdf += __shfl(p, k, 64);
+    label += cdf <= u;
+  }
+  const float value = ((float)label - h.sub_mean) / h.data_std;
+  for (int c = lane; c < h.Cs; c += 64) h.sample[((long)n * h.Cs + c) * HW + h.pix] = value;     // main.py:191,201: the (N, 1) draw broadcast over the channels
+  if (h.probs && lane < h.Q) h.probs[np * h.Q + lane] = p;
+  if (h.labels && lane == 0) h.labels[np] = label;
+}
+
 static int ew_blocks(long n) { long b = (n + 255) / 256; return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b)); }
 
-int launch_inorm_planar_fwd(int dt, const float* x, void* xn16, float* stats, int N, int C, int HW, hipStream_t s) {
-  if (C < 1 || C > 16) { set_error("inorm_planar: C=%d out of range (1..16)", C); return MMVAE_ERR_UNSUPPORTED; }
-  if (dt == DT_F32) hipLaunchKernelGGL((inorm_planar_fwd_kernel<float>), dim3(N), dim3(256), 0, s, x, (float*)xn16, stats, C, HW);
-  else hipLaunchKernelGGL((inorm_planar_fwd_kernel<bf16_t>), dim3(N), dim3(256), 0, s, x, (bf16_t*)xn16, stats, C, HW);
+int launch_inorm_planar2_fwd(int dt, const float* xa, int Ca, const float* xb, int Cb, void* xn16, float* stats, int N, int HW, hipStream_t s) {
+  const int C = Ca + Cb;
+  if (Ca < 0 || Cb < 0 || C < 1 || C > 16 || (Ca && !xa) || (Cb && !xb)) { set_error("inorm_planar: C=%d + %d out of range (1..16)", Ca, Cb); return MMVAE_ERR_UNSUPPORTED; }
+  if (dt == DT_F32) hipLaunchKernelGGL((inorm_planar_fwd_kernel<float>), dim3(N), dim3(256), 0, s, xa, Ca, xb, (float*)xn16, stats, C, HW);
+  else hipLaunchKernelGGL((inorm_planar_fwd_kernel<bf16_t>), dim3(N), dim3(256), 0, s, xa, Ca, xb, (bf16_t*)xn16, stats, C, HW);
   return check_launch("inorm_planar_fwd");
+}
+int launch_inorm_planar_fwd(int dt, const float* x, void* xn16, float* stats, int N, int C, int HW, hipStream_t s) {
+  return launch_inorm_planar2_fwd(dt, x, C, nullptr, 0, xn16, stats, N, HW, s);
 }
 int launch_inorm_planar_bwd(int dt, const void* g16, const float* x, const float* stats, float* dx, int N, int C, int HW, hipStream_t s) {
   if (C < 1 || C > 16) { set_error("inorm_planar: C=%d out of range (1..16)", C); return MMVAE_ERR_UNSUPPORTED; }
@@ -267,6 +329,17 @@ int launch_planar_to_nhwc16(int dt, const void* in, int in_dt, void* o16, int N,
   const long npix = (long)N * HW;
   hipLaunchKernelGGL((planar_to_nhwc16_kernel<bf16_t, bf16_t>), dim3(ew_blocks(npix)), dim3(256), 0, s, (const bf16_t*)in, (bf16_t*)o16, npix, C, HW);
   return check_launch("planar_to_nhwc16");
+}
+
+int launch_pixel_head(int dt, const PixelHeadArgs& h, int N, hipStream_t s) {
+  const int VE = dt == DT_F32 ? 4 : 8;
+  if (h.C < VE || h.C % VE || h.Q < 1 || h.Q > 16 || h.ntaps < 1 || h.ntaps > 49 || h.Cs < 1 || h.S < 1 || h.pix < 0 || h.pix >= h.S * h.S) {
+    set_error("pixel_head: unsupported shape (C %d, Q %d, taps %d, sample channels %d, S %d, pixel %d)", h.C, h.Q, h.ntaps, h.Cs, h.S, h.pix);
+    return MMVAE_ERR_UNSUPPORTED;
+  }
+  if (dt == DT_F32) hipLaunchKernelGGL((pixel_head_kernel<float>), dim3(N), dim3(64), 0, s, h);
+  else hipLaunchKernelGGL((pixel_head_kernel<bf16_t>), dim3(N), dim3(64), 0, s, h);
+  return check_launch("pixel_head");
 }
 
 }  // namespace mmvae

@@ -178,8 +178,13 @@ def select_model(args):
 
 
 @torch.no_grad()
-def generate_only_pixelcnn(sample, model, data_mean, data_std):
-    """main.py:186-192: autoregressive sampling of a PixelCNN-only model, pixel by pixel (S * S forward passes; `sample` is updated in place)."""
+def generate_only_pixelcnn(sample, model, data_mean, data_std, uniforms=None):
+    """main.py:186-192: autoregressive sampling of a PixelCNN-only model, pixel by pixel (S * S forward passes; `sample` is updated in place).
+    Default: the reference's loop, drawing with torch.multinomial from the global RNG.  uniforms: an (N, S*S) tensor of uniforms in [0, 1), or
+    True to draw them with torch.rand -- the whole loop then runs on the device in one call, model.sample_pixels (same distribution, another
+    random stream)."""
+    if uniforms is not None:
+        return model.sample_pixels(sample, None, data_mean=data_mean, data_std=data_std, uniforms=None if uniforms is True else uniforms)
     import torch.nn.functional as F
     out = None
     for i in range(model.input_image_size):
@@ -191,8 +196,11 @@ def generate_only_pixelcnn(sample, model, data_mean, data_std):
 
 
 @torch.no_grad()
-def generate(z_image, sample, model, data_mean, data_std):
-    """main.py:195-202: autoregressive sampling of a PixelVAE's PixelCNN conditioned on the decoder image."""
+def generate(z_image, sample, model, data_mean, data_std, uniforms=None):
+    """main.py:195-202: autoregressive sampling of a PixelVAE's PixelCNN conditioned on the decoder image.  uniforms: as in
+    generate_only_pixelcnn (None: the reference's loop; a tensor or True: model.sample_pixels on the device)."""
+    if uniforms is not None:
+        return model.sample_pixels(sample, z_image, data_mean=data_mean, data_std=data_std, uniforms=None if uniforms is True else uniforms)
     import torch.nn.functional as F
     output_ = None
     for i in range(model.input_image_size):

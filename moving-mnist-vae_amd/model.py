@@ -160,6 +160,14 @@ class _DecoderFn(torch.autograd.Function):
         return (None, d_enc) + model._grad_views(G, 1)
 
 
+def draw_labels(probs, u):
+    """The sampler's draw rule, the one definition of it: ``label = #{k in [0, Q-2] : cdf_k <= u}`` with ``cdf`` the cumulative sums of
+    ``probs`` (..., Q) along the last axis in channel order and ``u`` (...) uniform in [0, 1) -- inverse-CDF sampling of the categorical
+    distribution ``probs``.  Pure torch, any device; returns int64 labels of ``u``'s shape."""
+    cdf = torch.cumsum(probs, dim=-1)[..., :-1]
+    return (cdf <= u.unsqueeze(-1)).sum(dim=-1)
+
+
 class _PixelFn(torch.autograd.Function):
     """PixelCNN.forward (model.py:248-255) through mmvae_pixelcnn_fwd / _bwd."""
 
@@ -636,7 +644,9 @@ class VAE(nn.Module):
         return flat_like.data_ptr() + 4 * self._poff
 
     def _pixel_workspace(self, N, S):
-        need = lib().mmvae_pixelcnn_workspace_bytes(self._hp, int(N), int(S))
+        """The PixelCNN's one workspace, shared by forward / backward and the sampler (sized for whichever asks for more)."""
+        need = max(lib().mmvae_pixelcnn_workspace_bytes(self._hp, int(N), int(S)),
+                   lib().mmvae_pixelcnn_sample_workspace_bytes(self._hp, int(N), int(S)))
         ws = self._pix_ws
         if ws is None or ws.numel() < need or ws.device != self._flat.device:
             ws = torch.empty(need, dtype=torch.uint8, device=self._flat.device)
@@ -740,6 +750,64 @@ class VAE(nn.Module):
         if x.dim() != 4 or x.shape[2] != x.shape[3]:
             raise ValueError(f"expected a square (N, C, S, S) input, got {tuple(x.shape)}")
         return _PixelFn.apply(self, x, *self._pix_params_live())
+
+    @torch.no_grad()
+    def sample_pixels(self, sample, z_image=None, *, data_mean, data_std, uniforms=None, generator=None, return_probs=False):
+        """The autoregressive sampler of main.py:186-202 as ONE call (mmvae_pixelcnn_sample): all S x S pixels are enqueued on the current
+        stream, no host work per pixel.  ``sample`` (N, C, S, S) is updated in place, pixel by pixel in row-major order, with
+        ``(label - sub_mean) / data_std`` in every channel, the label drawn from the softmax of the PixelCNN's logits at that pixel.
+        A PixelCNN-only model takes ``z_image=None`` and uses ``sub_mean = 0`` (the reference's ``generate_only_pixelcnn`` does not subtract
+        the mean); a PixelVAE needs ``z_image`` (what ``get_z_image`` returns) and uses ``sub_mean = data_mean`` (``generate``).
+
+        The written value is the correctly rounded f32 quotient, as in ``prepare_batch``'s images (torch on the GPU multiplies by the
+        reciprocal of the scalar instead: the reference loop's values can differ from these in the last bit).
+
+        Randomness: ``label = draw_labels(probs, u)`` with ``u = uniforms[n, i * S + j]``; ``uniforms=None`` draws them with
+        ``torch.rand((N, S * S), generator=generator)``.  That is the distribution of ``torch.multinomial(probs, 1)`` but another random
+        stream: the same seed gives other images than the reference's loop.
+
+        Returns ``(out_logits, sample)`` like the reference's functions -- the logits are those of the last full forward, i.e. on the
+        sample as it was before the last pixel was written -- plus ``(probs (N, S*S, Q) f32, labels (N, S*S) int64)`` of every draw with
+        ``return_probs=True``.  Works in train and eval mode (InstanceNorm has no running statistics).  Like a forward it masks the stored
+        weights, and it reuses the PixelCNN's workspace: a backward through an earlier forward raises afterwards."""
+        if self._hp is None:
+            raise MmvaeError("this model has no PixelCNN")
+        self._ensure_flat()
+        if sample.dim() != 4 or sample.shape[2] != sample.shape[3]:
+            raise ValueError(f"expected a square (N, C, S, S) sample, got {tuple(sample.shape)}")
+        N, Cs, S = sample.shape[0], sample.shape[1], sample.shape[2]
+        dev = self._flat.device
+        if sample.device != dev:
+            raise ValueError(f"sample is on {sample.device}, the model on {dev}")
+        if self.only_pixelcnn:
+            if z_image is not None:
+                raise ValueError("a PixelCNN-only model takes no z_image")
+            cond, Cc, sub_mean = None, 0, 0.0                                  # main.py:191 (sic)
+        else:
+            if z_image is None:
+                raise ValueError("a PixelVAE samples conditioned on z_image (model.get_z_image(encoding))")
+            cond = z_image.to(dev).contiguous().float()
+            if cond.dim() != 4 or cond.shape[0] != N or tuple(cond.shape[2:]) != (S, S):
+                raise ValueError(f"z_image {tuple(z_image.shape)} does not match sample {tuple(sample.shape)}")
+            Cc, sub_mean = cond.shape[1], float(data_mean)                     # main.py:201
+        work = sample if (sample.dtype == torch.float32 and sample.is_contiguous()) else sample.contiguous().float()
+        if uniforms is None:
+            uniforms = torch.rand((N, S * S), device=dev, generator=generator)
+        u = uniforms.to(dev).contiguous().float()
+        if u.numel() != N * S * S:
+            raise ValueError(f"uniforms must hold N * S * S = {N * S * S} values, got {tuple(uniforms.shape)}")
+        Q = self.pixelcnn_out_channels
+        out = torch.empty((N, Q, S, S), device=dev, dtype=torch.float32)
+        probs = torch.empty((N, S * S, Q), device=dev, dtype=torch.float32) if return_probs else None
+        labels = torch.empty((N, S * S), device=dev, dtype=torch.int64) if return_probs else None
+        self._flat[:self._poff].mul_(self._pix_mask)                           # model.py:222: weight.data *= mask in every forward
+        ws = self._pixel_workspace(N, S)
+        self._stamp("pix", True)                                               # the workspace of an earlier forward is gone
+        check(lib().mmvae_pixelcnn_sample(self._hp, N, S, ptr(cond), Cc, ptr(work), Cs, ptr(u), sub_mean, float(data_std), ptr(self._flat),
+                                          ptr(ws), ws.numel(), ptr(out), ptr(probs), ptr(labels), _stream()), "mmvae_pixelcnn_sample")
+        if work is not sample:
+            sample.copy_(work)
+        return (out, sample, probs, labels) if return_probs else (out, sample)
 
     def _pix_params_live(self):
         return [e[1] for e in self._ptable if e[2] < self._poff]
