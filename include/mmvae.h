@@ -226,6 +226,23 @@ MMVAE_API int mmvae_adam_step(float* params, const float* grads, float* exp_avg,
 MMVAE_API int mmvae_adam_step_dev(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
                         float beta2, float eps, float weight_decay, double* step_dev, float grad_scale, void* stream);
 
+/* acc[0] += sum_i (grads[i] * grad_scale)^2, every term formed in f64 (the product of two f32 is exact there) and summed like the loss
+ * sums above: `partials` is MMVAE_SUM_PARTIALS doubles of scratch (first word zero between calls), NULL runs the sum in one block.
+ * `grads` needs no alignment beyond a float's.  The sum is finite exactly when every gradient is: +inf for an inf, NaN for a NaN. */
+MMVAE_API int mmvae_grad_norm_sq(const float* grads, int64_t n, float grad_scale, double* acc, double* partials, void* stream);
+
+/* mmvae_adam_step_dev behind two guards, all on the stream (no host read, `grads` is not rewritten; capturable in a HIP graph):
+ * the global norm  total = sqrt(mmvae_grad_norm_sq(grads, grad_scale))  is taken first; if it is not finite, params and both
+ * moments stay untouched and the step count does not advance; otherwise the gradient is scaled by
+ * clip = min(1, max_norm / (total + 1e-6))  (torch.nn.utils.clip_grad_norm_; max_norm <= 0: no clipping, clip = 1) folded with
+ * grad_scale into one f32 factor, so a call that does not clip yields the bits of mmvae_adam_step_dev.
+ * state (4 doubles, device): [0] step count, incremented by a taken step; [1] total norm of the last call (after grad_scale, before
+ * clipping; not finite after a skipped step); [2] number of skipped steps, incremented by a skipped one; [3] the norm^2 accumulator,
+ * zero on entry and left at zero.  partials: MMVAE_SUM_PARTIALS doubles as above.  NULL state or partials: MMVAE_ERR_ARG. */
+MMVAE_API int mmvae_adam_step_guarded(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
+                            float beta2, float eps, float weight_decay, double* state, double* partials, float grad_scale,
+                            float max_norm, void* stream);
+
 /* ------------------------------------------------------------------ single ops (layer-level parity tests)
  * Conv2d / ConvTranspose2d with PyTorch weight layouts on NHWC activations of `dtype`:
  *   x [N,H,W,Cin], y [N,Ho,Wo,Cout];  weight f32 (Cout,Cin,k,k) for Conv2d, (Cin,Cout,k,k) for ConvTranspose2d.

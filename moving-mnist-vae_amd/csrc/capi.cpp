@@ -304,6 +304,19 @@ int mmvae_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n,
   return launch_adam_dev(a, step_dev, S(st));
 }
 
+int mmvae_grad_norm_sq(const float* g, int64_t n, float grad_scale, double* acc, double* partials, void* st) {
+  if (n > 0 && (!g || !acc)) { set_error("grad_norm_sq: bad argument"); return MMVAE_ERR_ARG; }
+  return launch_grad_norm_sq(g, (long)n, grad_scale, acc, partials, S(st));
+}
+
+int mmvae_adam_step_guarded(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd,
+                            double* state, double* partials, float grad_scale, float max_norm, void* st) {
+  if (n > 0 && (!p || !g || !m || !v)) { set_error("adam_step_guarded: bad argument"); return MMVAE_ERR_ARG; }
+  if (n > 0 && (!state || !partials)) { set_error("adam_step_guarded: state and partials required"); return MMVAE_ERR_ARG; }
+  AdamArgs a{p, g, m, v, (long)n, lr, b1, b2, eps, wd, 1.f, 1.f, grad_scale};
+  return launch_adam_guarded(a, state, partials, max_norm, S(st));
+}
+
 // ---- single ops
 static inline ConvGeom geom_for(int transposed, int Cin, int Cout, int k, int s, int p) {
   // Conv2d weight (Cout,Cin,k,k): D0=Cout (small side = y), D1=Cin.  ConvT weight (Cin,Cout,k,k): D0=Cin (small side = x), D1=Cout.

@@ -377,6 +377,11 @@ int launch_mmd_bwd(const float* x, const float* y, int n, int d, float coef, con
 struct AdamArgs { float* p; const float* g; float* m; float* v; long n; float lr, beta1, beta2, eps, weight_decay; float bc1, bc2; float grad_scale; };
 int launch_adam(const AdamArgs& a, hipStream_t s);
 int launch_adam_dev(const AdamArgs& a, double* state, hipStream_t s);   // step count on the device (graph capture): bc1 / bc2 ignored
+// acc[0] += sum (g[i] * grad_scale)^2 in f64 through `part` (as the loss sums above; nullptr: one block); any alignment of g
+int launch_grad_norm_sq(const float* g, long n, float grad_scale, double* acc, double* part, hipStream_t s);
+// launch_adam_dev behind a global-norm clip (max_norm > 0) and a skip of non-finite steps; state = {step count, total norm of the last
+// call, skipped steps, norm^2 accumulator (zero between calls)}
+int launch_adam_guarded(const AdamArgs& a, double* state, double* part, float max_norm, hipStream_t s);
 // labels (int64) -> image T [(l - mean)/std] (+ f32 copy for the Gaussian target)
 // labels: int64 (label_bytes = 8) or uint8 (1)
 int launch_normalise(int dt, const void* labels, int label_bytes, long n, float mean, float stdv, void* img_t, float* img_f32, hipStream_t s);
