@@ -208,6 +208,25 @@ MMVAE_API int mmvae_rbf_kernel(const float* x, const float* y, int n, int m, int
 /* acc = {px, kl, mmd} (f64) -> out[4] = {(nll*px + kl_coef*kl + mmd_coef*mmd)/n, nll*px/n, kl/n, mmd/n}  (model.py:405-406) */
 MMVAE_API int mmvae_loss_finish(const double* acc, float* out, float nll, float kl_coef, float mmd_coef, float n, void* stream);
 
+/* ------------------------------------------------------------------ held-out evaluation: per-image terms
+ * Every output is f64 [N], one value per image, WRITTEN (not accumulated) in a fixed order by one block per image: two calls on
+ * the same inputs return the same bits.  No alignment is required of any pointer beyond its element type's.  A NULL pointer
+ * (`weight` excepted), a non-positive N, per, Q, HW, d or K, or sigma <= 0 returns MMVAE_ERR_ARG with nothing enqueued.
+ * out[n] = -sum_{i < per} log N(target[n][i]; recon[n][i], sigma)   (the per-image share of mmvae_gauss_nll_fwd) */
+MMVAE_API int mmvae_gauss_nll_per_image(const float* recon, const float* target, int N, int64_t per, float sigma, double* out, void* stream);
+/* out[n] = sum_pix weight[t] * (logsumexp_q recon[n][:][pix] - recon[n][t][pix]), t = target[n][pix]; recon [N,Q,HW] f32, target [N,HW]
+ * int64 in [0, Q), weight [Q] f32 or NULL   (the per-image share of mmvae_ce_fwd) */
+MMVAE_API int mmvae_ce_per_image(const float* recon, const int64_t* target, const float* weight, int N, int Q, int HW, double* out, void* stream);
+/* out[n] = -0.5 * sum_{i < d} (logvar - exp(logvar) - mu^2 + 1); mu, logvar [N,d] f32 */
+MMVAE_API int mmvae_kl_per_image(const float* mu, const float* logvar, int N, int d, double* out, void* stream);
+/* out[n] = log p(z) - log q(z|x) = -0.5 * sum_{i < d} (z^2 - eps^2 - logvar), z = mu + exp(logvar/2) * eps: the f32 code
+ * mmvae_rsample_fwd produces from the same inputs, p the standard normal prior */
+MMVAE_API int mmvae_latent_logratio(const float* mu, const float* logvar, const float* eps, int N, int d, double* out, void* stream);
+/* Importance-weighted bound from K samples: nll, logratio f64 [K][N] (row k: the two calls above for sample k);
+ * out[n] = logsumexp_k(logratio[k][n] - nll[k][n]) - log K, the maximum subtracted before any exponential.  K = 1 returns
+ * logratio - nll to the last bit. */
+MMVAE_API int mmvae_iw_bound(const double* nll, const double* logratio, int K, int N, double* out, void* stream);
+
 /* ------------------------------------------------------------------ train-step plumbing
  * (label - mean)/std, main.py:383-387.  labels int64 [n]; image f32 [n]. */
 MMVAE_API int mmvae_normalise_labels(const int64_t* labels, int64_t n, float mean, float stdv, float* image, void* stream);

@@ -56,6 +56,11 @@ PROTOTYPES = {
     "mmvae_mmd_fwd_ex": (c_int, [P, P, c_int, c_int, P, P, P, P]),
     "mmvae_mmd_bwd": (c_int, [P, P, c_int, c_int, c_float, P, P, P]),
     "mmvae_loss_finish": (c_int, [P, P, c_float, c_float, c_float, c_float, P]),
+    "mmvae_gauss_nll_per_image": (c_int, [P, P, c_int, c_int64, c_float, P, P]),
+    "mmvae_ce_per_image": (c_int, [P, P, P, c_int, c_int, c_int, P, P]),
+    "mmvae_kl_per_image": (c_int, [P, P, c_int, c_int, P, P]),
+    "mmvae_latent_logratio": (c_int, [P, P, P, c_int, c_int, P, P]),
+    "mmvae_iw_bound": (c_int, [P, P, c_int, c_int, P, P]),
     "mmvae_normalise_labels": (c_int, [P, c_int64, c_float, c_float, P, P]),
     "mmvae_quantise_normalise": (c_int, [P, c_int64, P, c_int, c_float, c_float, P, P, P]),
     "mmvae_adam_step": (c_int, [P, P, P, P, c_int64, c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_float, P]),

@@ -283,6 +283,29 @@ int mmvae_loss_finish(const double* acc, float* out, float nll, float kl_coef, f
   return launch_loss_finish(acc, out, nll, kl_coef, mmd_coef, n, S(st));
 }
 
+// ---- held-out evaluation: per-image f64 terms (eval_loss.hip).  A bad argument returns before anything is enqueued.
+int mmvae_gauss_nll_per_image(const float* r, const float* t, int N, int64_t per, float sigma, double* out, void* st) {
+  if (!(sigma > 0.f)) { set_error("gauss_nll_per_image: sigma must be > 0"); return MMVAE_ERR_ARG; }
+  if (!r || !t || !out || N < 1 || per < 1) { set_error("gauss_nll_per_image: bad argument"); return MMVAE_ERR_ARG; }
+  return launch_gauss_nll_per_image(r, t, N, (long)per, sigma, out, S(st));
+}
+int mmvae_ce_per_image(const float* r, const int64_t* t, const float* w, int N, int Q, int HW, double* out, void* st) {
+  if (!r || !t || !out || N < 1 || Q < 1 || HW < 1) { set_error("ce_per_image: bad argument"); return MMVAE_ERR_ARG; }
+  return launch_ce_per_image(r, reinterpret_cast<const long long*>(t), w, N, Q, HW, out, S(st));
+}
+int mmvae_kl_per_image(const float* mu, const float* lv, int N, int d, double* out, void* st) {
+  if (!mu || !lv || !out || N < 1 || d < 1) { set_error("kl_per_image: bad argument"); return MMVAE_ERR_ARG; }
+  return launch_kl_per_image(mu, lv, N, d, out, S(st));
+}
+int mmvae_latent_logratio(const float* mu, const float* lv, const float* eps, int N, int d, double* out, void* st) {
+  if (!mu || !lv || !eps || !out || N < 1 || d < 1) { set_error("latent_logratio: bad argument"); return MMVAE_ERR_ARG; }
+  return launch_latent_logratio(mu, lv, eps, N, d, out, S(st));
+}
+int mmvae_iw_bound(const double* nll, const double* logratio, int K, int N, double* out, void* st) {
+  if (!nll || !logratio || !out || K < 1 || N < 1) { set_error("iw_bound: bad argument"); return MMVAE_ERR_ARG; }
+  return launch_iw_bound(nll, logratio, K, N, out, S(st));
+}
+
 // ---- plumbing
 int mmvae_normalise_labels(const int64_t* labels, int64_t n, float mean, float stdv, float* image, void* st) {
   return launch_normalise(DT_F32, labels, 8, (long)n, mean, stdv, nullptr, image, S(st));

@@ -373,6 +373,20 @@ int launch_rbf_matrix(const float* x, const float* y, int n, int m, int d, float
 // d_y[j] += coef * d(mmd)/d(y_j)
 int launch_mmd_bwd(const float* x, const float* y, int n, int d, float coef, const float* gscale, float* d_y, hipStream_t s);
 
+// ---------------------------------------------------------------- held-out evaluation (eval_loss.hip)
+// Per-image f64 terms, out[n] WRITTEN by one block per image in a fixed order (no atomics); no alignment demanded of the rows.
+// The callers (capi.cpp) have checked the arguments: N, per, Q, HW, d, K >= 1, no null pointer (weight excepted).
+// out[n] = -sum_{i < per} log N(t[n][i]; r[n][i], sigma)
+int launch_gauss_nll_per_image(const float* r, const float* t, int N, long per, float sigma, double* out, hipStream_t s);
+// out[n] = sum_pix w[t] * (logsumexp_q r[n][:][pix] - r[n][t][pix]); w may be null
+int launch_ce_per_image(const float* r, const long long* t, const float* w, int N, int Q, int HW, double* out, hipStream_t s);
+// out[n] = -0.5 * sum_d (lv - exp(lv) - mu^2 + 1)
+int launch_kl_per_image(const float* mu, const float* logvar, int N, int d, double* out, hipStream_t s);
+// out[n] = log p(z) - log q(z|x) = -0.5 * sum_d (z^2 - eps^2 - lv), z = mu + exp(lv/2) * eps as launch_rsample_fwd forms it
+int launch_latent_logratio(const float* mu, const float* logvar, const float* eps, int N, int d, double* out, hipStream_t s);
+// nll, logratio f64 [K][N]: out[n] = logsumexp_k(logratio[k][n] - nll[k][n]) - log K
+int launch_iw_bound(const double* nll, const double* logratio, int K, int N, double* out, hipStream_t s);
+
 // ---------------------------------------------------------------- optimiser / misc
 struct AdamArgs { float* p; const float* g; float* m; float* v; long n; float lr, beta1, beta2, eps, weight_decay; float bc1, bc2; float grad_scale; };
 int launch_adam(const AdamArgs& a, hipStream_t s);

@@ -100,6 +100,73 @@ def train(model, data_loader, optimizer, device, args, epoch=0, data_mean=0, dat
     return losses, nlls, kls, mmds
 
 
+def evaluate(model, data_loader, device, args, data_mean=0, data_std=1, iw_samples=0, weighted=False, generator=None,
+             return_per_image=False) -> dict:
+    """Held-out evaluation of the HIP model (the reference builds a test loader, main.py:497, and never reads it): one eval-mode pass
+    over ``data_loader`` under ``torch.no_grad()``; the model's train / eval mode is restored afterwards and no parameter or buffer
+    changes.  Batches are prepared as in ``train``.  Per-image terms come from ``model.per_image_terms`` (and ``model.iw_bound``
+    with ``iw_samples`` = K > 0), are summed on the device in f64 and read back once, at the end.
+
+    Returns means PER IMAGE in nats (a ragged last batch weighs what its images weigh): ``n_images``, ``nll`` (-log p(x|z), one
+    sample of q(z|x) per image; unweighted unless ``weighted`` passes ``args.data_ratio_of_labels``), ``kl`` (0 without a logvar),
+    ``elbo`` = -(nll + kl), ``iw_bound`` (None when ``iw_samples`` == 0) and ``bits_per_dim`` = nll / (C S S ln 2) for categorical
+    models (None for Gaussian ones: a density, not a code length).  A PixelCNN on its own has no latent: ``kl``, ``elbo`` and
+    ``iw_bound`` are None.  ``generator`` (a device generator) draws every noise tensor; None uses the global one.
+    ``return_per_image=True`` adds ``per_image``: {'nll', 'kl', 'iw_bound'} as concatenated f64 device tensors (or None)."""
+    if not hasattr(model, "per_image_terms"):
+        raise TypeError("evaluate() drives the HIP VAE of this package (it needs model.per_image_terms)")
+    latent = not model.only_pixelcnn
+    categorical = _is_categorical(model)
+    weight = getattr(args, "data_ratio_of_labels", None) if (weighted and categorical) else None
+    was_training = bool(model.training)
+    sums = None                                    # f64 device: nll, kl, iw
+    kept = {"nll": [], "kl": [], "iw_bound": []}
+    n_images = 0
+    model.eval()
+    try:
+        with torch.no_grad():
+            for batch in data_loader:
+                image, target = prepare_batch(model, batch, device, args, data_mean, data_std)
+                N = image.shape[0]
+                injected = False
+                if latent and model.require_rsample and model.injected_eps is None:
+                    # the draw VAE._rsample would make itself, through `generator`
+                    model.injected_eps = torch.randn((N, model.z_dimensions, 1, 1), device=image.device, dtype=torch.float32, generator=generator)
+                    injected = True
+                try:
+                    mu, logvar, _, reconstruction = model(image, sample=image)          # PixelVAE: teacher-forced on the image itself
+                finally:
+                    if injected:
+                        model.injected_eps = None
+                nll, kl = model.per_image_terms(target, mu, logvar, reconstruction, weight=weight)
+                iw = model.iw_bound(image, target, iw_samples, generator=generator, weight=weight) if iw_samples else None
+                if sums is None:
+                    sums = torch.zeros(3, dtype=torch.float64, device=nll.device)
+                sums[0] += nll.sum()
+                if kl is not None:
+                    sums[1] += kl.sum()
+                if iw is not None:
+                    sums[2] += iw.sum()
+                n_images += N
+                if return_per_image:
+                    kept["nll"].append(nll)
+                    if kl is not None:
+                        kept["kl"].append(kl)
+                    if iw is not None:
+                        kept["iw_bound"].append(iw)
+    finally:
+        model.train(was_training)
+    if n_images == 0:
+        raise ValueError("evaluate(): the data loader yielded no batch")
+    s_nll, s_kl, s_iw = (v / n_images for v in sums.tolist())                           # the one device -> host copy
+    dims = model.in_channels * model.input_image_size ** 2
+    out = {"n_images": n_images, "nll": s_nll, "kl": s_kl if latent else None, "elbo": -(s_nll + s_kl) if latent else None,
+           "iw_bound": s_iw if iw_samples else None, "bits_per_dim": s_nll / (dims * float(np.log(2.0))) if categorical else None}
+    if return_per_image:
+        out["per_image"] = {k: (torch.cat(v) if v else None) for k, v in kept.items()}
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # Drop-in contract around the loop: model-name grammar, checkpoint format, device-side input quantisation
 # ---------------------------------------------------------------------------------------------------------------------

@@ -905,6 +905,95 @@ class VAE(nn.Module):
             return loss_t, DeferredScalar(grp, 1), DeferredScalar(grp, 2), DeferredScalar(grp, 3)
         return loss_t, grp.get(1), grp.get(2), grp.get(3)
 
+    # ---- held-out evaluation: per-image terms (csrc/eval_loss.hip).  The reference has no counterpart: it builds a test loader (main.py:497)
+    # and never reads it.
+    def _nll_rows(self, target, reconstruction, weight, out):
+        """Raw per-image negative log-likelihood of `reconstruction` into `out` (f64, N contiguous values on the device): categorical under
+        the condition of `loss` (model.py:398), Gaussian with sigma_decoder otherwise; not scaled by self.nll."""
+        dev = self._flat.device
+        N = reconstruction.shape[0]
+        if reconstruction.device != dev or reconstruction.dim() != 4:
+            raise ValueError(f"expected an (N, C, H, W) reconstruction on {dev}, got {tuple(reconstruction.shape)} on {reconstruction.device}")
+        recon = reconstruction.detach().float().contiguous()          # (the crop of a 28 x 28 model is a strided view)
+        if self.pixelcnn is not None or self.decoder_out_channels > self.in_channels:
+            Q, HW = recon.shape[1], recon.shape[2] * recon.shape[3]
+            tgt = target.detach().to(dev)
+            if tgt.dtype != torch.int64:
+                tgt = tgt.long()
+            tgt = tgt.contiguous()
+            if tgt.numel() != N * HW:
+                raise ValueError(f"target {tuple(target.shape)} does not hold one label per pixel of {tuple(recon.shape)}")
+            w = None
+            if weight is not None:
+                w = weight.detach().to(dev).float().contiguous()
+                if w.numel() != Q:
+                    raise ValueError(f"weight must hold {Q} values, got {tuple(weight.shape)}")
+            check(lib().mmvae_ce_per_image(ptr(recon), ptr(tgt), ptr(w), N, Q, HW, ptr(out), _stream()), "mmvae_ce_per_image")
+        else:
+            tgt = target.detach().to(dev).float().contiguous()
+            if tgt.numel() != recon.numel():
+                raise ValueError(f"target {tuple(target.shape)} does not match the reconstruction {tuple(recon.shape)}")
+            check(lib().mmvae_gauss_nll_per_image(ptr(recon), ptr(tgt), N, recon.numel() // N, float(self.sigma_decoder), ptr(out), _stream()),
+                  "mmvae_gauss_nll_per_image")
+
+    def per_image_terms(self, target, encoding_mu, encoding_logvar, reconstruction, weight=None):
+        """The two terms of the ELBO per image, as f64 device tensors (no host read): ``(nll [N], kl [N] or None)``.  ``nll`` is the raw
+        negative log-likelihood -log p(x|z) of the reconstruction -- the summand of ``loss`` before the ``self.nll`` coefficient and the
+        division by N, cross-entropy or Gaussian under the same condition (``weight``: per-class weights of the cross-entropy; None, the
+        default, gives a true likelihood) -- and ``kl`` the analytic KL(q(z|x) || N(0, I)), None without a logvar."""
+        self._ensure_flat()
+        N = reconstruction.shape[0]
+        dev = self._flat.device
+        nll = torch.empty(N, dtype=torch.float64, device=dev)
+        self._nll_rows(target, reconstruction, weight, nll)
+        if encoding_logvar is None or encoding_mu is None:
+            return nll, None
+        mu, lv = encoding_mu.detach().float().contiguous(), encoding_logvar.detach().float().contiguous()
+        if mu.shape[0] != N or lv.shape != mu.shape or mu.device != dev:
+            raise ValueError(f"mu {tuple(mu.shape)} / logvar {tuple(lv.shape)} do not match {N} images on {dev}")
+        kl = torch.empty(N, dtype=torch.float64, device=dev)
+        check(lib().mmvae_kl_per_image(ptr(mu), ptr(lv), N, mu.numel() // N, ptr(kl), _stream()), "mmvae_kl_per_image")
+        return nll, kl
+
+    @torch.no_grad()
+    def iw_bound(self, x, target, K, eps=None, generator=None, weight=None):
+        """Importance-weighted bound (Burda et al. 2016) on log p(x) per image, f64 [N] on the device, from K samples of q(z|x):
+        ``log (1/K) sum_k p(x|z_k) p(z_k) / q(z_k|x)``.  K = 1 is a one-sample ELBO estimate; the bound tightens with K.
+
+        One encoder forward, then K passes of reparameterisation, decoder and (PixelVAE) the PixelCNN teacher-forced on ``x`` as in
+        ``forward(x, sample=x)``; each pass writes row k of two f64 [K, N] buffers (mmvae_gauss_nll_per_image / mmvae_ce_per_image,
+        mmvae_latent_logratio) and mmvae_iw_bound reduces them.  ``eps`` [K, N, z] is the noise; None draws it with
+        ``torch.randn(..., generator=generator)``.  Eval mode only: batch statistics would make the images of a batch interact."""
+        if self.only_pixelcnn:
+            raise ValueError("a PixelCNN on its own has no latent code: no importance-weighted bound")
+        if not self.require_rsample:
+            raise ValueError("iw_bound needs q(z|x): the model was built with require_rsample=False")
+        K = int(K)
+        if K < 1:
+            raise ValueError(f"K must be >= 1, got {K}")
+        if self.training:
+            raise MmvaeError("iw_bound runs in eval mode only (train-mode BatchNorm couples the images of a batch): call model.eval() first")
+        mu, logvar = self._encode(x)
+        N, z = mu.shape[0], self.z_dimensions
+        dev = mu.device
+        if eps is None:
+            eps = torch.randn((K, N, z), device=dev, dtype=torch.float32, generator=generator)
+        eps = eps.to(dev).float().contiguous()
+        if eps.numel() != K * N * z:
+            raise ValueError(f"eps must be (K, N, z) = ({K}, {N}, {z}), got {tuple(eps.shape)}")
+        eps = eps.view(K, N, z)
+        rows = torch.empty((2, K, N), dtype=torch.float64, device=dev)          # [0]: nll, [1]: log p(z) - log q(z|x)
+        for k in range(K):
+            encoding = _RsampleFn.apply(mu, logvar, eps[k].view(mu.shape))
+            recon = self._decode(encoding)
+            if self._hp is not None:
+                recon = self.run_pixelcnn(torch.cat([recon, x.to(recon.dtype)], dim=1))
+            self._nll_rows(target, recon, weight, rows[0, k])
+            check(lib().mmvae_latent_logratio(ptr(mu), ptr(logvar), ptr(eps[k]), N, z, ptr(rows[1, k]), _stream()), "mmvae_latent_logratio")
+        out = torch.empty(N, dtype=torch.float64, device=dev)
+        check(lib().mmvae_iw_bound(ptr(rows[0]), ptr(rows[1]), K, N, ptr(out), _stream()), "mmvae_iw_bound")
+        return out
+
     # ---- train-loop hook (main.py:374-388): labels -> normalised frames, one kernel
     def prepare_batch(self, batch, device, data_mean, data_std, categorical):
         S = self.input_image_size
