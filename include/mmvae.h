@@ -303,7 +303,10 @@ MMVAE_API int mmvae_batchnorm_fwd(int dtype, const void* y, int64_t npix, int C,
 MMVAE_API int mmvae_batchnorm_bwd(int dtype, const void* dout, const void* y, const void* out, int64_t npix, int C, const float* gamma,
                         const float* save_mean, const float* save_istd, void* dy, float* dgamma, float* dbeta, void* scratch, void* stream);
 /* encoder.conv1: Conv2d(1 -> 32, k5 s2 p2, no bias) on x [N,S,S] of `dtype` -> y [N,S/2,S/2,32]; stats as mmvae_conv2d_fwd.
- * scratch: >= 2 KB * sizeof(dtype) for the packed weights. */
+ * 9 <= S <= 64.  scratch: MMVAE_STEM_SCRATCH_BYTES for the packed weights -- 32 channels x 25 taps x one 16-byte vector of input channels
+ * (8 bf16 / 4 f32, the image in the first): 12 800 bytes in either dtype (bf16 at S = 64 / 32 / 16 builds its weights in registers and
+ * leaves the scratch alone). */
+#define MMVAE_STEM_SCRATCH_BYTES 12800u
 MMVAE_API int mmvae_stem_fwd(int dtype, const void* x, const float* weight, void* y, int N, int S, float* stats, void* scratch, void* stream);
 /* Backward of relu(bn(conv1(x))) w.r.t. the parameters in ONE pass over g and y0 (stem_bwd.hip): g = gradient at the block input
  * (post-ReLU activation), y0 = conv1 output, (bn_scale, bn_shift) = gamma*istd, beta - mean*gamma*istd.

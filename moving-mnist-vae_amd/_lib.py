@@ -14,6 +14,8 @@ LIB_PATH = os.environ.get("MMVAE_LIB_PATH") or os.path.join(_HERE, "libmmvae_hip
 _lib = None
 ABI_VERSION = 3            # MMVAE_ABI_VERSION of include/mmvae.h
 SUM_PARTIALS = 1025        # MMVAE_SUM_PARTIALS: f64 scratch of each loss sum (mmvae_kl_fwd_ex, ...)
+BN_SCRATCH_BYTES = 16 << 20     # MMVAE_BN_SCRATCH_BYTES: mmvae_batchnorm_fwd / _bwd, mmvae_stem_bwd
+STEM_SCRATCH_BYTES = 12800      # MMVAE_STEM_SCRATCH_BYTES: packed weights of mmvae_stem_fwd
 
 P = c_void_p
 

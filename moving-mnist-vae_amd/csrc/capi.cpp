@@ -465,6 +465,7 @@ int mmvae_batchnorm_bwd(int dt, const void* dout, const void* y, const void* out
   if (rc < 0) return rc;
   return launch_bn_bwd_apply(dt, dout, out, nullptr, nullptr, y, coef, coef + C, coef + 2 * C, dy, nullptr, nullptr, nullptr, nullptr, nullptr, npix, C, S(st));
 }
+static_assert(MMVAE_STEM_SCRATCH_BYTES >= 32 * 25 * 16, "stem scratch: 32 columns x 25 taps x one 16-byte vector of padded input channels");
 int mmvae_stem_fwd(int dt, const void* x, const float* w, void* y, int N, int Sz, float* stats, void* scratch, void* st) {
   if (!scratch || N < 1 || Sz < 9 || Sz > 64) { set_error("stem_fwd: bad arguments"); return MMVAE_ERR_ARG; }
   if (stem_fwd_stream_ok(dt, Sz)) return launch_stem_fwd_stream(dt, x, w, y, stats, N, Sz, S(st));

@@ -1,0 +1,516 @@
+"""Float64 per-channel parity of mmvae_batchnorm_fwd / mmvae_batchnorm_bwd (csrc/bn_elem.hip: chan_stats_nhwc, bn_finalize, affine_join,
+bn_bwd_reduce, bn_bwd_finalize, bn_bwd_apply) over every accepted channel-group count, the grid cap, a shifted regime, a constant channel,
+the += contract, determinism, the refusal paths and the documented buffer sizes.
+
+References, both float64 and both built from the exact tensors handed to the device (already rounded to the storage type):
+  R64  the mathematical operation: batch mean, biased variance, dy = gamma istd (gm - mean(gm) - yhat mean(gm yhat));
+  Rq   the same arithmetic following the kernels: save_mean / save_istd rounded to f32 before the backward pass uses them, the ReLU mask
+       taken from the sign of the stored `out`, out / dy rounded to bf16 where the kernel stores bf16.
+The device is gated against Rq; |Rq - R64| is the storage error no kernel can remove: it is printed in the failure messages and gates nothing.
+
+Every gate is per channel.  Bounds are in units of u = 2^-24 and follow the kernels' operation order:
+  * the reductions (sum y, sum y^2, sum gm, sum gm y) run in f32 inside a thread over its T grid-stride passes, then in f32 over the
+    K = threads / cvecs threads of a block that share a channel group (block_channel_reduce, sequential), and in double after that.  The test
+    rebuilds that order from the launch geometry (block_threads_for, elem_blocks, the 768-block cap) and bounds the error of every f32
+    addition by u times the float64 partial sum it produces (first addition into a zero accumulator exact), a product by u of its value;
+  * mean = S1 / n, var = S2 / n - mean^2 in double: d var <= dS2 / n + 2 |mean| dS1 / n, which is where the (1 + mean^2 / var) factor of the
+    E[y^2] - mean^2 algorithm comes from; istd is bounded by evaluating 1 / sqrt(var + eps) at both ends of that interval, plus u for the store;
+  * elementwise kernels: coefficients the entry point does not return are rebuilt in float64 from the device's own save_mean / save_istd
+    (2u of |scale|, 2u |mean scale| + u |shift| away from the device's f32 values), the two or three f32 operations add 2u |y scale| + u |shift|:
+    4u (|y scale| + |shift| + |mean scale|) in all; dy = A g + B y + C likewise 4u (|A g| + |B y| + |C|) plus what the sums' own error moves
+    B and C by, |A| (istd |y - mean| d(sum g yhat) + d(sum g)) / n.  The term magnitudes, not the result, keep a cancelling dy honest; they
+    are those of the device's coefficients, |B| + dB and |C| + dC with dB = |A| istd d(sum g yhat) / n, dC = |A| d(sum g) / n + dB |mean|:
+    dB y and dB mean cancel in the sum but are rounded apart, and at var ~ 0 (one pixel) istd^2 = 1 / eps makes them exceed B y itself;
+  * a bf16 store adds half a bf16 ulp: 2^-9 of the value's binade top (2^-9 |v| .. 2^-8 |v|; 2^-9 |v| alone is less than the format rounds by).
+The mask of the backward pass is the sign of the stored `out` the test hands over, so no backward element is ambiguous by itself; the forward
+elements whose float64 pre-activation is within 4u (|y scale| + |shift|) of zero are counted on the CPU and capped at 0.1 % of a case.
+
+Worst error / bound per output measured on the MI355X over all cases: see the RATIO lines each test prints (recorded in the commit message).
+`out` and `dy` reach 0.9999 only with bf16 storage (C = 72, npix = 3001 among others): a value that lands on a bf16 rounding tie uses the
+whole half ulp, which no bound can undercut.  With f32 storage the worst are 0.57 (`out`, C = 128, npix = 3001) and 0.72 (`dy`, C = 512, npix = 3001).
+"""
+import importlib
+import math
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+U = 2.0 ** -24
+SLOP = 1.01                          # second-order terms of the first-order bounds
+EPS = float(np.float32(1e-5))        # the f32 scalars the entry point receives
+MOM = float(np.float32(0.1))
+ELEM_MAX_BLOCKS = 768                # kElemMaxBlocks of csrc/bn_elem.hip
+GUARD = 1 << 16
+PATTERN = 0xA5
+gpu = pytest.mark.gpu
+TDT = {"f32": torch.float32, "bf16": torch.bfloat16}
+VE = {"f32": 4, "bf16": 8}
+DTI = {"f32": 0, "bf16": 1}
+
+
+def _L():
+    return importlib.import_module("moving-mnist-vae_amd._lib")
+
+
+def _header_macro(name):
+    """Value (bytes) of a `#define NAME (Nu << S)` / `#define NAME Nu` of include/mmvae.h."""
+    src = open(os.path.join(ROOT, "include", "mmvae.h")).read()
+    m = re.search(r"#define\s+" + name + r"\s+\(?\s*(\d+)u?\s*(?:<<\s*(\d+))?\s*\)?", src)
+    assert m, name
+    return int(m.group(1)) << int(m.group(2) or 0)
+
+
+# ================================================================ launch geometry (csrc/bn_elem.hip)
+def block_threads_for(cvecs):
+    b = 256 - (256 % cvecs)
+    return cvecs if b < cvecs else b
+
+
+def elem_blocks(nvec, threads):
+    return max(1, min(ELEM_MAX_BLOCKS, (nvec + threads * 4 - 1) // (threads * 4)))
+
+
+def geometry(npix, C, dt):
+    """(K threads of a block per channel group, blocks, T passes of the grid-stride loop) of the reduction kernels."""
+    cvecs = C // VE[dt]
+    threads = block_threads_for(cvecs)
+    blocks = min(1024, elem_blocks(npix * cvecs, threads))
+    K = threads // cvecs
+    T = -(-npix // (blocks * K))
+    return K, blocks, T
+
+
+def sum_err(terms, dt, products=False):
+    """Per-channel bound on the error of the kernels' sum of terms [npix, C] (float64): pixel p = (k blocks + b) K + j is added in pass k by
+    thread j of block b's channel group -- f32 over k inside the thread, f32 over j inside the block, double over b."""
+    npix, C = terms.shape
+    K, blocks, T = geometry(npix, C, dt)
+    pad = T * blocks * K - npix
+    t = torch.cat([terms, terms.new_zeros(pad, C)]) if pad else terms
+    t = t.view(T, blocks, K, C)
+    c1 = t.cumsum(0)
+    e = c1[1:].abs().sum((0, 1, 2))
+    c2 = c1[-1].cumsum(1)
+    e = e + c2[:, 1:].abs().sum((0, 1))
+    if products:
+        e = e + terms.abs().sum(0)
+    return SLOP * U * e
+
+
+def half_ulp_bf16(v):
+    """Half a bf16 ulp at |v| (float64): 2^-9 of the top of the value's binade."""
+    _, ex = torch.frexp(v.abs())
+    return torch.where(v == 0, torch.zeros_like(v), torch.ldexp(torch.ones_like(v), ex - 9))
+
+
+def rq_store(v, dt):
+    return v.float().to(torch.bfloat16).double() if dt == "bf16" else v
+
+
+# ================================================================ float64 references (pure CPU)
+def ref_stats(y, rm=None, rv=None):
+    """R64 statistics of y [npix, C] (float64)."""
+    n = y.shape[0]
+    mean = y.mean(0)
+    var = ((y - mean) ** 2).mean(0)
+    r = dict(mean=mean, var=var, istd=1.0 / torch.sqrt(var + EPS))
+    if rm is not None:
+        r["rm"] = (1.0 - MOM) * rm.double() + MOM * mean
+        r["rv"] = (1.0 - MOM) * rv.double() + MOM * (var * n / (n - 1) if n > 1 else var)
+    return r
+
+
+def ref_fwd(y, gamma, beta, mean, istd, relu):
+    """out (before the store) from given statistics, with the magnitudes the bound uses."""
+    scale = gamma.double() * istd
+    shift = beta.double() - mean * scale
+    pre = y * scale + shift
+    return dict(pre=pre, out=pre.clamp_min(0) if relu else pre, mag=(y * scale).abs() + shift.abs() + (mean * scale).abs(),
+                mag_mask=(y * scale).abs() + shift.abs())
+
+
+def ref_bwd(g, y, mask, gamma, mean, istd):
+    """dy = gamma istd (gm - mean(gm) - yhat mean(gm yhat)) as the kernels form it: A gm + B y + C from the sums S0 = sum gm, S1 = sum gm y."""
+    n = y.shape[0]
+    gm = g if mask is None else g * mask
+    S0, S1 = gm.sum(0), (gm * y).sum(0)
+    sgy = istd * (S1 - mean * S0)
+    A = gamma.double() * istd
+    B = -A * (sgy / n) * istd
+    Cc = -A * (S0 / n) - B * mean
+    return dict(gm=gm, S0=S0, S1=S1, dgamma=sgy, dbeta=S0, A=A, B=B, C=Cc, dy=A * gm + B * y + Cc)
+
+
+def ambiguous(y, gamma, beta, st):
+    """Forward elements whose float64 pre-activation lies within 4u (|y scale| + |shift|) of zero."""
+    f = ref_fwd(y, gamma, beta, st["mean"], st["istd"], 1)
+    return f["pre"].abs() <= 4 * U * f["mag_mask"]
+
+
+def dy_bound(bq, y, mean, istd, E0, dsgy):
+    """Bound on dy = A g + B y + C before the store, from Rq (bq) and the bounds E0, dsgy on the errors of sum g and sum g yhat.  The device's
+    B and C sit within dB, dC of Rq's: their sum moves by dB |y - mean| + |A| E0 / n only, but the f32 operations round the device's own
+    terms B y and C one by one -- where var ~ 0 (one pixel, a constant channel) istd^2 = 1 / eps makes dB |y| far larger than B y."""
+    n = float(y.shape[0])
+    dB = bq["A"].abs() * istd * dsgy / n
+    dC = bq["A"].abs() * E0 / n + dB * mean.abs()
+    mag = (bq["A"] * bq["gm"]).abs() + (bq["B"].abs() + dB) * y.abs() + bq["C"].abs() + dC
+    return SLOP * (4 * U * mag + dB * (y - mean).abs() + bq["A"].abs() * E0 / n)
+
+
+# ================================================================ cases
+C_LIST = {"f32": [4, 12, 20, 36, 128, 260, 512], "bf16": [8, 24, 40, 72, 256, 504, 512]}
+NPIX_LIST = [1, 2, 37, 3001]
+BIG_NPIX = 262147                    # with C = 12 (f32) / 24 (bf16): cvecs = 3, 255 threads, 786 441 vectors > 768 * 255 * 4 -> 5 ragged passes
+CASES = [(dt, C, n, relu) for dt in ("f32", "bf16") for C in C_LIST[dt] for n in NPIX_LIST for relu in (0, 1)]
+CASES += [(dt, 3 * VE[dt], BIG_NPIX, relu) for dt in ("f32", "bf16") for relu in (0, 1)]
+_ids = lambda c: f"{c[0]}-C{c[1]}-n{c[2]}-relu{c[3]}"
+
+
+def make_case(dt, C, npix, relu, regime="span", const_channel=None):
+    """Host tensors of one case; y / dout already rounded to the storage type.  "span": per-channel magnitudes over four decades, the scale
+    of y rising and that of gamma falling with the channel (1e-2 .. 1e2 each).  "shift": channel mean 8, std 0.25 (mean^2 / var ~ 1000)."""
+    g = torch.Generator().manual_seed(C * 100003 + npix * 7 + relu)
+    ramp = torch.logspace(-2, 2, C) if C > 1 else torch.ones(1)
+    if regime == "span":
+        y = (torch.randn(npix, C, generator=g) * 1.7 + 0.3) * ramp
+        gamma = (torch.rand(C, generator=g) + 0.5) * ramp.flip(0)
+    else:
+        y = torch.randn(npix, C, generator=g) * 0.25 + 8.0
+        gamma = torch.rand(C, generator=g) + 0.5
+    if const_channel is not None:
+        y[:, const_channel] = 0.75
+    beta = (torch.rand(C, generator=g) * 0.3 + 0.1) * (torch.randint(0, 2, (C,), generator=g) * 2 - 1).float()
+    rm, rv = torch.randn(C, generator=g) * 0.1, torch.rand(C, generator=g) + 0.5
+    dout = torch.randn(npix, C, generator=g)
+    pre_dg, pre_db = torch.randn(C, generator=g), torch.randn(C, generator=g)
+    q = lambda t: t.to(TDT[dt])
+    return dict(dt=dt, C=C, npix=npix, relu=relu, y=q(y), dout=q(dout), gamma=gamma, beta=beta, rm=rm, rv=rv, pre_dg=pre_dg, pre_db=pre_db)
+
+
+def check_ambiguous_cap(c):
+    if not c["relu"]:
+        return 0
+    y = c["y"].double()
+    amb = ambiguous(y, c["gamma"], c["beta"], ref_stats(y))
+    count = int(amb.sum())
+    assert count <= 1e-3 * y.numel(), (count, y.numel())
+    return count
+
+
+# ================================================================ CPU self-checks
+@pytest.mark.parametrize("relu", [0, 1])
+@pytest.mark.parametrize("npix,C", [(3, 4), (2, 8), (37, 12), (150, 24)])
+def test_r64_matches_torch_float64(npix, C, relu):
+    g = torch.Generator().manual_seed(npix + C)
+    y = (torch.randn(npix, C, generator=g, dtype=torch.float64) * 1.7 + 0.3).requires_grad_(True)
+    gamma = (torch.rand(C, generator=g, dtype=torch.float64) + 0.5).requires_grad_(True)
+    beta = torch.randn(C, generator=g, dtype=torch.float64).requires_grad_(True)
+    rm, rv = torch.randn(C, generator=g, dtype=torch.float64), torch.rand(C, generator=g, dtype=torch.float64) + 0.5
+    dout = torch.randn(npix, C, generator=g, dtype=torch.float64)
+    rm_t, rv_t = rm.clone(), rv.clone()
+    o = F.batch_norm(y.t()[None], rm_t, rv_t, gamma, beta, True, MOM, EPS)          # [1, C, npix]
+    o = F.relu(o) if relu else o
+    o.backward(dout.t()[None])
+    st = ref_stats(y.detach(), rm, rv)
+    f = ref_fwd(y.detach(), gamma.detach(), beta.detach(), st["mean"], st["istd"], relu)
+    b = ref_bwd(dout, y.detach(), (f["out"] > 0).double() if relu else None, gamma.detach(), st["mean"], st["istd"])
+    tol = dict(rtol=0, atol=1e-12)
+    torch.testing.assert_close(f["out"], o.detach()[0].t(), **tol)
+    torch.testing.assert_close(st["rm"], rm_t, **tol)
+    torch.testing.assert_close(st["rv"], rv_t, **tol)
+    if npix > 1:        # one pixel: var = 0 and autograd's istd^3 factors amplify the last bit by 1 / eps
+        torch.testing.assert_close(b["dy"], y.grad, rtol=0, atol=1e-9 if npix == 2 else 1e-12)
+    torch.testing.assert_close(b["dgamma"], gamma.grad, **tol)
+    torch.testing.assert_close(b["dbeta"], beta.grad, **tol)
+
+
+def test_rq_equals_r64_without_rounding():
+    """f32 storage with the statistics kept in float64 and the mask taken from Rq's own unrounded `out`: Rq's chain is R64's."""
+    c = make_case("f32", 20, 37, 1)
+    y, g = c["y"].double(), c["dout"].double()
+    st = ref_stats(y)
+    f64 = ref_fwd(y, c["gamma"], c["beta"], st["mean"], st["istd"], 1)
+    out_q = rq_store(f64["out"], "f32")                                 # f32 storage of a float64 tensor: nothing is rounded
+    assert torch.equal(out_q, f64["out"])
+    bq = ref_bwd(g, y, (out_q > 0).double(), c["gamma"], st["mean"], st["istd"])
+    yhat = (y - st["mean"]) * st["istd"]
+    gm = g * (f64["pre"] > 0)
+    dy = c["gamma"].double() * st["istd"] * (gm - gm.mean(0) - yhat * (gm * yhat).mean(0))
+    torch.testing.assert_close(bq["dy"], dy, rtol=1e-13, atol=1e-12)          # values up to 1e4 in the large channels
+    torch.testing.assert_close(bq["dgamma"], (gm * yhat).sum(0), rtol=1e-13, atol=1e-12)
+    assert torch.equal(half_ulp_bf16(torch.tensor([1.0, 1.5, 0.75, 0.0, -3.0], dtype=torch.float64)),
+                       torch.tensor([2.0 ** -8, 2.0 ** -8, 2.0 ** -9, 0.0, 2.0 ** -7], dtype=torch.float64))
+
+
+def test_dy_bound_holds_for_one_pixel_in_f32():
+    """One pixel needs no summation order, so the backward kernels can be followed exactly on the CPU: f32 products, the finalize in double,
+    coefficients rounded to f32, dy = (A g + B y) + C in f32.  var = 0 and mean = y: dy is 0 in exact arithmetic, S1 - mean S0 is the
+    rounding of g y alone, and istd^2 = 1 / eps turns it into coefficients B, C whose terms cancel only up to their own rounding."""
+    worst = 0.0
+    for C in (128, 512):
+        for relu in (0, 1):
+            c = make_case("f32", C, 1, relu)
+            y, g = c["y"].double(), c["dout"].double()
+            mean = y[0].clone()
+            istd = torch.full((C,), float(np.float32(1.0 / math.sqrt(EPS))), dtype=torch.float64)
+            out = ref_fwd(y, c["gamma"], c["beta"], mean, istd, relu)["out"]
+            bq = ref_bwd(g, y, (out > 0).double() if relu else None, c["gamma"], mean, istd)
+            gm32, y32 = bq["gm"][0].float(), y[0].float()
+            s0, s1 = gm32.double(), (gm32 * y32).double()
+            sgy = istd * (s1 - mean * s0)
+            A = c["gamma"].double() * istd
+            Af, Bf, Cf = A.float(), (-A * sgy * istd).float(), (-A * s0 + A * sgy * istd * mean).float()
+            dy = ((Af * gm32 + Bf * y32) + Cf).double()
+            E0, E1 = sum_err(bq["gm"], "f32"), sum_err(bq["gm"] * y, "f32", products=True)
+            eb = dy_bound(bq, y, mean, istd, E0, istd * (E1 + mean.abs() * E0))[0]
+            ratio = (dy - bq["dy"][0]).abs() / eb.clamp_min(1e-300)
+            assert float(ratio.max()) <= 1.0, (C, relu, float(ratio.max()))
+            worst = max(worst, float(ratio.max()))
+    assert worst > 0.01, worst
+
+
+def test_geometry_covers_every_pixel_once():
+    for dt, C, npix in [("f32", 12, 1000), ("bf16", 504, 37), ("f32", 12, BIG_NPIX), ("bf16", 8, 3001), ("f32", 512, 3001)]:
+        K, blocks, T = geometry(npix, C, dt)
+        cvecs = C // VE[dt]
+        threads = block_threads_for(cvecs)
+        assert threads % cvecs == 0 and threads <= 256 and T * blocks * K >= npix and (T - 1) * blocks * K < npix
+        if npix == BIG_NPIX:
+            assert blocks == ELEM_MAX_BLOCKS and T == 5 and threads == 255
+        t = torch.ones(npix, C, dtype=torch.float64)
+        assert float(sum_err(t, dt).max()) < SLOP * U * npix * npix        # running sums of ones: below the n^2 / 2 of one long chain
+
+
+def test_ambiguous_share_within_cap():
+    worst = 0
+    for c in CASES:
+        worst = max(worst, check_ambiguous_cap(make_case(*c)))
+    for dt in ("f32", "bf16"):
+        check_ambiguous_cap(make_case(dt, 9 * VE[dt], 3001, 1, regime="shift"))
+        check_ambiguous_cap(make_case(dt, 5 * VE[dt], 3001, 1, const_channel=3))
+    print("ambiguous elements, worst case:", worst)
+
+
+def test_scratch_macro_covers_carve():
+    """capi.cpp carves 1024 partial rows x 3 x 512 floats and up to 3 coefficient rows of 512 out of the BatchNorm scratch."""
+    assert _header_macro("MMVAE_BN_SCRATCH_BYTES") >= (1024 * 3 * 512 + 8 * 512) * 4
+
+
+# ================================================================ device plumbing
+class Arena:
+    """A window of exactly `nbytes` inside a larger allocation filled with a byte pattern: an overrun changes guard bytes, never faults."""
+
+    def __init__(self, nbytes, fill=PATTERN):
+        self.n = nbytes
+        self.pad = (-nbytes) % 256
+        self.buf = torch.full((GUARD + nbytes + self.pad + GUARD,), fill, dtype=torch.uint8, device="cuda")
+        self.fill = fill
+
+    def view(self, dtype, shape):
+        return self.buf[GUARD:GUARD + self.n].view(dtype).view(shape)
+
+    def ptr(self):
+        return self.buf.data_ptr() + GUARD
+
+    def intact(self):
+        return bool((self.buf[:GUARD] == self.fill).all()) and bool((self.buf[GUARD + self.n:] == self.fill).all())
+
+    def untouched(self):
+        return bool((self.buf == self.fill).all())
+
+
+def window(t, fill=PATTERN):
+    """Copy of tensor t (or an uninitialised tensor of its shape when t is a (shape, dtype) pair) inside a guarded arena."""
+    if isinstance(t, tuple):
+        shape, dtype = t
+        a = Arena(int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size(), fill)
+        return a, a.view(dtype, shape)
+    a = Arena(t.numel() * t.element_size(), fill)
+    v = a.view(t.dtype, tuple(t.shape))
+    v.copy_(t)
+    return a, v
+
+
+_RATIOS = {}
+
+
+def gate(name, err, bound, what, storage=None):
+    """err <= bound for every channel (err, bound: [C] or [npix, C] -> per-channel maximum of err / bound)."""
+    ratio = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, torch.full_like(err, math.inf), torch.zeros_like(err)))
+    if ratio.dim() == 2:
+        ratio = ratio.max(0).values
+    worst = float(ratio.max())
+    _RATIOS[name] = max(_RATIOS.get(name, 0.0), worst)
+    print(f"RATIO {name} {worst:.4f} (so far {_RATIOS[name]:.4f}) {what}")
+    bad = (ratio > 1).nonzero().flatten().tolist()
+    assert not bad, (name, what, "channels", bad[:8], "worst err/bound", worst,
+                     "storage error |Rq - R64| max", None if storage is None else float(storage.max()))
+
+
+def run_case(c, null_running=False, report=None):
+    """Forward + backward of one case on the device inside guarded windows; every output gated per channel."""
+    L = _L(); lib = L.lib()
+    dt, C, npix, relu = c["dt"], c["C"], c["npix"], c["relu"]
+    what = f"{dt} C={C} npix={npix} relu={relu}"
+    amb_count = check_ambiguous_cap(c)                                   # CPU-only, before any device output is looked at
+    y, g = c["y"].double(), c["dout"].double()
+    gamma, beta = c["gamma"], c["beta"]
+    st64 = ref_stats(y, c["rm"], c["rv"])
+    st = torch.cuda.current_stream().cuda_stream
+    scratch = Arena(_header_macro("MMVAE_BN_SCRATCH_BYTES"))
+    arenas = {"scratch": scratch}
+
+    def dev(name, t, fill=PATTERN):
+        arenas[name], v = window(t, fill)
+        return v
+    yd, gd, bd = dev("y", c["y"].cuda()), dev("gamma", gamma.cuda()), dev("beta", beta.cuda())
+    rmd = None if null_running else dev("rm", c["rm"].cuda())
+    rvd = None if null_running else dev("rv", c["rv"].cuda())
+    nbt = None if null_running else dev("nbt", torch.tensor([41], dtype=torch.int64).cuda())
+    od = dev("out", ((npix, C), TDT[dt]), 0xFF)                           # 0xFF bytes: NaN in f32 and in bf16
+    sm, si = dev("save_mean", ((C,), torch.float32), 0xFF), dev("save_istd", ((C,), torch.float32), 0xFF)
+    L.check(lib.mmvae_batchnorm_fwd(DTI[dt], L.ptr(yd), npix, C, L.ptr(gd), L.ptr(bd), L.ptr(rmd), L.ptr(rvd), L.ptr(nbt), MOM, EPS, relu, L.ptr(od),
+                                    L.ptr(sm), L.ptr(si), scratch.ptr(), st), "batchnorm_fwd")
+    torch.cuda.synchronize()
+    out_dev = od.cpu()
+    sm_h, si_h = sm.cpu().double(), si.cpu().double()
+    # backward: twice, on the device's own out / save_mean / save_istd, into pre-filled dgamma / dbeta and a NaN-filled dy
+    doutd = dev("dout", c["dout"].cuda())
+    res = []
+    for rep in range(2):
+        dyd = dev(f"dy{rep}", ((npix, C), TDT[dt]), 0xFF)
+        dg, db = dev(f"dgamma{rep}", c["pre_dg"].cuda()), dev(f"dbeta{rep}", c["pre_db"].cuda())
+        L.check(lib.mmvae_batchnorm_bwd(DTI[dt], L.ptr(doutd), L.ptr(yd), L.ptr(od) if relu else None, npix, C, L.ptr(gd), L.ptr(sm), L.ptr(si),
+                                        L.ptr(dyd), L.ptr(dg), L.ptr(db), scratch.ptr(), st), "batchnorm_bwd")
+        res.append((dyd, dg, db))
+    torch.cuda.synchronize()
+    for name, a in arenas.items():
+        assert a.intact(), ("guard bytes changed around", name, what)
+    for a, b in zip(res[0], res[1]):
+        assert torch.equal(a.view(torch.uint8), b.view(torch.uint8)), ("backward is not bit-reproducible", what)
+    assert torch.equal(yd.cpu(), c["y"]) and torch.equal(doutd.cpu(), c["dout"]) and torch.equal(od.cpu(), out_dev), ("an input was written", what)
+
+    # ---- statistics against R64
+    n = float(npix)
+    e1, e2 = sum_err(y, dt), sum_err(y * y, dt, products=True)
+    dmean = e1 / n
+    dvar = e2 / n + 2 * st64["mean"].abs() * dmean + dmean * dmean
+    f = lambda v: 1.0 / torch.sqrt(v + EPS)
+    distd = torch.maximum((f(st64["var"] + dvar) - st64["istd"]).abs(), (f((st64["var"] - dvar).clamp_min(0)) - st64["istd"]).abs())
+    gate("save_mean", (sm_h - st64["mean"]).abs(), SLOP * (dmean + U * st64["mean"].abs()), what)
+    gate("save_istd", (si_h - st64["istd"]).abs(), SLOP * (distd + U * st64["istd"]), what)
+    if not null_running:
+        gate("running_mean", (rmd.cpu().double() - st64["rm"]).abs(), SLOP * (MOM * dmean + U * st64["rm"].abs()), what)
+        gate("running_var", (rvd.cpu().double() - st64["rv"]).abs(),
+             SLOP * (MOM * (n / (n - 1) if npix > 1 else 1.0) * dvar + U * st64["rv"].abs()), what)
+        assert int(nbt.item()) == 42, what
+    if report is not None:
+        report.update(istd_err=((si_h - st64["istd"]).abs() / st64["istd"]).max().item(), istd_bound=(SLOP * (distd + U * st64["istd"]) / st64["istd"]).max().item(),
+                      st64=st64)
+    # ---- out against Rq built on the device's own statistics
+    fq = ref_fwd(y, gamma, beta, sm_h, si_h, relu)
+    f64 = ref_fwd(y, gamma, beta, st64["mean"], st64["istd"], relu)
+    eb = 4 * U * SLOP * fq["mag"]
+    if dt == "bf16":
+        eb = eb + half_ulp_bf16(fq["out"].abs() + eb)
+    gate("out", (out_dev.double() - fq["out"]).abs(), eb, what, storage=(rq_store(fq["out"], dt) - f64["out"]).abs())
+    # ---- backward against Rq: mask = sign of the stored out, statistics = the f32 save_mean / save_istd
+    mask = (out_dev.double() > 0).double() if relu else None
+    bq = ref_bwd(g, y, mask, gamma, sm_h, si_h)
+    b64 = ref_bwd(g, y, (f64["out"] > 0).double() if relu else None, gamma, st64["mean"], st64["istd"])
+    E0, E1 = sum_err(bq["gm"], dt), sum_err(bq["gm"] * y, dt, products=True)
+    dsgy = si_h * (E1 + sm_h.abs() * E0)
+    dyd, dg, db = (t.cpu().double() for t in res[0])
+    pg, pb = c["pre_dg"].double(), c["pre_db"].double()
+    gate("dgamma", (dg - (pg + bq["dgamma"])).abs(), SLOP * (dsgy + U * bq["dgamma"].abs() + U * (pg + bq["dgamma"]).abs()), what,
+         storage=(bq["dgamma"] - b64["dgamma"]).abs())
+    gate("dbeta", (db - (pb + bq["dbeta"])).abs(), SLOP * (E0 + U * bq["dbeta"].abs() + U * (pb + bq["dbeta"]).abs()), what,
+         storage=(bq["dbeta"] - b64["dbeta"]).abs())
+    eb = dy_bound(bq, y, sm_h, si_h, E0, dsgy)
+    if dt == "bf16":
+        eb = eb + half_ulp_bf16(bq["dy"].abs() + eb)
+    assert not torch.isnan(dyd).any(), ("dy keeps NaN of its fill", what)
+    gate("dy", (dyd - bq["dy"]).abs(), eb, what, storage=(rq_store(bq["dy"], dt) - b64["dy"]).abs())
+    return dict(out=out_dev, beta=beta, fq=fq, amb=amb_count, dmean=SLOP * (dmean + U * st64["mean"].abs()), scale=(gamma.double() * si_h).abs())
+
+
+# ================================================================ GPU tests
+@gpu
+@pytest.mark.parametrize("case", CASES, ids=_ids)
+def test_batchnorm_f64(case):
+    run_case(make_case(*case))
+
+
+@gpu
+@pytest.mark.parametrize("dt", ["f32", "bf16"])
+def test_batchnorm_null_running_stats(dt):
+    run_case(make_case(dt, 5 * VE[dt], 37, 1), null_running=True)
+
+
+@gpu
+@pytest.mark.parametrize("relu", [0, 1])
+@pytest.mark.parametrize("dt", ["f32", "bf16"])
+def test_batchnorm_shifted_regime(dt, relu):
+    """Channel mean 8, std 0.25: the kernel's var = E[y^2] - mean^2 from f32 partial sums loses (1 + mean^2 / var) ~ 1000 times what a centred
+    sum loses; the bound on save_istd carries that factor.  The measured error is printed next to F.batch_norm's in f32 on the CPU."""
+    c = make_case(dt, 9 * VE[dt], 3001, relu, regime="shift")
+    rep = {}
+    run_case(c, report=rep)
+    yf = c["y"].float().t()[None].contiguous()
+    _, _, t_istd = torch.native_batch_norm(yf, c["gamma"], c["beta"], None, None, True, MOM, EPS)
+    t_err = ((t_istd.double() - rep["st64"]["istd"]).abs() / rep["st64"]["istd"]).max().item()
+    print(f"SHIFTED {dt} relu={relu}: save_istd rel err device {rep['istd_err']:.3e} (bound {rep['istd_bound']:.3e}), torch f32 CPU {t_err:.3e}")
+
+
+@gpu
+@pytest.mark.parametrize("npix", [37, 3001])
+@pytest.mark.parametrize("dt", ["f32", "bf16"])
+def test_batchnorm_constant_channel(dt, npix):
+    """Channel 3 holds 0.75 everywhere: var = 0, istd = 1 / sqrt(eps), out = beta within the elementwise bound; running_var follows R64
+    (gated inside run_case like every channel)."""
+    c = make_case(dt, 5 * VE[dt], npix, 0, const_channel=3)
+    r = run_case(c)
+    fq = r["fq"]
+    err = (r["out"].double()[:, 3] - float(c["beta"][3])).abs()
+    bound = SLOP * 4 * U * fq["mag"][:, 3] + r["scale"][3] * r["dmean"][3]      # pre - beta = scale (y - save_mean): the derived mean error
+    if dt == "bf16":
+        bound = bound + half_ulp_bf16(c["beta"][3].double().abs() + bound)
+    assert (err <= bound).all(), (dt, npix, float(err.max()), float(bound.max()))
+
+
+@gpu
+@pytest.mark.parametrize("dt", ["f32", "bf16"])
+def test_batchnorm_refusals(dt):
+    """C not a multiple of the 16-byte vector, C = 0, C = 516 and NULL scratch return < 0 and leave pattern-filled outputs untouched."""
+    L = _L(); lib = L.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    npix = 16
+    scratch = Arena(_header_macro("MMVAE_BN_SCRATCH_BYTES"))
+    big = 520
+    yd = torch.ones(npix * big, device="cuda", dtype=TDT[dt])
+    vec = torch.ones(big, device="cuda")
+    outs = {k: window(((npix * big,), TDT[dt]))[0] for k in ("out", "dy")}
+    outs.update({k: window(((big,), torch.float32))[0] for k in ("sm", "si", "rm", "rv", "dg", "db")})
+    outs["nbt"] = window(((1,), torch.int64))[0]
+    bad_c = [0, 516, VE[dt] // 2, VE[dt] + VE[dt] // 2, 510 if dt == "f32" else 508]
+    for C, sc in [(c, scratch.ptr()) for c in bad_c] + [(2 * VE[dt], None)]:
+        rc = lib.mmvae_batchnorm_fwd(DTI[dt], L.ptr(yd), npix, C, L.ptr(vec), L.ptr(vec), outs["rm"].ptr(), outs["rv"].ptr(), outs["nbt"].ptr(), MOM, EPS, 1,
+                                     outs["out"].ptr(), outs["sm"].ptr(), outs["si"].ptr(), sc, st)
+        assert rc < 0, ("fwd", C, sc, rc)
+        rc = lib.mmvae_batchnorm_bwd(DTI[dt], L.ptr(yd), L.ptr(yd), L.ptr(yd), npix, C, L.ptr(vec), L.ptr(vec), L.ptr(vec), outs["dy"].ptr(),
+                                     outs["dg"].ptr(), outs["db"].ptr(), sc, st)
+        assert rc < 0, ("bwd", C, sc, rc)
+    torch.cuda.synchronize()
+    for k, a in outs.items():
+        assert a.untouched(), ("a refused call wrote", k)
+    assert scratch.untouched()
