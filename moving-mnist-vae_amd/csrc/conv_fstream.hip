@@ -543,8 +543,8 @@ __global__ __launch_bounds__(256, 3) void convT4_stream_kernel(ConvT4StreamArgs 
 // up5_tail_fwd_kernel: tail_fwd_stream_kernel reads the two 64x64x16 branch outputs (1.34 GB at 5120 frames) that convT4_stream_kernel wrote a
 // moment ago; the forward kernels of this block are memory-bound (e4m3 storage of those tensors makes them 28-35 % faster, DESIGN lesson 36).
 // Here a wave keeps rings of the two ConvTranspose2d INPUT rows (32x32x16: 0.34 GB together) and recomputes both branch outputs for the
-// two output rows of an input row exactly like convT4_stream_kernel does (same MFMA sequence, the results rounded to bf16 like the stored
-// tensors), joins them in the D-fragment mapping (lane = 4 channels of one output pixel) into the ring of joined rows the tail conv reads.
+// two output rows of an input row exactly like convT4_stream_kernel does (same MFMA sequence; the f32 accumulators are NOT rounded to bf16 as the
+// stored tensors are), joins them in the D-fragment mapping (lane = 4 channels of one output pixel) into the ring of joined rows (bf16) the tail conv reads.
 // y2 / ys are still written by convT4_stream_kernel (statistics; the backward pass reads them): this kernel only stops READING them.
 struct Up5TailFwdArgs {
   const void* y1; const float* p1s; const float* p1b; const void* w2;      // conv2 branch: input (pre-bn1), bn1 scale / shift, packed up weights
@@ -688,7 +688,7 @@ __global__ __launch_bounds__(256, 2) void up5_tail_fwd_kernel(Up5TailFwdArgs a) 
               accS[pt] = mma_bf16(wuA[2 * ph + pw][th], *reinterpret_cast<const Vec16*>(ringX + off), accS[pt]);
             }
           }
-          // lane (r = input column p, gq) holds output channels 4gq .. 4gq+3 of output pixel 2p + pw: round like the stored tensors, join
+          // lane (r = input column p, gq) holds output channels 4gq .. 4gq+3 of output pixel 2p + pw: join the f32 accumulators, round the joined value
 #pragma unroll
           for (int pt = 0; pt < 2; ++pt) {
             float o[4];
