@@ -234,6 +234,26 @@ MMVAE_API int mmvae_normalise_labels(const int64_t* labels, int64_t n, float mea
  * utils.py:279-309; lowest index wins ties) -> labels int64 (may be NULL) and image = (label-mean)/std f32 (may be NULL). */
 MMVAE_API int mmvae_quantise_normalise(const uint8_t* frames, int64_t n, const float* centres, int q, float mean, float stdv,
                              int64_t* labels, float* image, void* stream);
+/* Fitting that quantiser (utils.save_kmeans_file, utils.py:279-309).  Everything the reference derives by sampling is an exact function
+ * of the byte histogram of the data, taken in one pass on the device:
+ * counts[b] += occurrences of byte b.  clip_index == NULL: the bytes [0, n_clips * clip_bytes) of frames; otherwise the n_clips clips
+ * frames + clip_index[i] * clip_bytes (device int64; repeats are counted again; the CALLER keeps every index inside the buffer).
+ * counts: 256 device uint64, ADDED to (the caller zeroes them; several buffers may share one histogram).  frames and clip_bytes may
+ * have any alignment.  n_clips == 0 is a no-op.  Integer atomics only: the same bits every run. */
+MMVAE_API int mmvae_u8_histogram(const uint8_t* frames, int64_t clip_bytes, const int64_t* clip_index, int64_t n_clips, uint64_t* counts,
+                       void* stream);
+/* HOST function, every pointer host memory: exact weighted k-means of the 256 byte values b/255 (weights counts[b]) into q clusters by
+ * dynamic programming over contiguous partitions of the non-empty bins (ties: the smallest cut index).  centres[q]: the weighted means,
+ * ASCENDING, on the ToTensor scale -- label k is the k-th darkest cluster, where scikit-learn's label order is arbitrary (data_mean /
+ * data_std below depend on the order).  inertia (may be NULL): sum_b counts[b] (b/255 - centre(b))^2.  MMVAE_ERR_ARG: q < 1, q > 256,
+ * all counts zero, q > the number of distinct values present (the message names it); MMVAE_ERR_UNSUPPORTED: more than 2^64 / 255^2
+ * pixels. */
+MMVAE_API int mmvae_kmeans1d_fit(const uint64_t* counts, int q, double* centres, double* inertia);
+/* HOST function: lut[b] = the label mmvae_quantise_normalise gives byte b with these f32 centres (the kernel's own f32 arithmetic and
+ * tie rule), and from counts and lut in f64: ratios[q] (class frequencies, utils.py:296-297), the mean and the POPULATION std of the
+ * labels (utils.py:298-299: main.py's data_mean / data_std, unrounded).  ratios, label_mean, label_std may be NULL. */
+MMVAE_API int mmvae_quantiser_stats(const uint64_t* counts, const float* centres, int q, uint8_t* lut, double* ratios, double* label_mean,
+                          double* label_std);
 /* torch.optim.Adam defaults (main.py:468) over a flat buffer: bc1 = 1-beta1^t, bc2_sqrt = sqrt(1-beta2^t);
  * grad_scale multiplies the gradient first (1/world_size after a sum all-reduce). */
 MMVAE_API int mmvae_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,

@@ -65,6 +65,9 @@ PROTOTYPES = {
     "mmvae_iw_bound": (c_int, [P, P, c_int, c_int, P, P]),
     "mmvae_normalise_labels": (c_int, [P, c_int64, c_float, c_float, P, P]),
     "mmvae_quantise_normalise": (c_int, [P, c_int64, P, c_int, c_float, c_float, P, P, P]),
+    "mmvae_u8_histogram": (c_int, [P, c_int64, P, c_int64, P, P]),
+    "mmvae_kmeans1d_fit": (c_int, [P, c_int, P, P]),
+    "mmvae_quantiser_stats": (c_int, [P, P, c_int, P, P, P, P]),
     "mmvae_adam_step": (c_int, [P, P, P, P, c_int64, c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_float, P]),
     "mmvae_adam_step_dev": (c_int, [P, P, P, P, c_int64, c_float, c_float, c_float, c_float, c_float, P, c_float, P]),
     "mmvae_grad_norm_sq": (c_int, [P, c_int64, c_float, P, P, P]),

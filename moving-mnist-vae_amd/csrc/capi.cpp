@@ -5,6 +5,7 @@
 #include "../../include/mmvae.h"
 #include "conv_ops.hpp"
 #include "pixel_net.hpp"
+#include "quantiser_fit.hpp"
 #include "vae_net.hpp"
 
 namespace mmvae { const char* last_error(); }
@@ -313,6 +314,15 @@ int mmvae_normalise_labels(const int64_t* labels, int64_t n, float mean, float s
 int mmvae_quantise_normalise(const uint8_t* frames, int64_t n, const float* centres, int q, float mean, float stdv, int64_t* labels,
                              float* image, void* st) {
   return launch_quantise_normalise(frames, (long)n, centres, q, mean, stdv, reinterpret_cast<long long*>(labels), image, S(st));
+}
+int mmvae_u8_histogram(const uint8_t* frames, int64_t clip_bytes, const int64_t* clip_index, int64_t n_clips, uint64_t* counts, void* st) {
+  return launch_u8_histogram(frames, (long)clip_bytes, reinterpret_cast<const long long*>(clip_index), (long)n_clips,
+                             reinterpret_cast<unsigned long long*>(counts), S(st));
+}
+int mmvae_kmeans1d_fit(const uint64_t* counts, int q, double* centres, double* inertia) { return kmeans1d_fit(counts, q, centres, inertia); }
+int mmvae_quantiser_stats(const uint64_t* counts, const float* centres, int q, uint8_t* lut, double* ratios, double* label_mean,
+                          double* label_std) {
+  return quantiser_stats(counts, centres, q, lut, ratios, label_mean, label_std);
 }
 int mmvae_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd, float bc1,
                     float bc2_sqrt, float grad_scale, void* st) {

@@ -401,6 +401,10 @@ int launch_adam_guarded(const AdamArgs& a, double* state, double* part, float ma
 int launch_normalise(int dt, const void* labels, int label_bytes, long n, float mean, float stdv, void* img_t, float* img_f32, hipStream_t s);
 int launch_quantise_normalise(const unsigned char* frames, long n, const float* centres, int q, float mean, float stdv,
                               long long* labels, float* image, hipStream_t s);
+// counts[b] += occurrences of byte b in n_clips ranges of clip_bytes bytes: frames + clip_index[i] * clip_bytes, or the contiguous
+// [0, n_clips * clip_bytes) with clip_index == nullptr (quantiser.hip); any alignment of frames and clip_bytes
+int launch_u8_histogram(const unsigned char* frames, long clip_bytes, const long long* clip_index, long n_clips,
+                        unsigned long long* counts, hipStream_t s);
 int launch_convert(int dt_in, int dt_out, const void* in, void* out, long n, hipStream_t s);
 int launch_fill_f32(float* p, float v, long n, hipStream_t s);
 int launch_concat2_to_t(int dt, const float* a, const float* b, int rows, int ca, int cb, void* out, hipStream_t s);

@@ -337,6 +337,121 @@ def quantise_frames(frames_u8, centres, data_mean, data_std):
     return labels, image
 
 
+def pixel_histogram(frames_u8, clip_index=None):
+    """Byte histogram of uint8 frames on the device: a (256,) int64 device tensor, ``counts[b]`` = occurrences of byte ``b``
+    (exact; integer atomics, so the same bits every run).  ``frames_u8``: a contiguous uint8 device tensor of any alignment whose
+    leading axis is the clip axis.  ``clip_index`` (int64 indices into that axis; repeats count again) histograms only those
+    clips, without materialising a gather -- the reference's "3000 random clips" (utils.py:284); the indices are checked against
+    the clip axis first (one device -> host read), since the kernel trusts them."""
+    from ._lib import check, lib, ptr
+    f = frames_u8.contiguous()
+    if f.dtype != torch.uint8 or not f.is_cuda:
+        raise ValueError("pixel_histogram expects a uint8 tensor on the GPU")
+    if f.dim() < 1:
+        raise ValueError("pixel_histogram expects a leading clip axis")
+    counts = torch.zeros(256, dtype=torch.int64, device=f.device)
+    n = f.shape[0]
+    clip_bytes = f.numel() // n if n else 0
+    idx = None
+    if clip_index is not None:
+        idx = torch.as_tensor(clip_index, dtype=torch.int64, device=f.device).reshape(-1).contiguous()
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n):
+            raise IndexError(f"pixel_histogram: clip_index outside [0, {n})")
+        n = idx.numel()
+    with torch.cuda.device(f.device):
+        check(lib().mmvae_u8_histogram(ptr(f), clip_bytes, ptr(idx), n, ptr(counts), torch.cuda.current_stream().cuda_stream),
+              "mmvae_u8_histogram")
+    return counts
+
+
+class QuantiserFit:
+    """What ``fit_quantiser`` returns.  ``centres``: (q,) f64, ASCENDING, on the ToTensor scale [0, 1] -- label k is the k-th darkest
+    cluster (scikit-learn's label order is arbitrary, and ``data_mean`` / ``data_std``, statistics of the labels, follow the order:
+    use a quantiser with its own statistics).  ``data_mean`` / ``data_std``: mean and population std of the labels, unrounded.
+    ``ratios``: (q,) class frequencies.  ``counts``: (256,) int64 histogram the fit was made on.  ``inertia``: the k-means
+    objective on the ToTensor scale.  ``lut``: (256,) uint8, the label ``quantise_frames`` gives each byte with these centres."""
+
+    def __init__(self, centres, data_mean, data_std, ratios, counts, inertia, lut):
+        self.centres, self.data_mean, self.data_std, self.ratios = centres, data_mean, data_std, ratios
+        self.counts, self.inertia, self.lut = counts, inertia, lut
+
+    def weights(self, device=None):
+        """``args.data_ratio_of_labels`` under ``--weighted_entropy`` (main.py:481): ``1 - ratios`` as a float tensor."""
+        return torch.tensor(1.0 - self.ratios, dtype=torch.float32, device=device)
+
+
+def _fit_counts(counts, n_clusters):
+    """Host half of fit_quantiser: (256,) counts -> QuantiserFit through the library's exact 1-D k-means and label statistics."""
+    from ._lib import check, lib
+    q = int(n_clusters)
+    counts = np.ascontiguousarray(counts, dtype=np.uint64)
+    if counts.shape != (256,):
+        raise ValueError("expected 256 counts")
+    centres = np.zeros(max(q, 1), dtype=np.float64)
+    inertia = np.zeros(1, dtype=np.float64)
+    check(lib().mmvae_kmeans1d_fit(counts.ctypes.data, q, centres.ctypes.data, inertia.ctypes.data), "mmvae_kmeans1d_fit")
+    c32 = centres.astype(np.float32)                      # what quantise_frames hands the kernel
+    lut = np.zeros(256, dtype=np.uint8)
+    ratios = np.zeros(q, dtype=np.float64)
+    stats = np.zeros(2, dtype=np.float64)
+    check(lib().mmvae_quantiser_stats(counts.ctypes.data, c32.ctypes.data, q, lut.ctypes.data, ratios.ctypes.data, stats.ctypes.data,
+                                      stats.ctypes.data + 8), "mmvae_quantiser_stats")
+    return QuantiserFit(centres, float(stats[0]), float(stats[1]), ratios, counts.astype(np.int64), float(inertia[0]), lut)
+
+
+def fit_quantiser(source, n_clusters, clips=None, generator=None):
+    """Fit the k-means pixel quantiser on the device (the fit of utils.save_kmeans_file, utils.py:279-309): one histogram launch
+    over the resident uint8 data, one 2 KB device -> host copy, then the exact 1-D k-means and the label statistics on those 256
+    numbers.  ``source``: a uint8 device tensor (leading axis = clips) or a ``MovingMNISTClips``.  ``clips=None`` uses every clip
+    -- no sampling noise in ``data_mean`` / ``data_std``; an int draws that many DISTINCT clips with ``generator`` (the reference
+    uses 3000).  Deterministic given the clips; never worse than Lloyd's iterations.  Returns a ``QuantiserFit``."""
+    frames = source.clips if isinstance(source, MovingMNISTClips) else source
+    idx = None
+    if clips is not None:
+        n, k = frames.shape[0], int(clips)
+        if not 0 < k <= n:
+            raise ValueError(f"fit_quantiser: clips={k} of {n} available")
+        gdev = generator.device if generator is not None else "cpu"
+        idx = torch.randperm(n, generator=generator, device=gdev)[:k]
+    counts = pixel_histogram(frames, idx).cpu().numpy()                 # the one device -> host copy
+    return _fit_counts(counts, n_clusters)
+
+
+KMEANS_FILE_NOTE = ("k-means pixel quantiser: data only (numpy arrays), not a pickle. centres ascending on the [0, 1] scale; "
+                    "data_mean / data_std / ratios rounded to 4 digits; counts = the byte histogram fitted on.")
+
+
+def save_kmeans_file(n_clusters, dataset="MovingMNIST", folder="data", source=None, device="cuda"):
+    """The reference's entry point (utils.py:279-309) on the device.  ``source`` None loads ``folder``/movingmnisttrain.npz; else
+    an (N, C, W, H) uint8 array in the file's layout, a uint8 device tensor or a ``MovingMNISTClips``.  Fits on every clip, rounds
+    ``data_mean`` / ``data_std`` / ``ratios`` to 4 digits as utils.py:303-305 does, and writes ``folder``/kmeans_{dataset}_{q}.npz
+    (arrays only: centres, data_mean, data_std, ratios, counts and a note -- NOT the reference's joblib pickle of an sklearn
+    object; read it with ``load_kmeans_file``).  Returns ``(centres, data_mean, data_std, ratios)`` like utils.py:309, centres
+    of shape (q, 1) as ``kmeans.cluster_centers_``."""
+    import os
+    if source is None:
+        path = os.path.join(folder, "movingmnisttrain.npz")
+        if not os.path.isfile(path):
+            raise FileNotFoundError(path)
+        source = np.load(path)["arr_0"]
+    if isinstance(source, np.ndarray):
+        source = clips_from_npz_array(source).to(device)
+    fit = fit_quantiser(source, n_clusters)
+    data_mean, data_std, ratios = round(fit.data_mean, 4), round(fit.data_std, 4), fit.ratios.round(4)
+    os.makedirs(folder, exist_ok=True)
+    np.savez(os.path.join(folder, "kmeans_{:}_{:}.npz".format(dataset, int(n_clusters))), centres=fit.centres,
+             data_mean=np.float64(data_mean), data_std=np.float64(data_std), ratios=ratios, counts=fit.counts, note=np.str_(KMEANS_FILE_NOTE))
+    return fit.centres.reshape(-1, 1), data_mean, data_std, ratios
+
+
+def load_kmeans_file(path):
+    """Reads a file ``save_kmeans_file`` wrote (never unpickles): {'centres' (q,) f64, 'data_mean', 'data_std' floats, 'ratios' (q,),
+    'counts' (256,) int64}."""
+    with np.load(path, allow_pickle=False) as d:
+        return {"centres": d["centres"].astype(np.float64), "data_mean": float(d["data_mean"]), "data_std": float(d["data_std"]),
+                "ratios": d["ratios"].astype(np.float64), "counts": d["counts"].astype(np.int64)}
+
+
 def clips_from_npz_array(arr) -> torch.Tensor:
     """File layout of movingmnist{train,test}.npz ['arr_0'] is (N, C, W, H) uint8.  The reference dataset transposes it to
     (N, H, W, C) (movingmnistdataset.py:15) and ToTensor turns every sample into (C, H, W) (main.py:29-31): net effect, the
@@ -354,7 +469,8 @@ class MovingMNISTClips:
     int64 k-means labels of shape (B, C*H*W) -- so ``train()`` consumes it unchanged.  No host work per step.
 
     source: a folder holding movingmnisttrain.npz / movingmnisttest.npz, or an (N, C, W, H) uint8 array in the file's layout.
-    centres: the q k-means centres on the ToTensor scale [0, 1] (kmeans_dict['kmeans'].cluster_centers_.ravel())."""
+    centres: the q k-means centres on the ToTensor scale [0, 1] (kmeans_dict['kmeans'].cluster_centers_.ravel()), or None: call
+    ``fit_quantiser`` before iterating."""
 
     def __init__(self, source, centres, batch_size, device, train=True, shuffle=True, seed=None, drop_last=False):
         import os
@@ -366,7 +482,7 @@ class MovingMNISTClips:
         self.device = torch.device(device)
         self.clips = clips_from_npz_array(source).to(self.device)
         self.train_data = self.clips                  # len(dataset.train_data) is read by main.py:506
-        self.centres = torch.as_tensor(centres, dtype=torch.float32).reshape(-1)
+        self.centres = None if centres is None else torch.as_tensor(centres, dtype=torch.float32).reshape(-1)
         self.batch_size, self.shuffle, self.drop_last = int(batch_size), bool(shuffle), bool(drop_last)
         self._gen = torch.Generator(device="cpu")
         if seed is not None:
@@ -376,7 +492,16 @@ class MovingMNISTClips:
         n = self.clips.shape[0]
         return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
 
+    def fit_quantiser(self, n_clusters, clips=None, generator=None):
+        """Fits the quantiser on the resident clips (module-level ``fit_quantiser``), installs its centres and returns the
+        ``QuantiserFit`` (``data_mean`` / ``data_std`` for ``train``, ``weights()`` for ``args.data_ratio_of_labels``)."""
+        fit = fit_quantiser(self, n_clusters, clips=clips, generator=generator)
+        self.centres = torch.as_tensor(fit.centres, dtype=torch.float32).reshape(-1)
+        return fit
+
     def __iter__(self):
+        if self.centres is None:
+            raise RuntimeError("MovingMNISTClips has no k-means centres: pass `centres` or call .fit_quantiser(n_clusters) first")
         n = self.clips.shape[0]
         order = torch.randperm(n, generator=self._gen) if self.shuffle else torch.arange(n)
         order = order.to(self.device)

@@ -1,0 +1,240 @@
+"""CPU: the host half of the k-means pixel quantiser fit -- mmvae_kmeans1d_fit (exact weighted 1-D k-means of a byte histogram)
+and mmvae_quantiser_stats (byte -> label table by the quantise kernel's f32 rule, class ratios, label mean / std) -- driven
+through the C ABI with ctypes, against the committed scikit-learn fixtures, a brute-force enumeration in numpy, and edge cases.
+
+Tolerances.  Centres and inertia are ratios of exact integer sums, one or two f64 roundings each (about 1e-16 relative); the
+numpy references sum a few thousand f64 terms (about 1e-13).  1e-9 on the golden centres is still six orders below the 1/255
+grid; rel 1e-12 is asked wherever both sides are f64 sums."""
+import importlib
+import itertools
+from fractions import Fraction
+
+import numpy as np
+import pytest
+
+from conftest import load_golden
+
+OK, ERR_ARG, ERR_UNSUPPORTED = 0, -1, -4
+
+
+@pytest.fixture(scope="module")
+def L():
+    return importlib.import_module("moving-mnist-vae_amd._lib")
+
+
+def _hist(a):
+    return np.bincount(np.asarray(a, dtype=np.uint8).ravel(), minlength=256).astype(np.uint64)
+
+
+def _fit(L, counts, q):
+    """(rc, centres, inertia)"""
+    counts = np.ascontiguousarray(counts, dtype=np.uint64)
+    centres = np.full(max(int(q), 1), np.nan)
+    inertia = np.full(1, np.nan)
+    rc = L.lib().mmvae_kmeans1d_fit(counts.ctypes.data, int(q), centres.ctypes.data, inertia.ctypes.data)
+    return rc, centres, float(inertia[0])
+
+
+def _stats(L, counts, centres):
+    """(rc, lut, ratios, mean, std)"""
+    counts = np.ascontiguousarray(counts, dtype=np.uint64)
+    c32 = np.ascontiguousarray(centres, dtype=np.float32)
+    lut = np.full(256, 255, dtype=np.uint8)
+    ratios = np.full(c32.size, np.nan)
+    ms = np.full(2, np.nan)
+    rc = L.lib().mmvae_quantiser_stats(counts.ctypes.data, c32.ctypes.data, int(c32.size), lut.ctypes.data, ratios.ctypes.data,
+                                       ms.ctypes.data, ms.ctypes.data + 8)
+    return rc, lut, ratios, float(ms[0]), float(ms[1])
+
+
+def _last_error(L):
+    return (L.lib().mmvae_last_error() or b"").decode()
+
+
+def _inertia_of(counts, centres):
+    """sum_b counts[b] min_k (b/255 - c_k)^2 in f64"""
+    x = np.arange(256) / 255.0
+    d = (x[:, None] - np.asarray(centres, dtype=np.float64)[None, :]) ** 2
+    return float((counts.astype(np.float64) * d.min(axis=1)).sum())
+
+
+def _numpy_lut(centres):
+    x = np.arange(256).astype(np.float32) / np.float32(255.0)
+    return np.argmin((x[..., None] - np.asarray(centres, dtype=np.float32)) ** 2, axis=-1).astype(np.uint8)
+
+
+# ------------------------------------------------------------------------------------------------------------- golden fixtures
+def test_q2_fit_reproduces_sklearn_centres(L):
+    g = load_golden("kmeans_q2")
+    counts = _hist(g["frames"][:4])                       # the pixels scikit-learn was fitted on
+    rc, centres, inertia = _fit(L, counts, 2)
+    assert rc == OK, _last_error(L)
+    want = np.sort(g["centres"])
+    print("q2 centres", centres, "golden (sorted)", want, "max abs diff", np.abs(centres - want).max())
+    assert np.all(np.diff(centres) > 0)
+    assert np.abs(centres - want).max() <= 1e-9
+    assert abs(inertia - _inertia_of(counts, centres)) <= 1e-12 * inertia
+
+
+def test_q4_fit_is_no_worse_than_sklearn_and_a_lloyd_fixed_point(L):
+    g = load_golden("kmeans_q4")
+    counts = _hist(g["frames"][:4])
+    rc, centres, inertia = _fit(L, counts, 4)
+    assert rc == OK, _last_error(L)
+    sklearn_inertia = _inertia_of(counts, g["centres"])   # scikit-learn stopped in a local optimum on these pixels
+    print("q4 inertia", inertia, "sklearn", sklearn_inertia)
+    assert inertia <= sklearn_inertia * (1 + 1e-12)
+    assert abs(inertia - _inertia_of(counts, centres)) <= 1e-12 * inertia
+    assert np.all(np.diff(centres) > 0)
+    # Lloyd fixed point: every centre is the f64 weighted mean of the bins nearest to it
+    x = np.arange(256) / 255.0
+    nearest = np.argmin((x[:, None] - centres[None, :]) ** 2, axis=1)
+    w = counts.astype(np.float64)
+    for k in range(4):
+        sel = nearest == k
+        assert w[sel].sum() > 0
+        assert abs((w[sel] * x[sel]).sum() / w[sel].sum() - centres[k]) <= 1e-12
+
+
+# ----------------------------------------------------------------------------------------------------------------- brute force
+def _brute_force(values, weights, q):
+    """Every contiguous partition of the m points into q non-empty runs: (best inertia, centres of the best)."""
+    m = len(values)
+    x = values / 255.0
+    best = None
+    for cuts in itertools.combinations(range(1, m), q - 1):
+        edges = (0,) + cuts + (m,)
+        cost, cs = 0.0, []
+        for a, b in zip(edges[:-1], edges[1:]):
+            c = (weights[a:b] * x[a:b]).sum() / weights[a:b].sum()
+            cost += (weights[a:b] * (x[a:b] - c) ** 2).sum()
+            cs.append(c)
+        if best is None or cost < best[0]:
+            best = (cost, np.asarray(cs))
+    return best
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_fit_matches_enumeration_of_all_partitions(L, seed):
+    rng = np.random.default_rng(100 + seed)
+    m = int(rng.integers(5, 13))
+    values = np.sort(rng.choice(256, size=m, replace=False))
+    weights = rng.integers(1, 100000, size=m).astype(np.float64)        # generic: no two partitions tie
+    counts = np.zeros(256, dtype=np.uint64)
+    counts[values] = weights.astype(np.uint64)
+    for q in range(1, 5):
+        want_inertia, want_centres = _brute_force(values.astype(np.float64), weights, q)
+        rc, centres, inertia = _fit(L, counts, q)
+        assert rc == OK, _last_error(L)
+        # the same cuts: the centres are the means of the same runs
+        np.testing.assert_allclose(centres, want_centres, rtol=1e-12, atol=0)
+        assert abs(inertia - want_inertia) <= 1e-12 * want_inertia
+
+
+# ----------------------------------------------------------------------------------------------------------------------- edges
+def test_as_many_clusters_as_distinct_values(L):
+    counts = np.zeros(256, dtype=np.uint64)
+    values = [0, 7, 8, 130, 255]
+    counts[values] = [5, 1, 900, 33, 2]
+    rc, centres, inertia = _fit(L, counts, 5)
+    assert rc == OK, _last_error(L)
+    assert inertia == 0.0
+    np.testing.assert_allclose(centres, np.asarray(values) / 255.0, rtol=1e-15)
+
+
+def test_256_clusters_on_a_full_ramp(L):
+    rc, centres, inertia = _fit(L, np.ones(256, dtype=np.uint64), 256)
+    assert rc == OK, _last_error(L)
+    assert inertia == 0.0
+    np.testing.assert_allclose(centres, np.arange(256) / 255.0, rtol=1e-15)
+
+
+def test_large_counts_stay_exact(L):
+    counts = np.zeros(256, dtype=np.uint64)
+    n10, n200 = 3_000_000_001, 2_000_000_007
+    counts[10], counts[200] = n10, n200
+    rc, centres, inertia = _fit(L, counts, 1)
+    assert rc == OK, _last_error(L)
+    mean = Fraction(n10 * 10 + n200 * 200, n10 + n200)                 # exact rationals
+    want_inertia = (n10 * (10 - mean) ** 2 + n200 * (200 - mean) ** 2) / 255 ** 2
+    assert abs(centres[0] - float(mean / 255)) <= 4e-16 * float(mean / 255)
+    assert abs(inertia - float(want_inertia)) <= 1e-15 * float(want_inertia)
+    rc, centres, inertia = _fit(L, counts, 2)
+    assert rc == OK and inertia == 0.0
+    np.testing.assert_allclose(centres, [10 / 255.0, 200 / 255.0], rtol=1e-15)
+
+
+def test_fit_errors(L):
+    ramp = np.ones(256, dtype=np.uint64)
+    for q in (0, -3, 257):
+        rc, _, _ = _fit(L, ramp, q)
+        assert rc == ERR_ARG and str(q) in _last_error(L)
+    rc, _, _ = _fit(L, np.zeros(256, dtype=np.uint64), 2)
+    assert rc == ERR_ARG and "empty" in _last_error(L)
+    three = np.zeros(256, dtype=np.uint64)
+    three[[1, 2, 250]] = 9
+    rc, _, _ = _fit(L, three, 4)
+    assert rc == ERR_ARG and "3 distinct" in _last_error(L)
+    huge = np.zeros(256, dtype=np.uint64)
+    huge[[0, 255]] = 2 ** 48                                            # 2^49 pixels > 2^64 / 255^2 = 2^48.01
+    rc, _, _ = _fit(L, huge, 2)
+    assert rc == ERR_UNSUPPORTED and "overflow" in _last_error(L)
+    rc, _, _, _, _ = _stats(L, np.zeros(256, dtype=np.uint64), [0.1, 0.9])
+    assert rc == ERR_ARG and "empty" in _last_error(L)
+    assert L.lib().mmvae_quantiser_stats(ramp.ctypes.data, np.zeros(1, dtype=np.float32).ctypes.data, 0, ramp.ctypes.data, None, None,
+                                         None) == ERR_ARG
+
+
+# ----------------------------------------------------------------------------------------------------------------------- stats
+GRID_TIE_CENTRES = [0.0, 2 / 255.0, 4 / 255.0]       # bytes 1 and 3 sit midway between two centres: ties or near-ties in f32
+
+
+def test_lut_is_the_quantise_kernels_rule(L):
+    ramp = np.ones(256, dtype=np.uint64)
+    sets = [load_golden("kmeans_q2")["centres"], load_golden("kmeans_q4")["centres"], GRID_TIE_CENTRES]      # scikit-learn's order
+    for q in (2, 4):
+        rc, fitted, _ = _fit(L, _hist(load_golden(f"kmeans_q{q}")["frames"][:4]), q)
+        assert rc == OK
+        sets.append(fitted)
+    for centres in sets:
+        rc, lut, ratios, _, _ = _stats(L, ramp, centres)
+        assert rc == OK, _last_error(L)
+        assert np.array_equal(lut, _numpy_lut(centres)), centres
+        assert abs(ratios.sum() - 1.0) <= 1e-12
+
+
+@pytest.mark.parametrize("q", [2, 4])
+def test_label_statistics_match_the_fixture(L, q):
+    g = load_golden(f"kmeans_q{q}")
+    counts = _hist(g["frames"])                                         # all 5 frames, as the stored data_mean / data_std
+    rc, lut, ratios, mean, std = _stats(L, counts, g["centres"])        # scikit-learn's label order
+    assert rc == OK, _last_error(L)
+    assert np.array_equal(lut[g["frames"]], g["labels"])
+    print(f"q={q}: label mean {mean} (stored {float(g['data_mean'])}), std {std} (stored {float(g['data_std'])})")
+    assert abs(mean - float(g["data_mean"])) < 1e-4 and abs(std - float(g["data_std"])) < 1e-4
+    assert abs(ratios.sum() - 1.0) <= 1e-12
+    labels = g["labels"].astype(np.int64)
+    np.testing.assert_allclose(ratios, np.bincount(labels.ravel(), minlength=q) / labels.size, rtol=1e-12)
+    assert abs(mean - labels.mean()) <= 1e-12 and abs(std - labels.std()) <= 1e-12
+
+
+# -------------------------------------------------------------------------------------------------------------- python surface
+def test_python_fit_object_and_loader_without_centres(pkg):
+    main = importlib.import_module("moving-mnist-vae_amd.main")
+    g = load_golden("kmeans_q2")
+    fit = main._fit_counts(_hist(g["frames"][:4]), 2)
+    assert isinstance(fit, pkg.QuantiserFit)
+    assert fit.centres.dtype == np.float64 and np.abs(fit.centres - np.sort(g["centres"])).max() <= 1e-9
+    assert fit.counts.dtype == np.int64 and fit.counts.sum() == 4 * 64 * 64
+    assert np.array_equal(fit.lut, _numpy_lut(fit.centres))
+    w = fit.weights()
+    assert w.dtype.is_floating_point and w.shape == (2,)
+    np.testing.assert_allclose(w.numpy(), (1.0 - fit.ratios).astype(np.float32))
+    L = importlib.import_module("moving-mnist-vae_amd._lib")
+    with pytest.raises(L.MmvaeError, match="distinct"):
+        main._fit_counts(_hist(np.zeros(10)), 2)
+    # a loader built without centres is legal; iterating it before a fit is a clear error
+    loader = pkg.MovingMNISTClips(np.zeros((2, 3, 4, 4), dtype=np.uint8), None, 2, "cpu")
+    assert loader.centres is None and len(loader) == 1
+    with pytest.raises(RuntimeError, match="fit_quantiser"):
+        next(iter(loader))
