@@ -62,7 +62,7 @@ Bn Net::add_bn(const std::string& prefix, int C) {
   b.rv_off = n_bnbuf; add_entry(prefix + ".running_var", {C}, EK_BN_F32, n_bnbuf); n_bnbuf += C;
   b.nbt_idx = n_nbt; { Entry e; e.name = prefix + ".num_batches_tracked"; e.ndim = 0; e.kind = EK_BN_I64; e.offset = n_nbt;
                        for (int i = 0; i < 4; ++i) e.shape[i] = 1; entries.push_back(e); } n_nbt += 1;
-  b.ws = n_bnws; n_bnws += 7L * align_up(C, 4);
+  b.ws = n_bnws; n_bnws += b.scratch_floats();
   return b;
 }
 
@@ -225,54 +225,54 @@ const Plan& Net::plan(int N) {
   return plan_;
 }
 
-int Net::fill_consts(char* base, hipStream_t s) {
-  float* c = reinterpret_cast<float*>(base + plan_.cvec);
-  MM_TRY(launch_fill_f32(c, 1.f, 256, s));
-  return launch_fill_f32(c + 256, 0.f, 256, s);
+int Net::begin_pass(Pass& ps, int N, void* ws, size_t ws_bytes, const float* params, float* grads, float* bnbuf, long long* nbt, bool training) {
+  const Plan& P = plan(N);
+  if (ws_bytes < P.bytes) { set_error("workspace too small: %zu < %zu", ws_bytes, P.bytes); return MMVAE_ERR_WORKSPACE; }
+  ps.P = &P; ps.base = static_cast<char*>(ws); ps.params = params; ps.grads = grads; ps.bnbuf = bnbuf; ps.nbt = nbt; ps.N = N;
+  ps.training = training; ps.esz = esz();
+  ps.part = reinterpret_cast<float*>(ps.base + P.partials);
+  ps.wscratch = reinterpret_cast<float*>(ps.base + P.wscratch);
+  return MMVAE_OK;
 }
 
-float* Net::bnf(const Bn& bn, char* base, int which) const {
-  return reinterpret_cast<float*>(base + plan_.bnws) + bn.ws + (long)which * align_up(bn.C, 4);
+int Net::fill_consts(const Pass& ps, hipStream_t s) {
+  float* c = reinterpret_cast<float*>(ps.base + ps.P->cvec);
+  MM_TRY(launch_fill_f32(c, 1.f, 256, s));
+  return launch_fill_f32(c + 256, 0.f, 256, s);
 }
 
 // ------------------------------------------------------------------------------------------------ conv helpers
 static inline ConvGeom geom(const ConvW& w) { return ConvGeom{w.D0, w.D1, w.k, w.s, w.p}; }
 
-// fwd = 1: this pack feeds the conv's FORWARD direction (an fp8 layer then gets e4m3 bytes); every pack of an fp8 layer is scaled
-// the pack that feeds a conv's FORWARD direction (down for Conv2d, up for ConvTranspose2d) is e4m3 bytes on an fp8 layer; every pack
-// of an fp8 layer carries its weight scale
+// The pack that feeds a conv's FORWARD direction (down for Conv2d, up for ConvTranspose2d) is e4m3 bytes on an fp8 layer (fragment-major
+// when the fp8 form of the kernel takes the shape); every pack of an fp8 layer carries its weight scale.
 // The up form of a 1x1 stride-2 shortcut has stride phases without a tap: in this net it only ever accumulates into (or rides along
 // with) the main path's data gradient, so those phases are skipped.
-// (an fp8 layer's FORWARD pack is e4m3: fragment-major when the fp8 form of the kernel takes the shape)
 int Net::frag_down(const ConvW& w) const { return w.Hl > 0 ? op_deep2_down_ok(dt(), geom(w), w.Hl, w.Hl, (w.fp8 && !w.tr) ? 1 : 0) : 0; }
 int Net::frag_up(const ConvW& w) const { return w.Hl > 0 ? op_deep2_up_ok(dt(), geom(w), w.Hl, w.Hl, 1, (w.fp8 && w.tr) ? 1 : 0) : 0; }
-int Net::pack_down(const ConvW& w, const float* params, char* base, hipStream_t s) {
-  return op_pack_down(dt(), geom(w), params + w.off, base + plan_.packed + w.packD * (long)esz(), s, w.wscale, (w.fp8 && !w.tr) ? 1 : 0,
-                      frag_down(w));
+int Net::pack_down(const Pass& ps, const ConvW& w, hipStream_t s) {
+  return op_pack_down(dt(), geom(w), ps.params + w.off, ps.packed(w.packD), s, w.wscale, (w.fp8 && !w.tr) ? 1 : 0, frag_down(w));
 }
-int Net::pack_up(const ConvW& w, const float* params, char* base, hipStream_t s) {
-  return op_pack_up(dt(), geom(w), params + w.off, base + plan_.packed + w.packU * (long)esz(), s, w.wscale, (w.fp8 && w.tr) ? 1 : 0,
-                    frag_up(w));
+int Net::pack_up(const Pass& ps, const ConvW& w, hipStream_t s) {
+  return op_pack_up(dt(), geom(w), ps.params + w.off, ps.packed(w.packU), s, w.wscale, (w.fp8 && w.tr) ? 1 : 0, frag_up(w));
 }
-int Net::run_down(const ConvW& w, char* base, int N, const void* L, int Hl, int Wl, void* S, int Hs, int Ws,
+int Net::run_down(const Pass& ps, const ConvW& w, const void* L, int Hl, int Wl, void* S, int Hs, int Ws,
                   const float* pro_s, const float* pro_b, int relu, float* stats, int accumulate, int out_dt, hipStream_t s,
                   const ConvW* w2, const void* x2) {
   SecondSrc q;
-  if (w2) { q.x2 = x2; q.w2 = base + plan_.packed + w2->packU * (long)esz(); q.Cin2 = w2->D0; }
+  if (w2) { q.x2 = x2; q.w2 = ps.packed(w2->packU); q.Cin2 = w2->D0; }
   q.fp8 = (w.fp8 && !w.tr) ? 1 : 0;               // a Conv2d's forward
   q.wfrag = frag_down(w); q.wfrag2 = w2 ? frag_up(*w2) : 0;
-  return op_run_down(dt(), out_dt, geom(w), base + plan_.packed + w.packD * (long)esz(), N, L, Hl, Wl, S, Hs, Ws, pro_s, pro_b, relu,
-                     stats, accumulate, s, q);
+  return op_run_down(dt(), out_dt, geom(w), ps.packed(w.packD), ps.N, L, Hl, Wl, S, Hs, Ws, pro_s, pro_b, relu, stats, accumulate, s, q);
 }
-int Net::run_up(const ConvW& w, char* base, int N, const void* S, int Hs, int Ws, void* L, int Hl, int Wl,
+int Net::run_up(const Pass& ps, const ConvW& w, const void* S, int Hs, int Ws, void* L, int Hl, int Wl,
                 const float* pro_s, const float* pro_b, int relu, float* stats, int accumulate, hipStream_t s,
                 const ConvW* w2, const void* x2) {
   SecondSrc q;
-  if (w2) { q.x2 = x2; q.w2 = base + plan_.packed + w2->packU * (long)esz(); q.Cin2 = w2->D0; }
+  if (w2) { q.x2 = x2; q.w2 = ps.packed(w2->packU); q.Cin2 = w2->D0; }
   q.fp8 = (w.fp8 && w.tr) ? 1 : 0;                // a ConvTranspose2d's forward
   q.wfrag = frag_up(w); q.wfrag2 = w2 ? frag_up(*w2) : 0;
-  return op_run_up(dt(), geom(w), base + plan_.packed + w.packU * (long)esz(), N, S, Hs, Ws, L, Hl, Wl, pro_s, pro_b, relu, stats,
-                   accumulate, s, q);
+  return op_run_up(dt(), geom(w), ps.packed(w.packU), ps.N, S, Hs, Ws, L, Hl, Wl, pro_s, pro_b, relu, stats, accumulate, s, q);
 }
 hipStream_t Net::wgrad_stream(hipStream_t s) {
   if (side_state_ == 0) {
@@ -320,11 +320,20 @@ int Net::side_wait_mark(int slot, hipStream_t s) {
   return MMVAE_OK;
 }
 
-int Net::run_wgrad(const ConvW& w, int N, const void* P, int Hs, int Ws, const float* proP_s, const float* proP_b,
-                   const void* G, int Hl, int Wl, const float* proG_s, const float* proG_b, float* grads, hipStream_t s) {
+int Net::run_wgrad(const Pass& ps, const ConvW& w, const void* P, int Hs, int Ws, const float* proP_s, const float* proP_b,
+                   const void* G, int Hl, int Wl, const float* proG_s, const float* proG_b, hipStream_t s) {
   // (measured in round 3: a SECOND side stream with its own scratch, the weight gradients alternating between the two, is slower --
   // 7.74 vs 7.63 ms per step: the phases where the side stream lags are bandwidth-bound, two wgrad kernels at once only thrash)
-  return op_run_wgrad(dt(), geom(w), N, P, Hs, Ws, proP_s, proP_b, 1, G, Hl, Wl, proG_s, proG_b, 1, grads + w.off, s, wscratch_, w.wscale);
+  return op_run_wgrad(dt(), geom(w), ps.N, P, Hs, Ws, proP_s, proP_b, 1, G, Hl, Wl, proG_s, proG_b, 1, ps.grads + w.off, s, ps.wscratch,
+                      w.wscale);
+}
+
+int Net::reduce_wgrad_parts(const Pass& ps, const ConvW& w, const float* parts, int nparts, int ntaps, hipStream_t s) {
+  WgradReduceArgs u; std::memset(&u, 0, sizeof(u));
+  u.part = parts; u.dW = ps.grads + w.off; u.Ca = w.D0; u.Cb = w.D1; u.ntaps = ntaps; u.nparts = nparts;
+  u.Ca_valid = w.D0; u.Cb_valid = w.D1; u.sA = w.D1 * ntaps; u.sB = ntaps; u.scale = w.wscale;
+  for (int t = 0; t < ntaps; ++t) u.tap_off[t] = t;
+  return launch_wgrad_reduce(u, s);
 }
 
 // conv1 (3x3 s2) + 1x1 s2 shortcut weight gradients in one stream pass: encoder.layer1's shape (bf16, 32 -> 32 channels, 32x32 -> 16x16)
@@ -357,9 +366,9 @@ bool Net::tail_fwd_fused() const {
 
 // SyncBN: sum the partial rows locally, let the host's collective sum the row over the ranks (stream-ordered), and hand the
 // finalize kernels that one row.  Two operand slots: the caller's stream and the side stream may both have one in flight.
-int Net::sync_rows(char* base, const float* partials, int nparts, int width, hipStream_t s, float** out, int row_stride) {
+int Net::sync_rows(const Pass& ps, const float* partials, int nparts, int width, hipStream_t s, float** out, int row_stride) {
   if (width > 1024) { set_error("sync_bn: %d statistics per BatchNorm > 1024", width); return MMVAE_ERR_UNSUPPORTED; }
-  float* buf = reinterpret_cast<float*>(base + plan_.syncbuf) + (s == side_ ? 1024 : 0);
+  float* buf = reinterpret_cast<float*>(ps.base + ps.P->syncbuf) + (s == side_ ? 1024 : 0);
   MM_TRY(launch_partial_rowsum(partials, nparts, width, buf, s, row_stride));
   if (comm_) MM_TRY(comm_allreduce_sum((s == side_ && comm_side_) ? comm_side_ : comm_, buf, width, s));
   else if (ar_fn_(buf, width, s, ar_user_) != 0) { set_error("sync_bn: the all-reduce callback failed"); return MMVAE_ERR_ARG; }
@@ -367,30 +376,34 @@ int Net::sync_rows(char* base, const float* partials, int nparts, int width, hip
   return MMVAE_OK;
 }
 
-int Net::bn_train(const Bn& bn, const float* params, float* bnbuf, long long* nbt, char* base, int nparts, double count, hipStream_t s,
-                  long part_off, float in_scale) {
+int Net::bn_fwd(const Pass& ps, const Bn& bn, int nparts, double count, hipStream_t s, long part_off, float in_scale) {
+  if (!ps.training) {      // fold_bn_eval() has written every (scale, shift) pair of the entry point already
+    if (eval_folded_) return MMVAE_OK;
+    set_error("bn_eval: the entry point did not fold its BatchNorms"); return MMVAE_ERR_ARG;
+  }
   BnFinalizeArgs a;
   a.in_scale = in_scale;
-  a.partials = reinterpret_cast<const float*>(base + plan_.partials) + part_off; a.nparts = nparts; a.C = bn.C; a.count = count;
+  a.partials = ps.part + part_off; a.nparts = nparts; a.C = bn.C; a.count = count;
   if (sync_bn_on()) {      // statistics over the global batch (equal shards per rank)
     float* row = nullptr;
-    MM_TRY(sync_rows(base, a.partials, nparts, 2 * bn.C, s, &row));
+    MM_TRY(sync_rows(ps, a.partials, nparts, 2 * bn.C, s, &row));
     a.partials = row; a.nparts = 1; a.count = count * ar_world_;
   }
-  a.gamma = params + bn.g_off; a.beta = params + bn.b_off;
-  a.running_mean = bnbuf ? bnbuf + bn.rm_off : nullptr; a.running_var = bnbuf ? bnbuf + bn.rv_off : nullptr;
-  a.nbt = nbt ? nbt + bn.nbt_idx : nullptr;
-  a.mean = bnf(bn, base, 0); a.istd = bnf(bn, base, 1); a.scale = bnf(bn, base, 2); a.shift = bnf(bn, base, 3);
+  a.gamma = ps.params + bn.g_off; a.beta = ps.params + bn.b_off;
+  a.running_mean = ps.bnbuf ? ps.bnbuf + bn.rm_off : nullptr; a.running_var = ps.bnbuf ? ps.bnbuf + bn.rv_off : nullptr;
+  a.nbt = ps.nbt ? ps.nbt + bn.nbt_idx : nullptr;
+  const BnRows r = ps.rows(bn);
+  a.mean = r.mean; a.istd = r.istd; a.scale = r.scale; a.shift = r.shift;
   a.momentum = 0.1f; a.eps = 1e-5f;
   return launch_bn_finalize(a, s);
 }
 
-int Net::fold_bn_eval(int which, const float* params, const float* bnbuf, char* base, hipStream_t s) {
+int Net::fold_bn_eval(const Pass& ps, int which, hipStream_t s) {
   std::vector<BnFoldEntry> tab;
   auto add = [&](const Bn& bn, float in_scale) {
     BnFoldEntry e;
     e.g_off = (int)bn.g_off; e.b_off = (int)bn.b_off; e.rm_off = (int)bn.rm_off; e.rv_off = (int)bn.rv_off;
-    e.scale_off = (int)(bn.ws + 2L * align_up(bn.C, 4)); e.shift_off = (int)(bn.ws + 3L * align_up(bn.C, 4)); e.C = bn.C; e.in_scale = in_scale;
+    e.scale_off = (int)bn.row(Bn::SCALE); e.shift_off = (int)bn.row(Bn::SHIFT); e.C = bn.C; e.in_scale = in_scale;
     tab.push_back(e);
   };
   if (which == 0) add(bn0, 1.f); else add(dbn0, dstem.wscale);
@@ -399,106 +412,94 @@ int Net::fold_bn_eval(int which, const float* params, const float* bnbuf, char* 
     if (!B.identity) add(B.bs, B.cs.wscale);
   }
   if (which == 1) add(bn_out, 1.f);
-  MM_TRY(launch_bn_fold_eval(tab.data(), (int)tab.size(), params, bnbuf, reinterpret_cast<float*>(base + plan_.bnws), 1e-5f, s));
+  MM_TRY(launch_bn_fold_eval(tab.data(), (int)tab.size(), ps.params, ps.bnbuf, reinterpret_cast<float*>(ps.base + ps.P->bnws), 1e-5f, s));
   eval_folded_ = true;
   return MMVAE_OK;
 }
 
-// eval mode: fold_bn_eval() has written every (scale, shift) pair of the entry point already
-int Net::bn_eval(const Bn&, const float*, const float*, char*, hipStream_t, float) {
-  if (eval_folded_) return MMVAE_OK;
-  set_error("bn_eval: the entry point did not fold its BatchNorms"); return MMVAE_ERR_ARG;
-}
-
-BnBwdFinalizeArgs Net::bwd_finalize_args(const Bn& bn, const float* params, float* grads, char* base, const float* partials, int nparts, int ny,
-                                         int which, double count) const {
-  const Net& net = *this;
+BnBwdFinalizeArgs Net::bwd_finalize_args(const Pass& ps, const Bn& bn, const float* partials, int nparts, int ny, int which,
+                                         double count) const {
+  const BnRows r = ps.rows(bn);
   BnBwdFinalizeArgs a;
   a.partials = partials; a.nparts = nparts; a.C = bn.C; a.which = which; a.ny = ny;
-  a.count = count; a.gamma = params + bn.g_off; a.mean = net.bnf(bn, base, 0); a.istd = net.bnf(bn, base, 1);
-  a.dgamma = grads + bn.g_off; a.dbeta = grads + bn.b_off;
-  a.coefA = net.bnf(bn, base, 4); a.coefB = net.bnf(bn, base, 5); a.coefC = net.bnf(bn, base, 6);
+  a.count = count; a.gamma = ps.params + bn.g_off; a.mean = r.mean; a.istd = r.istd;
+  a.dgamma = ps.grads + bn.g_off; a.dbeta = ps.grads + bn.b_off;
+  a.coefA = r.A; a.coefB = r.B; a.coefC = r.C;
   return a;
 }
 // SyncBN backward: dgamma / dbeta stay the rank's own sums (the gradient all-reduce adds the ranks up), the coefficients of
 // dx = A*g + B*y + C use the sums over the global batch -- so the local finalize runs first and a second one, fed with the
 // all-reduced row, overwrites the coefficients.
-int Net::bn_backward_coefs(const Bn& bn, const float* params, float* grads, char* base, int nparts, int ny, int which, double count,
-                           hipStream_t s, float* dbias_conv) {
-  const float* part = reinterpret_cast<const float*>(base + plan_.partials);
-  BnBwdFinalizeArgs l = bwd_finalize_args(bn, params, grads, base, part, nparts, ny, which, count);
+int Net::bn_backward_coefs(const Pass& ps, const Bn& bn, int nparts, int ny, int which, double count, hipStream_t s, float* dbias_conv) {
+  BnBwdFinalizeArgs l = bwd_finalize_args(ps, bn, ps.part, nparts, ny, which, count);
   if (!sync_bn_on()) l.dbias_conv = dbias_conv;
   MM_TRY(launch_bn_bwd_finalize(l, s));
   if (!sync_bn_on()) return MMVAE_OK;
   float* row = nullptr;
-  MM_TRY(sync_rows(base, part, nparts, (1 + ny) * bn.C, s, &row));
-  BnBwdFinalizeArgs g = bwd_finalize_args(bn, params, grads, base, row, 1, ny, which, count * ar_world_);
+  MM_TRY(sync_rows(ps, ps.part, nparts, (1 + ny) * bn.C, s, &row));
+  BnBwdFinalizeArgs g = bwd_finalize_args(ps, bn, row, 1, ny, which, count * ar_world_);
   g.dgamma = nullptr; g.dbeta = nullptr;
   // the gradient all-reduce sums the ranks: every rank contributes 1/world of the global closed form
   g.dbias_conv = dbias_conv; g.dbias_scale = 1.f / (float)ar_world_;
   return launch_bn_bwd_finalize(g, s);
 }
 // the two BatchNorms of a residual join (partials rows: sum g, sum g*y2, sum g*ys) in one launch
-int Net::bn_backward_coefs_join(const Bn& b2, const Bn& bs, const float* params, float* grads, char* base, int nparts, double count,
-                                hipStream_t s) {
-  const float* part = reinterpret_cast<const float*>(base + plan_.partials);
-  MM_TRY(launch_bn_bwd_finalize2(bwd_finalize_args(b2, params, grads, base, part, nparts, 2, 0, count),
-                                 bwd_finalize_args(bs, params, grads, base, part, nparts, 2, 1, count), s));
+int Net::bn_backward_coefs_join(const Pass& ps, const Bn& b2, const Bn& bs, int nparts, double count, hipStream_t s) {
+  MM_TRY(launch_bn_bwd_finalize2(bwd_finalize_args(ps, b2, ps.part, nparts, 2, 0, count),
+                                 bwd_finalize_args(ps, bs, ps.part, nparts, 2, 1, count), s));
   if (!sync_bn_on()) return MMVAE_OK;
   float* row = nullptr;
-  MM_TRY(sync_rows(base, part, nparts, 3 * b2.C, s, &row));
-  BnBwdFinalizeArgs g2 = bwd_finalize_args(b2, params, grads, base, row, 1, 2, 0, count * ar_world_);
-  BnBwdFinalizeArgs gs = bwd_finalize_args(bs, params, grads, base, row, 1, 2, 1, count * ar_world_);
+  MM_TRY(sync_rows(ps, ps.part, nparts, 3 * b2.C, s, &row));
+  BnBwdFinalizeArgs g2 = bwd_finalize_args(ps, b2, row, 1, 2, 0, count * ar_world_);
+  BnBwdFinalizeArgs gs = bwd_finalize_args(ps, bs, row, 1, 2, 1, count * ar_world_);
   g2.dgamma = g2.dbeta = gs.dgamma = gs.dbeta = nullptr;
   return launch_bn_bwd_finalize2(g2, gs, s);
 }
 
 // ------------------------------------------------------------------------------------------------ weight re-packs per entry point
 // (recorded by launch_pack() while a batch is open; see pack_batch_begin/flush)
-int Net::packs_enc_fwd(const float* params, char* base, hipStream_t s) {
-  const Plan& P = plan_;
+int Net::packs_enc_fwd(const Pass& ps, hipStream_t s) {
   {
     const int cpad = dt() == DT_F32 ? 4 : 8;
     PackArgs pa; std::memset(&pa, 0, sizeof(pa));
-    pa.src = params + stem.off; pa.dst = base + P.packed + stem_pack * (long)esz();
+    pa.src = ps.params + stem.off; pa.dst = ps.packed(stem_pack);
     pa.cols = 32; pa.K = cpad; pa.K_valid = cfg.in_ch; pa.ntaps = 25; pa.s_col = 25 * cfg.in_ch; pa.s_k = 25; pa.scale = 1.f;
     for (int t = 0; t < 25; ++t) pa.tap_off[t] = t;
     MM_TRY(launch_pack(dt(), pa, s));
   }
   for (const Block& B : enc) {
-    MM_TRY(pack_down(B.c1, params, base, s));
-    MM_TRY(pack_down(B.c2, params, base, s));
-    if (!B.identity) MM_TRY(pack_down(B.cs, params, base, s));
+    MM_TRY(pack_down(ps, B.c1, s));
+    MM_TRY(pack_down(ps, B.c2, s));
+    if (!B.identity) MM_TRY(pack_down(ps, B.cs, s));
   }
   const int nt = Hf * Wf;
   for (int h = 0; h < (cfg.need_logvar ? 2 : 1); ++h) {
     const ConvW& hw = h == 0 ? head_mu : head_lv;
     const long poff = h == 0 ? head_pack_mu : head_pack_lv;
     PackArgs pa; std::memset(&pa, 0, sizeof(pa));
-    pa.src = params + hw.off; pa.dst = base + P.packed + poff * (long)esz();
+    pa.src = ps.params + hw.off; pa.dst = ps.packed(poff);
     pa.cols = cfg.z; pa.K = 256; pa.ntaps = nt; pa.s_col = 256; pa.s_k = 1; pa.scale = 1.0f / nt;
     MM_TRY(launch_pack(dt(), pa, s));
   }
   return MMVAE_OK;
 }
 
-int Net::packs_enc_bwd(const float* params, char* base, hipStream_t s) {
-  const Plan& P = plan_;
+int Net::packs_enc_bwd(const Pass& ps, hipStream_t s) {
   const int Ch = cfg.need_logvar ? 2 * cfg.z : cfg.z;
   PackArgs pa; std::memset(&pa, 0, sizeof(pa));
-  pa.src = params + head_mu.off; pa.dst = base + P.packed + head_pack_dg * (long)esz();
+  pa.src = ps.params + head_mu.off; pa.dst = ps.packed(head_pack_dg);
   pa.cols = 256; pa.K = Ch; pa.ntaps = 1; pa.s_col = 1; pa.s_k = 256; pa.scale = 1.0f / (Hf * Wf);
   MM_TRY(launch_pack(dt(), pa, s));
   for (const Block& B : enc) {
-    MM_TRY(pack_up(B.c2, params, base, s));
-    MM_TRY(pack_up(B.c1, params, base, s));
-    if (!B.identity) MM_TRY(pack_up(B.cs, params, base, s));
+    MM_TRY(pack_up(ps, B.c2, s));
+    MM_TRY(pack_up(ps, B.c1, s));
+    if (!B.identity) MM_TRY(pack_up(ps, B.cs, s));
   }
   if (l1_dgrad_stream()) {
     // dx[n,h,w,ci] = sum_{kh,kw,co} dy[n, h+1-kh, w+1-kw, co] W[co][ci][kh][kw]: a forward 3x3 conv over dy with weights [ci][tap' = 8 - tap][co]
     const ConvW& w = enc[0].c2;
     PackArgs pf; std::memset(&pf, 0, sizeof(pf));
-    pf.src = params + w.off; pf.dst = base + P.packed + l1c2_flip * (long)esz();
+    pf.src = ps.params + w.off; pf.dst = ps.packed(l1c2_flip);
     pf.cols = 32; pf.K = 32; pf.ntaps = 9; pf.s_col = 9; pf.s_k = 32 * 9; pf.scale = w.wscale;
     for (int t = 0; t < 9; ++t) pf.tap_off[t] = 8 - t;
     MM_TRY(launch_pack(dt(), pf, s));
@@ -506,90 +507,86 @@ int Net::packs_enc_bwd(const float* params, char* base, hipStream_t s) {
   return MMVAE_OK;
 }
 
-int Net::packs_dec_fwd(const float* params, char* base, hipStream_t s) {
-  const Plan& P = plan_;
-  MM_TRY(pack_up(dstem, params, base, s));
+int Net::packs_dec_fwd(const Pass& ps, hipStream_t s) {
+  MM_TRY(pack_up(ps, dstem, s));
   for (const Block& B : dec) {
-    MM_TRY(pack_down(B.c1, params, base, s));
-    if (B.identity) MM_TRY(pack_down(B.c2, params, base, s));       // 3x3 Conv2d
-    else { MM_TRY(pack_up(B.c2, params, base, s)); MM_TRY(pack_up(B.cs, params, base, s)); }
+    MM_TRY(pack_down(ps, B.c1, s));
+    if (B.identity) MM_TRY(pack_down(ps, B.c2, s));       // 3x3 Conv2d
+    else { MM_TRY(pack_up(ps, B.c2, s)); MM_TRY(pack_up(ps, B.cs, s)); }
   }
   PackArgs pa; std::memset(&pa, 0, sizeof(pa));
-  pa.src = params + tail.off; pa.dst = base + P.packed + tail_pack_f * (long)esz();
+  pa.src = ps.params + tail.off; pa.dst = ps.packed(tail_pack_f);
   pa.cols = 16; pa.cols_valid = cfg.out_ch; pa.K = 16; pa.ntaps = 9; pa.s_col = 144; pa.s_k = 9; pa.scale = 1.f;
   for (int t = 0; t < 9; ++t) pa.tap_off[t] = t;
   MM_TRY(launch_pack(dt(), pa, s));
   return MMVAE_OK;
 }
 
-int Net::packs_dec_bwd(const float* params, char* base, bool need_denc, hipStream_t s) {
-  const Plan& P = plan_;
+int Net::packs_dec_bwd(const Pass& ps, bool need_denc, hipStream_t s) {
   PackArgs pa; std::memset(&pa, 0, sizeof(pa));
-  pa.src = params + tail.off; pa.dst = base + P.packed + tail_pack_d * (long)esz();
+  pa.src = ps.params + tail.off; pa.dst = ps.packed(tail_pack_d);
   pa.cols = 16; pa.K = 8; pa.K_valid = cfg.out_ch; pa.ntaps = 9; pa.s_col = 9; pa.s_k = 144; pa.scale = 1.f;
   for (int t = 0; t < 9; ++t) pa.tap_off[t] = t;
   MM_TRY(launch_pack(dt(), pa, s));
   for (const Block& B : dec) {
-    MM_TRY(pack_up(B.c1, params, base, s));
-    if (B.identity) MM_TRY(pack_up(B.c2, params, base, s));
-    else { MM_TRY(pack_down(B.c2, params, base, s)); MM_TRY(pack_down(B.cs, params, base, s)); }
+    MM_TRY(pack_up(ps, B.c1, s));
+    if (B.identity) MM_TRY(pack_up(ps, B.c2, s));
+    else { MM_TRY(pack_down(ps, B.c2, s)); MM_TRY(pack_down(ps, B.cs, s)); }
   }
-  if (need_denc) MM_TRY(pack_down(dstem, params, base, s));
+  if (need_denc) MM_TRY(pack_down(ps, dstem, s));
   return MMVAE_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ encoder
 int Net::stage_labels(int N, const void* labels, int label_bytes, float mean, float stdv, float* image, void* ws, size_t ws_bytes, hipStream_t s) {
-  const Plan& P = plan(N);
-  if (ws_bytes < P.bytes) { set_error("workspace too small: %zu < %zu", ws_bytes, P.bytes); return MMVAE_ERR_WORKSPACE; }
-  return launch_normalise(dt(), labels, label_bytes, (long)N * cfg.in_ch * cfg.S * cfg.S, mean, stdv, static_cast<char*>(ws) + P.x_t, image, s);
+  Pass ps;
+  MM_TRY(begin_pass(ps, N, ws, ws_bytes));
+  return launch_normalise(dt(), labels, label_bytes, (long)N * cfg.in_ch * cfg.S * cfg.S, mean, stdv, ps.base + ps.P->x_t, image, s);
 }
 
 int Net::encoder_fwd(int N, const float* x, const float* params, float* bnbuf, long long* nbt, void* ws, size_t ws_bytes,
                      float* mu, float* logvar, int training, hipStream_t s, bool staged) {
   if (Hf > 2) { set_error("encoder: image size %d unsupported (final map %dx%d)", cfg.S, Hf, Wf); return MMVAE_ERR_UNSUPPORTED; }
-  const Plan& P = plan(N);
-  if (ws_bytes < P.bytes) { set_error("workspace too small: %zu < %zu", ws_bytes, P.bytes); return MMVAE_ERR_WORKSPACE; }
-  char* base = static_cast<char*>(ws);
-  float* part = reinterpret_cast<float*>(base + P.partials);
+  Pass ps;
+  MM_TRY(begin_pass(ps, N, ws, ws_bytes, params, nullptr, bnbuf, nbt, training != 0));
+  const Plan& P = *ps.P;
+  char* const base = ps.base;
+  float* const part = ps.part;
   float* stats = training ? part : nullptr;
   const int S = cfg.S;
   pack_batch_begin();                       // every weight re-pack of this entry point in ONE launch
-  MM_TRY(packs_enc_fwd(params, base, s));
+  MM_TRY(packs_enc_fwd(ps, s));
   MM_TRY(pack_batch_flush(dt(), s));
   eval_folded_ = false;
   gram_ready_ = false; gram_fwd_N_ = training ? N : 0; gram_fwd_ws_ = ws;
-  if (!training) MM_TRY(fold_bn_eval(0, params, bnbuf, base, s));
+  if (!training) MM_TRY(fold_bn_eval(ps, 0, s));
   if (!staged) MM_TRY(launch_convert(DT_F32, dt(), x, base + P.x_t, (long)N * cfg.in_ch * S * S, s));
+  int np;
   if (cfg.in_ch == 1 && stem_fwd_stream_ok(dt(), S)) {
-    const int np = launch_stem_fwd_stream(dt(), base + P.x_t, params + stem.off, base + P.y0, stats, N, S, s);
-    MM_TRY(np);
-    if (training) MM_TRY(bn_train(bn0, params, bnbuf, nbt, base, np, (double)N * H1 * W1, s));
+    np = launch_stem_fwd_stream(dt(), base + P.x_t, params + stem.off, base + P.y0, stats, N, S, s);
   } else {
     // stem Conv2d(in_channels -> 32, k5 s2 p2) (model.py:94): the planar image (in_channels <= 4 planes) is staged as a zero-padded
     // VE-channel NHWC patch in LDS and runs through the MFMA patch-tile kernel; BatchNorm statistics come out of its epilogue.
     const int cpad = dt() == DT_F32 ? 4 : 8;
     GatherArgs a; std::memset(&a, 0, sizeof(a));
-    a.x = base + P.x_t; a.w = base + P.packed + stem_pack * (long)esz(); a.y = base + P.y0; a.stats = stats;
+    a.x = base + P.x_t; a.w = ps.packed(stem_pack); a.y = base + P.y0; a.stats = stats;
     a.x_planar = 2; a.x_planes = cfg.in_ch;
     a.N = N; a.Hi = S; a.Wi = S; a.Cin = cpad; a.Ho = H1; a.Wo = W1; a.Cout = 32; a.SI = 2; a.SO = 1;
     a.nphase = 1; a.phases[0] = Phase{0, 0, H1, W1, 25, 0, 0};
     for (int kh = 0; kh < 5; ++kh) for (int kw = 0; kw < 5; ++kw) a.taps[kh * 5 + kw] = Tap{kh - 2, kw - 2};
-    const int np = launch_gather_gemm(dt(), dt(), a, s);
-    MM_TRY(np);
-    if (training) MM_TRY(bn_train(bn0, params, bnbuf, nbt, base, np, (double)N * H1 * W1, s));
+    np = launch_gather_gemm(dt(), dt(), a, s);
   }
-  if (training) {
-  } else {
-    MM_TRY(bn_eval(bn0, params, bnbuf, base, s));
-  }
+  MM_TRY(np);
+  MM_TRY(bn_fwd(ps, bn0, np, (double)N * H1 * W1, s));
   const void* xin = base + P.y0;
-  const float* xs = bnf(bn0, base, 2);
-  const float* xb = bnf(bn0, base, 3);
-  if (cfg.blocks > 1) MM_TRY(fill_consts(base, s));
+  const float* xs = ps.rows(bn0).scale;
+  const float* xb = ps.rows(bn0).shift;
+  if (cfg.blocks > 1) MM_TRY(fill_consts(ps, s));
   for (size_t i = 0; i < enc.size(); ++i) {
     Block& B = enc[i];
     const double cnt = (double)N * B.Hout * B.Wout;
+    const BnRows r1 = ps.rows(B.b1), r2 = ps.rows(B.b2);
+    const Shortcut sc = ps.shortcut(B, xin);
     // shortcut branch (conv + its BatchNorm) on the side stream, concurrently with conv1 -> bn1 -> conv2 -> bn2
     // encoder.layer1 (32 -> 32 channels, bf16): conv1 AND the 1x1 shortcut from ONE read of the block input, conv2 likewise a per-wave
     // stream (conv_fstream.hip); both BatchNorms finalise on the caller's stream
@@ -597,50 +594,41 @@ int Net::encoder_fwd(int N, const float* x, const float* params, float* bnbuf, l
                          conv3_stream_ok(dt(), B.Cin, B.C, B.c1.k, B.c1.s, B.c1.p, B.Hin, B.Win);
     const bool stream2 = !B.c2.fp8 && conv3_stream_ok(dt(), B.C, B.C, B.c2.k, B.c2.s, B.c2.p, B.Hout, B.Wout);
     const bool fork = !B.identity && !stream1;
-    int np;
     if (stream1) {
-      np = launch_conv3_stream(dt(), 2, xin, base + plan_.packed + B.c1.packD * (long)esz(), base + plan_.packed + B.cs.packD * (long)esz(), base + B.y1,
+      np = launch_conv3_stream(dt(), 2, xin, ps.packed(B.c1.packD), ps.packed(B.cs.packD), base + B.y1,
                                base + B.ys, xs, xb, 1, stats, stats ? stats + kPartialFloats : nullptr, N, B.Hout, s);
       MM_TRY(np);
-      MM_TRY(training ? bn_train(B.bs, params, bnbuf, nbt, base, np, cnt, s, kPartialFloats, B.cs.wscale) : bn_eval(B.bs, params, bnbuf, base, s, B.cs.wscale));
-      MM_TRY(training ? bn_train(B.b1, params, bnbuf, nbt, base, np, cnt, s, 0, B.c1.wscale) : bn_eval(B.b1, params, bnbuf, base, s, B.c1.wscale));
+      MM_TRY(bn_fwd(ps, B.bs, np, cnt, s, kPartialFloats, B.cs.wscale));
+      MM_TRY(bn_fwd(ps, B.b1, np, cnt, s, 0, B.c1.wscale));
     } else if (!B.identity) {
       if (fork) MM_TRY(side_fork(s));
       hipStream_t ss = fork ? wgrad_stream(s) : s;
-      np = run_down(B.cs, base, N, xin, B.Hin, B.Win, base + B.ys, B.Hout, B.Wout, xs, xb, 1, stats ? stats + kPartialFloats : nullptr, 0, dt(), ss);
+      np = run_down(ps, B.cs, xin, B.Hin, B.Win, base + B.ys, B.Hout, B.Wout, xs, xb, 1, stats ? stats + kPartialFloats : nullptr, 0, dt(), ss);
       MM_TRY(np);
-      MM_TRY(training ? bn_train(B.bs, params, bnbuf, nbt, base, np, cnt, ss, kPartialFloats, B.cs.wscale) : bn_eval(B.bs, params, bnbuf, base, ss, B.cs.wscale));
+      MM_TRY(bn_fwd(ps, B.bs, np, cnt, ss, kPartialFloats, B.cs.wscale));
     }
     if (!stream1) {
-      np = run_down(B.c1, base, N, xin, B.Hin, B.Win, base + B.y1, B.Hout, B.Wout, xs, xb, 1, stats, 0, dt(), s);
+      np = run_down(ps, B.c1, xin, B.Hin, B.Win, base + B.y1, B.Hout, B.Wout, xs, xb, 1, stats, 0, dt(), s);
       MM_TRY(np);
-      MM_TRY(training ? bn_train(B.b1, params, bnbuf, nbt, base, np, cnt, s, 0, B.c1.wscale) : bn_eval(B.b1, params, bnbuf, base, s, B.c1.wscale));
+      MM_TRY(bn_fwd(ps, B.b1, np, cnt, s, 0, B.c1.wscale));
     }
     if (stream2)
-      np = launch_conv3_stream(dt(), 1, base + B.y1, base + plan_.packed + B.c2.packD * (long)esz(), nullptr, base + B.y2, nullptr, bnf(B.b1, base, 2),
-                               bnf(B.b1, base, 3), 1, stats, nullptr, N, B.Hout, s);
+      np = launch_conv3_stream(dt(), 1, base + B.y1, ps.packed(B.c2.packD), nullptr, base + B.y2, nullptr, r1.scale, r1.shift, 1, stats,
+                               nullptr, N, B.Hout, s);
     else
-      np = run_down(B.c2, base, N, base + B.y1, B.Hout, B.Wout, base + B.y2, B.Hout, B.Wout, bnf(B.b1, base, 2), bnf(B.b1, base, 3), 1,
-                    stats, 0, dt(), s);
+      np = run_down(ps, B.c2, base + B.y1, B.Hout, B.Wout, base + B.y2, B.Hout, B.Wout, r1.scale, r1.shift, 1, stats, 0, dt(), s);
     MM_TRY(np);
-    MM_TRY(training ? bn_train(B.b2, params, bnbuf, nbt, base, np, cnt, s, 0, B.c2.wscale) : bn_eval(B.b2, params, bnbuf, base, s, B.c2.wscale));
+    MM_TRY(bn_fwd(ps, B.b2, np, cnt, s, 0, B.c2.wscale));
     if (fork) MM_TRY(side_join(s));
-    // identity shortcut (model.py:40,52): the block input itself, i.e. a unit "BatchNorm" (scale 1, shift 0) of it
-    MM_TRY(launch_join_fwd(dt(), base + B.y2, bnf(B.b2, base, 2), bnf(B.b2, base, 3), B.identity ? xin : base + B.ys,
-                           B.identity ? ones(base) : bnf(B.bs, base, 2), B.identity ? zeros(base) : bnf(B.bs, base, 3), base + B.out,
+    MM_TRY(launch_join_fwd(dt(), base + B.y2, r2.scale, r2.shift, sc.y, sc.scale, sc.shift, base + B.out,
                            (long)N * B.Hout * B.Wout, B.C, s));
     xin = base + B.out; xs = xb = nullptr;
   }
   // global average pool + the two 1x1 heads (model.py:123-128) as ONE k=Hf,s=Hf conv whose taps share W/(Hf*Wf)
   const int nt = Hf * Wf;
   for (int h = 0; h < (cfg.need_logvar ? 2 : 1); ++h) {
-    const ConvW& hw = h == 0 ? head_mu : head_lv;
-    const long poff = h == 0 ? head_pack_mu : head_pack_lv;
-    PackArgs pa; std::memset(&pa, 0, sizeof(pa));
-    pa.src = params + hw.off; pa.dst = base + P.packed + poff * (long)esz();
-    pa.cols = cfg.z; pa.K = 256; pa.ntaps = nt; pa.s_col = 256; pa.s_k = 1; pa.scale = 1.0f / nt;
     GatherArgs a; std::memset(&a, 0, sizeof(a));
-    a.x = xin; a.w = base + P.packed + poff * (long)esz(); a.y = h == 0 ? mu : logvar;
+    a.x = xin; a.w = ps.packed(h == 0 ? head_pack_mu : head_pack_lv); a.y = h == 0 ? mu : logvar;
     a.N = N; a.Hi = Hf; a.Wi = Wf; a.Cin = 256; a.Ho = 1; a.Wo = 1; a.Cout = cfg.z; a.SI = Hf; a.SO = 1;
     a.nphase = 1; a.phases[0] = Phase{0, 0, 1, 1, nt, 0, 0};
     for (int kh = 0; kh < Hf; ++kh) for (int kw = 0; kw < Wf; ++kw) a.taps[kh * Wf + kw] = Tap{kh, kw};
@@ -651,15 +639,16 @@ int Net::encoder_fwd(int N, const float* x, const float* params, float* bnbuf, l
 
 int Net::encoder_bwd(int N, const float* d_mu, const float* d_logvar, const float* params, float* grads, void* ws, size_t ws_bytes,
                      hipStream_t s) {
-  const Plan& P = plan(N);
-  if (ws_bytes < P.bytes) { set_error("workspace too small"); return MMVAE_ERR_WORKSPACE; }
-  char* base = static_cast<char*>(ws);
-  wscratch_ = reinterpret_cast<float*>(base + P.wscratch);
-  float* part = reinterpret_cast<float*>(base + P.partials);
+  Pass ps;
+  MM_TRY(begin_pass(ps, N, ws, ws_bytes, params, grads));
+  const Plan& P = *ps.P;
+  char* const base = ps.base;
+  float* const part = ps.part;
+  const BnRows r0 = ps.rows(bn0);
   const int Ch = cfg.need_logvar ? 2 * cfg.z : cfg.z;
   const int nt = Hf * Wf;
   pack_batch_begin();
-  MM_TRY(packs_enc_bwd(params, base, s));
+  MM_TRY(packs_enc_bwd(ps, s));
   MM_TRY(pack_batch_flush(dt(), s));
   // ---- heads: dh = [d_mu | d_logvar] in T
   MM_TRY(launch_concat2_to_t(dt(), d_mu, cfg.need_logvar ? d_logvar : nullptr, N, cfg.z, cfg.need_logvar ? cfg.z : 0, base + P.dh, s));
@@ -668,10 +657,9 @@ int Net::encoder_bwd(int N, const float* d_mu, const float* d_logvar, const floa
     a.P = base + P.dh; a.G = base + enc.back().out; a.dW = grads + head_mu.off; a.proP_relu = a.proG_relu = 0;
     a.N = N; a.Hp = 1; a.Wp = 1; a.Ca = Ch; a.Hg = Hf; a.Wg = Wf; a.Cb = 256; a.Cb_valid = 256;
     a.stride = Hf; a.pad = 0; a.ksz = Hf; a.sA = 256; a.sB = 1; a.ntaps = nt; a.scale = 1.0f / nt;
-    a.scratch = wscratch_;
+    a.scratch = ps.wscratch;
     MM_TRY(side_fork(s));
     MM_TRY(launch_wgrad(dt(), a, wgrad_stream(s)));
-    // the stem's im2col depends on the input image only: early, off the tail of the critical path
     // the stem's input-only work (patch gram matrix / im2col) early, off the tail of the critical path
     if (stem_bwd_fused() && !(gram_ready_ && gram_fwd_N_ == N && gram_fwd_ws_ == ws)) {
       MM_TRY(launch_stem_gram(dt(), base + P.x_t, reinterpret_cast<float*>(base + P.stem_gram), 1024L * stem_bwd_part_floats(),
@@ -681,25 +669,25 @@ int Net::encoder_bwd(int N, const float* d_mu, const float* d_logvar, const floa
     }
     gram_ready_ = false;            // (consumed: the next backward pass belongs to another forward pass)
     if (!stem_bwd_fused() && cfg.in_ch == 1 && wgrad_stream(s) != s) MM_TRY(launch_stem_im2col(dt(), base + P.x_t, base + P.col, N, cfg.S, cfg.S, H1, W1, wgrad_stream(s)));
-    PackArgs pa; std::memset(&pa, 0, sizeof(pa));
-    pa.src = params + head_mu.off; pa.dst = base + P.packed + head_pack_dg * (long)esz();
-    pa.cols = 256; pa.K = Ch; pa.ntaps = 1; pa.s_col = 1; pa.s_k = 256; pa.scale = 1.0f / nt;
     GatherArgs g; std::memset(&g, 0, sizeof(g));
-    g.x = base + P.dh; g.w = pa.dst; g.y = base + P.g[0];
+    g.x = base + P.dh; g.w = ps.packed(head_pack_dg); g.y = base + P.g[0];
     g.N = N; g.Hi = 1; g.Wi = 1; g.Cin = Ch; g.Ho = Hf; g.Wo = Wf; g.Cout = 256; g.SI = 1; g.SO = Hf;
     g.nphase = nt;
     for (int i = 0; i < nt; ++i) { g.phases[i] = Phase{i / Wf, i % Wf, 1, 1, 1, i, 0}; g.taps[i] = Tap{0, 0}; }
     MM_TRY(launch_gather_gemm(dt(), dt(), g, s));
   }
   int cur = 0;   // d_out lives in g[cur]
+  long stem_dy1 = 0, stem_dys = 0;   // workspace offsets of layer1's dy1 / dys, for the stem's fused backward
   const int ne = (int)enc.size();
   for (int i = ne - 1; i >= 0; --i) {
     Block& B = enc[i];
     const long npix = (long)N * B.Hout * B.Wout;
     const double cnt = (double)npix;
     const void* xin = i == 0 ? base + P.y0 : base + enc[i - 1].out;
-    const float* xs = i == 0 ? bnf(bn0, base, 2) : nullptr;
-    const float* xb = i == 0 ? bnf(bn0, base, 3) : nullptr;
+    const float* xs = i == 0 ? r0.scale : nullptr;
+    const float* xb = i == 0 ? r0.shift : nullptr;
+    const BnRows r1 = ps.rows(B.b1), r2 = ps.rows(B.b2);
+    const Shortcut sc = ps.shortcut(B, xin);
     // dy1 / dy2 / dys alternate between two sets, so this block only has to wait for the weight gradients of the block
     // before the previous one (the side stream may lag one block behind)
     // The two blocks visited first (small tensors) own private sets: with a deferred decoder join the side stream may still be
@@ -711,18 +699,13 @@ int Net::encoder_bwd(int N, const float* d_mu, const float* d_logvar, const floa
     // an identity shortcut's gradient is the masked incoming gradient itself: it goes straight into the block-input gradient
     const long dyso = B.identity ? P.g[cur ^ 1] : (priv ? P.edys[i - (ne - 2)] : P.dys[ds]);
     if (i + 2 <= ne - 1) MM_TRY(side_wait_mark(i + 2, s));
-    const void* ysp = B.identity ? xin : base + B.ys;
-    const float* ssc = B.identity ? ones(base) : bnf(B.bs, base, 2);
-    const float* ssh = B.identity ? zeros(base) : bnf(B.bs, base, 3);
     // join backward: g = d_out * [out > 0] feeds bn2 (y2) and the shortcut BN (ys)
-    int np = launch_bn_bwd_reduce(dt(), base + P.g[cur], nullptr, bnf(B.b2, base, 2), bnf(B.b2, base, 3), base + B.y2, ysp, npix, B.C, part, s, ssc, ssh);
+    int np = launch_bn_bwd_reduce(dt(), base + P.g[cur], nullptr, r2.scale, r2.shift, base + B.y2, sc.y, npix, B.C, part, s, sc.scale, sc.shift);
     MM_TRY(np);
-    if (B.identity) MM_TRY(bn_backward_coefs(B.b2, params, grads, base, np, 2, 0, cnt, s));
-    else MM_TRY(bn_backward_coefs_join(B.b2, B.bs, params, grads, base, np, cnt, s));
-    MM_TRY(launch_bn_bwd_apply(dt(), base + P.g[cur], nullptr, bnf(B.b2, base, 2), bnf(B.b2, base, 3), base + B.y2, bnf(B.b2, base, 4), bnf(B.b2, base, 5),
-                               bnf(B.b2, base, 6), base + dy2o, ysp, B.identity ? ones(base) : bnf(B.bs, base, 4),
-                               B.identity ? zeros(base) : bnf(B.bs, base, 5), B.identity ? zeros(base) : bnf(B.bs, base, 6), base + dyso, npix, B.C, s,
-                               ssc, ssh));
+    if (B.identity) MM_TRY(bn_backward_coefs(ps, B.b2, np, 2, 0, cnt, s));
+    else MM_TRY(bn_backward_coefs_join(ps, B.b2, B.bs, np, cnt, s));
+    MM_TRY(launch_bn_bwd_apply(dt(), base + P.g[cur], nullptr, r2.scale, r2.shift, base + B.y2, r2.A, r2.B, r2.C, base + dy2o, sc.y, sc.A, sc.B,
+                               sc.C, base + dyso, npix, B.C, s, sc.scale, sc.shift));
     // conv2 (3x3 s1): wgrad with a1 = relu(bn1(y1)) recomputed in the load prologue; dgrad -> d_a1
     hipStream_t wsm = wgrad_stream(s);
     MM_TRY(side_fork(s));
@@ -733,47 +716,44 @@ int Net::encoder_bwd(int N, const float* d_mu, const float* d_logvar, const floa
     // 10, and it sat in front of the last big kernel of the side stream
     WgradReduceArgs late; late.nparts = 0;
     if (i == 0 && wsm != s && !B.c2.fp8 && op_wgrad_is_stream(dt(), geom(B.c2), N, B.Hout, B.Wout, B.Hout, B.Wout, false, true))
-      MM_TRY(op_run_wgrad(dt(), geom(B.c2), N, base + dy2o, B.Hout, B.Wout, nullptr, nullptr, 1, base + B.y1, B.Hout, B.Wout, bnf(B.b1, base, 2),
-                          bnf(B.b1, base, 3), 1, grads + B.c2.off, wsm, reinterpret_cast<float*>(base + P.wscratch2), B.c2.wscale, &late));
+      MM_TRY(op_run_wgrad(dt(), geom(B.c2), N, base + dy2o, B.Hout, B.Wout, nullptr, nullptr, 1, base + B.y1, B.Hout, B.Wout, r1.scale,
+                          r1.shift, 1, grads + B.c2.off, wsm, reinterpret_cast<float*>(base + P.wscratch2), B.c2.wscale, &late));
     else
-      MM_TRY(run_wgrad(B.c2, N, base + dy2o, B.Hout, B.Wout, nullptr, nullptr, base + B.y1, B.Hout, B.Wout, bnf(B.b1, base, 2),
-                       bnf(B.b1, base, 3), grads, wsm));
+      MM_TRY(run_wgrad(ps, B.c2, base + dy2o, B.Hout, B.Wout, nullptr, nullptr, base + B.y1, B.Hout, B.Wout, r1.scale, r1.shift, wsm));
     // (encoder.layer1: the shortcut's weight gradient rides on conv1's pass over the block input, below)
     const bool pair = !B.identity && !B.c1.fp8 && !B.cs.fp8 && wgrad_pair_ok(dt(), geom(B.c1), geom(B.cs), B.Hout, B.Hin);
-    if (!B.identity && !pair) MM_TRY(run_wgrad(B.cs, N, base + dyso, B.Hout, B.Wout, nullptr, nullptr, xin, B.Hin, B.Win, xs, xb, grads, wsm));
+    if (!B.identity && !pair) MM_TRY(run_wgrad(ps, B.cs, base + dyso, B.Hout, B.Wout, nullptr, nullptr, xin, B.Hin, B.Win, xs, xb, wsm));
     if (i == 0 && l1_dgrad_stream()) {
       // encoder.layer1.conv2: the data gradient as a per-wave stream over dy2 (conv3_stream_kernel) with bn1's backward sums from the same pass
-      np = launch_conv3_stream_bwd(dt(), base + dy2o, base + plan_.packed + l1c2_flip * (long)esz(), base + P.da1, base + B.y1, bnf(B.b1, base, 2),
-                                   bnf(B.b1, base, 3), part, N, B.Hout, s);
+      np = launch_conv3_stream_bwd(dt(), base + dy2o, ps.packed(l1c2_flip), base + P.da1, base + B.y1, r1.scale, r1.shift, part, N, B.Hout, s);
     } else {
-      MM_TRY(run_up(B.c2, base, N, base + dy2o, B.Hout, B.Wout, base + P.da1, B.Hout, B.Wout, nullptr, nullptr, 0, nullptr, 0, s));
+      MM_TRY(run_up(ps, B.c2, base + dy2o, B.Hout, B.Wout, base + P.da1, B.Hout, B.Wout, nullptr, nullptr, 0, nullptr, 0, s));
       // bn1 + relu backward
-      np = launch_bn_bwd_reduce(dt(), base + P.da1, nullptr, bnf(B.b1, base, 2), bnf(B.b1, base, 3), base + B.y1, nullptr, npix, B.C, part, s);
+      np = launch_bn_bwd_reduce(dt(), base + P.da1, nullptr, r1.scale, r1.shift, base + B.y1, nullptr, npix, B.C, part, s);
     }
     MM_TRY(np);
-    MM_TRY(bn_backward_coefs(B.b1, params, grads, base, np, 1, 0, cnt, s));
-    MM_TRY(launch_bn_bwd_apply(dt(), base + P.da1, nullptr, bnf(B.b1, base, 2), bnf(B.b1, base, 3), base + B.y1, bnf(B.b1, base, 4),
-                               bnf(B.b1, base, 5), bnf(B.b1, base, 6), base + dy1o, nullptr, nullptr, nullptr, nullptr, nullptr, npix,
-                               B.C, s));
+    MM_TRY(bn_backward_coefs(ps, B.b1, np, 1, 0, cnt, s));
+    MM_TRY(launch_bn_bwd_apply(dt(), base + P.da1, nullptr, r1.scale, r1.shift, base + B.y1, r1.A, r1.B, r1.C, base + dy1o, nullptr, nullptr,
+                               nullptr, nullptr, nullptr, npix, B.C, s));
     // conv1 (3x3) and the 1x1 s2 shortcut: weight gradients, then d_xin = dgrad(conv1) + dgrad(shortcut)
     MM_TRY(side_fork(s));
     int taken = 0;
     if (pair) {
       taken = op_run_wgrad_pair(dt(), geom(B.c1), geom(B.cs), N, base + dy1o, base + dyso, B.Hout, B.Wout, xin, B.Hin, B.Win, xs, xb, 1,
-                                grads + B.c1.off, grads + B.cs.off, wsm, wscratch_, B.c1.wscale, B.cs.wscale);
+                                grads + B.c1.off, grads + B.cs.off, wsm, ps.wscratch, B.c1.wscale, B.cs.wscale);
       MM_TRY(taken);
-      if (!taken) MM_TRY(run_wgrad(B.cs, N, base + dyso, B.Hout, B.Wout, nullptr, nullptr, xin, B.Hin, B.Win, xs, xb, grads, wsm));
+      if (!taken) MM_TRY(run_wgrad(ps, B.cs, base + dyso, B.Hout, B.Wout, nullptr, nullptr, xin, B.Hin, B.Win, xs, xb, wsm));
     }
-    if (!taken) MM_TRY(run_wgrad(B.c1, N, base + dy1o, B.Hout, B.Wout, nullptr, nullptr, xin, B.Hin, B.Win, xs, xb, grads, wsm));
+    if (!taken) MM_TRY(run_wgrad(ps, B.c1, base + dy1o, B.Hout, B.Wout, nullptr, nullptr, xin, B.Hin, B.Win, xs, xb, wsm));
     if (late.nparts > 0) MM_TRY(launch_wgrad_reduce(late, wsm));
     MM_TRY(side_mark(i));
     if (i == 0 && stem_dg_fused()) {
       // the gradient of the stem's output is never a tensor: stem_bwd_kernel<DG> recomputes it row by row from dy1 / dys (below)
-      stem_dy1_ = dy1o; stem_dys_ = dyso;
+      stem_dy1 = dy1o; stem_dys = dyso;
     } else if (B.identity)     // d_xin already holds the shortcut's share: the main path's data gradient is added to it
-      MM_TRY(run_up(B.c1, base, N, base + dy1o, B.Hout, B.Wout, base + P.g[cur ^ 1], B.Hin, B.Win, nullptr, nullptr, 0, nullptr, 1, s));
+      MM_TRY(run_up(ps, B.c1, base + dy1o, B.Hout, B.Wout, base + P.g[cur ^ 1], B.Hin, B.Win, nullptr, nullptr, 0, nullptr, 1, s));
     else                // one kernel: the 1x1 stride-2 shortcut's data gradient is a second source of the 3x3 conv's (phase (0,0))
-      MM_TRY(run_up(B.c1, base, N, base + dy1o, B.Hout, B.Wout, base + P.g[cur ^ 1], B.Hin, B.Win, nullptr, nullptr, 0, nullptr, 0, s, &B.cs,
+      MM_TRY(run_up(ps, B.c1, base + dy1o, B.Hout, B.Wout, base + P.g[cur ^ 1], B.Hin, B.Win, nullptr, nullptr, 0, nullptr, 0, s, &B.cs,
                     base + dyso));
     cur ^= 1;
   }
@@ -784,21 +764,19 @@ int Net::encoder_bwd(int N, const float* d_mu, const float* d_logvar, const floa
     const long npix = (long)N * H1 * W1;
     const Block& B0 = enc[0];
     const int np = stem_dg_fused()
-        ? launch_stem_bwd_dg(base + stem_dy1_, base + stem_dys_, base + P.packed + B0.c1.packU * (long)esz(), base + P.packed + B0.cs.packU * (long)esz(),
-                             base + P.y0, base + P.x_t, bnf(bn0, base, 2), bnf(bn0, base, 3), part, kPartialFloats, N, cfg.S, H1, W1, s)
-        : launch_stem_bwd(dt(), base + P.g[cur], base + P.y0, base + P.x_t, bnf(bn0, base, 2), bnf(bn0, base, 3), part, kPartialFloats,
-                          N, cfg.S, H1, W1, s);
+        ? launch_stem_bwd_dg(base + stem_dy1, base + stem_dys, ps.packed(B0.c1.packU), ps.packed(B0.cs.packU), base + P.y0, base + P.x_t,
+                             r0.scale, r0.shift, part, kPartialFloats, N, cfg.S, H1, W1, s)
+        : launch_stem_bwd(dt(), base + P.g[cur], base + P.y0, base + P.x_t, r0.scale, r0.shift, part, kPartialFloats, N, cfg.S, H1, W1, s);
     MM_TRY(np);
     const float* gsum = nullptr; double cnt = (double)npix;
     if (sync_bn_on()) {
       float* row = nullptr;
-      MM_TRY(sync_rows(base, part, np, 64, s, &row, stem_bwd_part_floats()));
+      MM_TRY(sync_rows(ps, part, np, 64, s, &row, stem_bwd_part_floats()));
       gsum = row; cnt *= ar_world_;
     }
     if (side_state_ == 1 && hipStreamWaitEvent(s, gram_ev_, 0) != hipSuccess) { set_error("side stream wait failed"); return MMVAE_ERR_HIP; }
     MM_TRY(launch_stem_bwd_finalize(part, np, reinterpret_cast<const double*>(base + P.stem_R), params + stem.off, gsum, cnt,
-                                    params + bn0.g_off, bnf(bn0, base, 0), bnf(bn0, base, 1), grads + bn0.g_off, grads + bn0.b_off,
-                                    grads + stem.off, s));
+                                    params + bn0.g_off, r0.mean, r0.istd, grads + bn0.g_off, grads + bn0.b_off, grads + stem.off, s));
     return side_join(s);             // every weight gradient of this pass
   }
   // ---- stem: bn0 + relu backward, then the 5x5 weight gradient
@@ -806,15 +784,15 @@ int Net::encoder_bwd(int N, const float* d_mu, const float* d_logvar, const floa
   const int ds = 1;
   {
     const long npix = (long)N * H1 * W1;
-    int np = launch_bn_bwd_reduce(dt(), base + P.g[cur], nullptr, bnf(bn0, base, 2), bnf(bn0, base, 3), base + P.y0, nullptr, npix, 32, part, s);
+    int np = launch_bn_bwd_reduce(dt(), base + P.g[cur], nullptr, r0.scale, r0.shift, base + P.y0, nullptr, npix, 32, part, s);
     MM_TRY(np);
-    MM_TRY(bn_backward_coefs(bn0, params, grads, base, np, 1, 0, (double)npix, s));
-    MM_TRY(launch_bn_bwd_apply(dt(), base + P.g[cur], nullptr, bnf(bn0, base, 2), bnf(bn0, base, 3), base + P.y0, bnf(bn0, base, 4),
-                               bnf(bn0, base, 5), bnf(bn0, base, 6), base + P.dy1[ds], nullptr, nullptr, nullptr, nullptr, nullptr, npix, 32, s));
+    MM_TRY(bn_backward_coefs(ps, bn0, np, 1, 0, (double)npix, s));
+    MM_TRY(launch_bn_bwd_apply(dt(), base + P.g[cur], nullptr, r0.scale, r0.shift, base + P.y0, r0.A, r0.B, r0.C, base + P.dy1[ds], nullptr,
+                               nullptr, nullptr, nullptr, nullptr, npix, 32, s));
     MM_TRY(side_fork(s));
     hipStream_t wsm = wgrad_stream(s);
     WgradArgs a; std::memset(&a, 0, sizeof(a));
-    a.P = base + P.dy1[ds]; a.dW = grads + stem.off; a.scratch = wscratch_;
+    a.P = base + P.dy1[ds]; a.dW = grads + stem.off; a.scratch = ps.wscratch;
     a.N = N; a.Hp = H1; a.Wp = W1; a.Ca = 32; a.scale = 1.f;
     if (cfg.in_ch > 1) {
       // in_channels > 1 (main.py:555): G = the image as NHWC with 16 zero-padded channels, the generic 25-tap weight gradient
@@ -837,28 +815,29 @@ int Net::encoder_bwd(int N, const float* d_mu, const float* d_logvar, const floa
 // ------------------------------------------------------------------------------------------------ decoder
 int Net::decoder_fwd(int N, const float* encv, const float* params, float* bnbuf, long long* nbt, void* ws, size_t ws_bytes,
                      float* recon, int training, hipStream_t s) {
-  const Plan& P = plan(N);
-  if (ws_bytes < P.bytes) { set_error("workspace too small: %zu < %zu", ws_bytes, P.bytes); return MMVAE_ERR_WORKSPACE; }
-  char* base = static_cast<char*>(ws);
-  float* part = reinterpret_cast<float*>(base + P.partials);
+  Pass ps;
+  MM_TRY(begin_pass(ps, N, ws, ws_bytes, params, nullptr, bnbuf, nbt, training != 0));
+  const Plan& P = *ps.P;
+  char* const base = ps.base;
+  float* const part = ps.part;
   float* stats = training ? part : nullptr;
   pack_batch_begin();
-  MM_TRY(packs_dec_fwd(params, base, s));
+  MM_TRY(packs_dec_fwd(ps, s));
   MM_TRY(pack_batch_flush(dt(), s));
   eval_folded_ = false;
-  if (!training) MM_TRY(fold_bn_eval(1, params, bnbuf, base, s));
+  if (!training) MM_TRY(fold_bn_eval(ps, 1, s));
   MM_TRY(launch_convert(DT_F32, dt(), encv, base + P.enc_t, (long)N * cfg.z, s));
   // stem ConvTranspose2d(z -> 128, k2) on the 1x1 latent (model.py:159-161,182)
-  int np = run_up(dstem, base, N, base + P.enc_t, 1, 1, base + P.y0d, 2, 2, nullptr, nullptr, 0, stats, 0, s);
+  int np = run_up(ps, dstem, base + P.enc_t, 1, 1, base + P.y0d, 2, 2, nullptr, nullptr, 0, stats, 0, s);
   MM_TRY(np);
-  MM_TRY(training ? bn_train(dbn0, params, bnbuf, nbt, base, np, (double)N * 4, s, 0, dstem.wscale) : bn_eval(dbn0, params, bnbuf, base, s, dstem.wscale));
+  MM_TRY(bn_fwd(ps, dbn0, np, (double)N * 4, s, 0, dstem.wscale));
   const void* xin = base + P.y0d;
-  const float* xs = bnf(dbn0, base, 2);
-  const float* xb = bnf(dbn0, base, 3);
+  const float* xs = ps.rows(dbn0).scale;
+  const float* xb = ps.rows(dbn0).shift;
   const int nd = (int)dec.size();
   if (cfg.blocks > 1) {
     // the first block of a deeper decoder has an identity shortcut: it needs the stem's activation as a tensor
-    MM_TRY(fill_consts(base, s));
+    MM_TRY(fill_consts(ps, s));
     MM_TRY(launch_affine_act(dt(), base + P.y0d, xs, xb, 1, base + P.act0d, (long)N * 4, 128, s));
     xin = base + P.act0d; xs = xb = nullptr;
   }
@@ -866,33 +845,35 @@ int Net::decoder_fwd(int N, const float* encv, const float* params, float* bnbuf
   for (int i = 0; i < nd; ++i) {
     Block& B = dec[i];
     const double cnt = (double)N * B.Hout * B.Wout;
+    const BnRows r1 = ps.rows(B.b1), r2 = ps.rows(B.b2);
+    const Shortcut sc = ps.shortcut(B, xin);
     // upsample (shortcut) branch on the side stream, concurrently with conv1 -> bn1 -> conv2 -> bn2
     if (!B.identity) {
       MM_TRY(side_fork(s));
       hipStream_t ss = wgrad_stream(s);
       if (!B.cs.fp8 && convT4_stream_ok(dt(), B.cs.D0, B.cs.D1, B.cs.k, B.cs.s, B.cs.p, B.Hin, B.Win))
-        np = launch_convT4_stream(dt(), xin, base + plan_.packed + B.cs.packU * (long)esz(), base + B.ys, xs, xb, 1, stats ? stats + kPartialFloats : nullptr,
+        np = launch_convT4_stream(dt(), xin, ps.packed(B.cs.packU), base + B.ys, xs, xb, 1, stats ? stats + kPartialFloats : nullptr,
                                   N, B.Hin, ss, (store8 && i == nd - 1) ? 1 : 0);
       else
-        np = run_up(B.cs, base, N, xin, B.Hin, B.Win, base + B.ys, B.Hout, B.Wout, xs, xb, 1, stats ? stats + kPartialFloats : nullptr, 0, ss);
+        np = run_up(ps, B.cs, xin, B.Hin, B.Win, base + B.ys, B.Hout, B.Wout, xs, xb, 1, stats ? stats + kPartialFloats : nullptr, 0, ss);
       MM_TRY(np);
-      MM_TRY(training ? bn_train(B.bs, params, bnbuf, nbt, base, np, cnt, ss, kPartialFloats, B.cs.wscale) : bn_eval(B.bs, params, bnbuf, base, ss, B.cs.wscale));
+      MM_TRY(bn_fwd(ps, B.bs, np, cnt, ss, kPartialFloats, B.cs.wscale));
     }
     // (conv1 already done: the previous block's join kernel computed it from the joined row it had in LDS -- join_conv1_fwd below)
-    np = c1_done > 0 ? c1_done : run_down(B.c1, base, N, xin, B.Hin, B.Win, base + B.y1, B.Hin, B.Win, xs, xb, 1, stats, 0, dt(), s);
+    np = c1_done > 0 ? c1_done : run_down(ps, B.c1, xin, B.Hin, B.Win, base + B.y1, B.Hin, B.Win, xs, xb, 1, stats, 0, dt(), s);
     c1_done = 0;
     MM_TRY(np);
-    MM_TRY(training ? bn_train(B.b1, params, bnbuf, nbt, base, np, (double)N * B.Hin * B.Win, s, 0, B.c1.wscale) : bn_eval(B.b1, params, bnbuf, base, s, B.c1.wscale));
+    MM_TRY(bn_fwd(ps, B.b1, np, (double)N * B.Hin * B.Win, s, 0, B.c1.wscale));
     if (B.identity)    // 3x3 Conv2d, shape preserving
-      np = run_down(B.c2, base, N, base + B.y1, B.Hin, B.Win, base + B.y2, B.Hout, B.Wout, bnf(B.b1, base, 2), bnf(B.b1, base, 3), 1, stats, 0, dt(), s);
+      np = run_down(ps, B.c2, base + B.y1, B.Hin, B.Win, base + B.y2, B.Hout, B.Wout, r1.scale, r1.shift, 1, stats, 0, dt(), s);
     else
       if (!B.c2.fp8 && convT4_stream_ok(dt(), B.c2.D0, B.c2.D1, B.c2.k, B.c2.s, B.c2.p, B.Hin, B.Win))   // per-wave stream (conv_fstream.hip)
-        np = launch_convT4_stream(dt(), base + B.y1, base + plan_.packed + B.c2.packU * (long)esz(), base + B.y2, bnf(B.b1, base, 2), bnf(B.b1, base, 3), 1,
-                                  stats, N, B.Hin, s, (store8 && i == nd - 1) ? 1 : 0);
+        np = launch_convT4_stream(dt(), base + B.y1, ps.packed(B.c2.packU), base + B.y2, r1.scale, r1.shift, 1, stats, N, B.Hin, s,
+                                  (store8 && i == nd - 1) ? 1 : 0);
       else
-        np = run_up(B.c2, base, N, base + B.y1, B.Hin, B.Win, base + B.y2, B.Hout, B.Wout, bnf(B.b1, base, 2), bnf(B.b1, base, 3), 1, stats, 0, s);
+        np = run_up(ps, B.c2, base + B.y1, B.Hin, B.Win, base + B.y2, B.Hout, B.Wout, r1.scale, r1.shift, 1, stats, 0, s);
     MM_TRY(np);
-    MM_TRY(training ? bn_train(B.b2, params, bnbuf, nbt, base, np, cnt, s, 0, B.c2.wscale) : bn_eval(B.b2, params, bnbuf, base, s, B.c2.wscale));
+    MM_TRY(bn_fwd(ps, B.b2, np, cnt, s, 0, B.c2.wscale));
     if (!B.identity) MM_TRY(side_join(s));
     if (i == nd - 1 && tail_fwd_fused()) break;     // the join of the last block happens inside the tail conv kernel
     if (i == nd - 1 && store8) { set_error("fp8 storage of the last up-block needs the fused tail kernels"); return MMVAE_ERR_UNSUPPORTED; }
@@ -902,67 +883,60 @@ int Net::decoder_fwd(int N, const float* encv, const float* params, float* bnbuf
                          dec[i + 1].c1.D1 == B.C && frag_down(dec[i + 1].c1) == 0 && dec[i + 1].c1.wscale == 1.f &&
                          join_conv1_fwd_ok(dt(), B.C, dec[i + 1].c1.D0, (long)N * B.Hout * B.Wout);
     if (fuse_c1) {
-      c1_done = launch_join_conv1_fwd(B.C, base + B.y2, bnf(B.b2, base, 2), bnf(B.b2, base, 3), base + B.ys, bnf(B.bs, base, 2), bnf(B.bs, base, 3),
-                                      base + plan_.packed + dec[i + 1].c1.packD * (long)esz(), base + B.out, base + dec[i + 1].y1, stats,
-                                      (long)N * B.Hout * B.Wout, s);
+      c1_done = launch_join_conv1_fwd(B.C, base + B.y2, r2.scale, r2.shift, sc.y, sc.scale, sc.shift, ps.packed(dec[i + 1].c1.packD),
+                                      base + B.out, base + dec[i + 1].y1, stats, (long)N * B.Hout * B.Wout, s);
       MM_TRY(c1_done);
     } else
-    MM_TRY(launch_join_fwd(dt(), base + B.y2, bnf(B.b2, base, 2), bnf(B.b2, base, 3), B.identity ? xin : base + B.ys,
-                           B.identity ? ones(base) : bnf(B.bs, base, 2), B.identity ? zeros(base) : bnf(B.bs, base, 3), base + B.out,
+    MM_TRY(launch_join_fwd(dt(), base + B.y2, r2.scale, r2.shift, sc.y, sc.scale, sc.shift, base + B.out,
                            (long)N * B.Hout * B.Wout, B.C, s));
     xin = base + B.out; xs = xb = nullptr;
   }
   // tail conv (+bias) and the output BatchNorm (model.py:193)
   float* r_raw = reinterpret_cast<float*>(base + P.r_raw);
   if (tail_fwd_fused()) {
-    const Block& B = dec.back();
+    const Block& B = dec.back();     // (the join left to this kernel: xin is still the block's input)
+    const BnRows r1 = ps.rows(B.b1), r2 = ps.rows(B.b2);
+    const Shortcut sc = ps.shortcut(B, xin);
     if (!store8 && !B.identity && !B.c2.fp8 && !B.cs.fp8 && tail_fwd_stream_ok(dt(), cfg.out_ch, Sd, Sd) &&
         up5_tail_fwd_ok(dt(), cfg.out_ch, B.C, B.Cin, B.Hin, B.Hout) && convT4_stream_ok(dt(), B.c2.D0, B.c2.D1, B.c2.k, B.c2.s, B.c2.p, B.Hin, B.Win))
       // the join + tail conv with both branch outputs recomputed from the ConvTranspose2d inputs (0.34 GB) instead of read back (1.34 GB)
-      np = launch_up5_tail_fwd(base + B.y1, bnf(B.b1, base, 2), bnf(B.b1, base, 3), base + plan_.packed + B.c2.packU * (long)esz(), xin, xs, xb,
-                               base + plan_.packed + B.cs.packU * (long)esz(), bnf(B.b2, base, 2), bnf(B.b2, base, 3), bnf(B.bs, base, 2),
-                               bnf(B.bs, base, 3), params + tail.off, params + tail_bias, r_raw, stats, N, s);
+      np = launch_up5_tail_fwd(base + B.y1, r1.scale, r1.shift, ps.packed(B.c2.packU), xin, xs, xb, ps.packed(B.cs.packU), r2.scale, r2.shift,
+                               sc.scale, sc.shift, params + tail.off, params + tail_bias, r_raw, stats, N, s);
     else if (tail_fwd_stream_ok(dt(), cfg.out_ch, Sd, Sd))
-      np = launch_tail_fwd_stream(dt(), base + B.y2, bnf(B.b2, base, 2), bnf(B.b2, base, 3), base + B.ys, bnf(B.bs, base, 2), bnf(B.bs, base, 3),
-                                  params + tail.off, params + tail_bias, r_raw, stats, N, Sd, Sd, s, store8 ? 1 : 0);
+      np = launch_tail_fwd_stream(dt(), base + B.y2, r2.scale, r2.shift, sc.y, sc.scale, sc.shift, params + tail.off, params + tail_bias,
+                                  r_raw, stats, N, Sd, Sd, s, store8 ? 1 : 0);
     else if (store8) { set_error("fp8 storage of the last up-block needs tail_fwd_stream"); return MMVAE_ERR_UNSUPPORTED; }
     else
-      np = launch_tail_join_fwd(dt(), base + B.y2, bnf(B.b2, base, 2), bnf(B.b2, base, 3), base + B.ys, bnf(B.bs, base, 2), bnf(B.bs, base, 3),
-                                params + tail.off, params + tail_bias, r_raw, stats, N, Sd, Sd, s);
-    MM_TRY(np);
-    if (training) MM_TRY(bn_train(bn_out, params, bnbuf, nbt, base, np, (double)N * Sd * Sd, s));
+      np = launch_tail_join_fwd(dt(), base + B.y2, r2.scale, r2.shift, sc.y, sc.scale, sc.shift, params + tail.off, params + tail_bias,
+                                r_raw, stats, N, Sd, Sd, s);
   } else {
     // Conv2d(16 -> out_ch, k3 p1, bias): GEMM rows padded to 16 in LDS, epilogue stores the out_ch real rows as NCHW f32
-    PackArgs pa; std::memset(&pa, 0, sizeof(pa));
-    pa.src = params + tail.off; pa.dst = base + P.packed + tail_pack_f * (long)esz();
-    pa.cols = 16; pa.cols_valid = cfg.out_ch; pa.K = 16; pa.ntaps = 9; pa.s_col = 144; pa.s_k = 9; pa.scale = 1.f;
-    for (int t = 0; t < 9; ++t) pa.tap_off[t] = t;
     GatherArgs a; std::memset(&a, 0, sizeof(a));
-    a.x = xin; a.w = pa.dst; a.y = r_raw; a.bias = params + tail_bias; a.stats = stats; a.y_planes = cfg.out_ch;
+    a.x = xin; a.w = ps.packed(tail_pack_f); a.y = r_raw; a.bias = params + tail_bias; a.stats = stats; a.y_planes = cfg.out_ch;
     a.N = N; a.Hi = Sd; a.Wi = Sd; a.Cin = 16; a.Ho = Sd; a.Wo = Sd; a.Cout = 16; a.SI = 1; a.SO = 1;
     a.nphase = 1; a.phases[0] = Phase{0, 0, Sd, Sd, 9, 0, 0};
     for (int kh = 0; kh < 3; ++kh) for (int kw = 0; kw < 3; ++kw) a.taps[kh * 3 + kw] = Tap{kh - 1, kw - 1};
     np = launch_gather_gemm(dt(), DT_F32, a, s);
-    MM_TRY(np);
-    if (training) MM_TRY(bn_train(bn_out, params, bnbuf, nbt, base, np, (double)N * Sd * Sd, s));
   }
-  if (!training) MM_TRY(bn_eval(bn_out, params, bnbuf, base, s));
-  MM_TRY(launch_affine_nchw(r_raw, bnf(bn_out, base, 2), bnf(bn_out, base, 3), recon, N, cfg.out_ch, Sd * Sd, s));
+  MM_TRY(np);
+  MM_TRY(bn_fwd(ps, bn_out, np, (double)N * Sd * Sd, s));
+  MM_TRY(launch_affine_nchw(r_raw, ps.rows(bn_out).scale, ps.rows(bn_out).shift, recon, N, cfg.out_ch, Sd * Sd, s));
   return MMVAE_OK;
 }
 
 int Net::decoder_bwd(int N, const float* d_recon, const float* params, float* grads, void* ws, size_t ws_bytes, float* d_enc,
                      hipStream_t s, const GaussTail* gauss) {
-  const Plan& P = plan(N);
-  if (ws_bytes < P.bytes) { set_error("workspace too small"); return MMVAE_ERR_WORKSPACE; }
-  char* base = static_cast<char*>(ws);
-  wscratch_ = reinterpret_cast<float*>(base + P.wscratch);
-  float* part = reinterpret_cast<float*>(base + P.partials);
+  Pass ps;
+  MM_TRY(begin_pass(ps, N, ws, ws_bytes, params, grads));
+  const Plan& P = *ps.P;
+  char* const base = ps.base;
+  float* const part = ps.part;
   float* r_raw = reinterpret_cast<float*>(base + P.r_raw);
   float* d_raw = reinterpret_cast<float*>(base + P.d_raw);
+  const BnRows r0 = ps.rows(dbn0), ro = ps.rows(bn_out);
   const int HW = Sd * Sd;
   pack_batch_begin();
-  MM_TRY(packs_dec_bwd(params, base, d_enc != nullptr, s));
+  MM_TRY(packs_dec_bwd(ps, d_enc != nullptr, s));
   MM_TRY(pack_batch_flush(dt(), s));
   // the encoder stem's patch gram matrix (input only; stem_bwd.hip): here the side stream is idle for ~1 ms beside HBM-bound kernels, at the
   // start of encoder_bwd it ran beside the latency-bound kernels around the latent code and held their small launches up (lesson 55)
@@ -976,17 +950,17 @@ int Net::decoder_bwd(int N, const float* d_recon, const float* params, float* gr
     // 6.018 vs 6.018 ms over three A/B pairs; not kept)
   }
   // ---- output BN backward, tail conv backward
-  int np = gauss ? launch_gauss_tail_reduce(r_raw, gauss->target, bnf(bn_out, base, 2), bnf(bn_out, base, 3), gauss->sigma, gauss->coef, gauss->gscale, N,
-                                            cfg.out_ch, HW, part, s)
+  int np = gauss ? launch_gauss_tail_reduce(r_raw, gauss->target, ro.scale, ro.shift, gauss->sigma, gauss->coef, gauss->gscale, N, cfg.out_ch,
+                                            HW, part, s)
                  : launch_bn_bwd_reduce_nchw(d_recon, r_raw, N, cfg.out_ch, HW, part, s);
   MM_TRY(np);
   // (the tail conv's bias gradient, sum of d_raw per output channel, in closed form from the same sums: BnBwdFinalizeArgs::dbias_conv)
-  MM_TRY(bn_backward_coefs(bn_out, params, grads, base, np, 1, 0, (double)N * HW, s, grads + tail_bias));
+  MM_TRY(bn_backward_coefs(ps, bn_out, np, 1, 0, (double)N * HW, s, grads + tail_bias));
   if (gauss)
-    MM_TRY(launch_gauss_tail_apply(r_raw, gauss->target, bnf(bn_out, base, 2), bnf(bn_out, base, 3), gauss->sigma, gauss->coef, gauss->gscale,
-                                   bnf(bn_out, base, 4), bnf(bn_out, base, 5), bnf(bn_out, base, 6), d_raw, N, cfg.out_ch, HW, s));
+    MM_TRY(launch_gauss_tail_apply(r_raw, gauss->target, ro.scale, ro.shift, gauss->sigma, gauss->coef, gauss->gscale, ro.A, ro.B, ro.C, d_raw,
+                                   N, cfg.out_ch, HW, s));
   else
-    MM_TRY(launch_bn_bwd_apply_nchw(d_recon, r_raw, bnf(bn_out, base, 4), bnf(bn_out, base, 5), bnf(bn_out, base, 6), d_raw, N, cfg.out_ch, HW, s));
+    MM_TRY(launch_bn_bwd_apply_nchw(d_recon, r_raw, ro.A, ro.B, ro.C, d_raw, N, cfg.out_ch, HW, s));
   const bool tail_fused = !dec.empty() && dec.back().C == 16 && tail_join_fusable(dt(), cfg.out_ch, N, Sd, Sd);
   // forward did not store the joined activation: the weight gradient recomputes it inside the join-backward reduce pass (below)
   const bool tail_wg_in_reduce = tail_fwd_fused() && tail_fused;
@@ -995,7 +969,7 @@ int Net::decoder_bwd(int N, const float* d_recon, const float* params, float* gr
     if (tail_fwd_fused()) { set_error("decoder_bwd: the fused tail forward (no stored join) needs the fused tail backward"); return MMVAE_ERR_UNSUPPORTED; }
     // dW[oc][ci][kh][kw]: P = d_raw (planar f32, out_ch planes staged as 16 zero-padded channels), G = the last up-block's output
     WgradArgs a; std::memset(&a, 0, sizeof(a));
-    a.P = d_raw; a.P_planar = 1; a.P_planes = cfg.out_ch; a.G = base + dec.back().out; a.dW = grads + tail.off; a.scratch = wscratch_;
+    a.P = d_raw; a.P_planar = 1; a.P_planes = cfg.out_ch; a.G = base + dec.back().out; a.dW = grads + tail.off; a.scratch = ps.wscratch;
     a.N = N; a.Hp = Sd; a.Wp = Sd; a.Ca = 16; a.Ca_valid = cfg.out_ch; a.Hg = Sd; a.Wg = Sd; a.Cb = 16; a.Cb_valid = 16;
     a.stride = 1; a.pad = 1; a.ksz = 3; a.sA = 16 * 9; a.sB = 9; a.ntaps = 9; a.scale = 1.f;
     for (int t = 0; t < 9; ++t) a.tap_off[t] = t;
@@ -1007,12 +981,8 @@ int Net::decoder_bwd(int N, const float* d_recon, const float* params, float* gr
   // (launch_tail_join_bwd_*).  Otherwise the separate dgrad kernel:
   if (!tail_fused) {
     // dx[n,h,w,ci] = sum dy[n,oc,h+1-kh,w+1-kw] * w[oc][ci][kh][kw]: planar f32 source padded to 8 channels in LDS
-    PackArgs pa; std::memset(&pa, 0, sizeof(pa));
-    pa.src = params + tail.off; pa.dst = base + P.packed + tail_pack_d * (long)esz();
-    pa.cols = 16; pa.K = 8; pa.K_valid = cfg.out_ch; pa.ntaps = 9; pa.s_col = 9; pa.s_k = 144; pa.scale = 1.f;
-    for (int t = 0; t < 9; ++t) pa.tap_off[t] = t;
     GatherArgs a; std::memset(&a, 0, sizeof(a));
-    a.x = d_raw; a.w = pa.dst; a.y = base + P.g[cur]; a.x_planar = 1; a.x_planes = cfg.out_ch;
+    a.x = d_raw; a.w = ps.packed(tail_pack_d); a.y = base + P.g[cur]; a.x_planar = 1; a.x_planes = cfg.out_ch;
     a.N = N; a.Hi = Sd; a.Wi = Sd; a.Cin = 8; a.Ho = Sd; a.Wo = Sd; a.Cout = 16; a.SI = 1; a.SO = 1;
     a.nphase = 1; a.phases[0] = Phase{0, 0, Sd, Sd, 9, 0, 0};
     for (int kh = 0; kh < 3; ++kh) for (int kw = 0; kw < 3; ++kw) a.taps[kh * 3 + kw] = Tap{1 - kh, 1 - kw};
@@ -1037,72 +1007,59 @@ int Net::decoder_bwd(int N, const float* d_recon, const float* params, float* gr
     const long npo = (long)N * B.Hout * B.Wout, npi = (long)N * B.Hin * B.Win;
     // (blocks > 1: block 0 has an identity shortcut and reads the stem's materialised activation)
     const void* xin = i == 0 ? (cfg.blocks > 1 ? base + P.act0d : base + P.y0d) : base + dec[i - 1].out;
-    const float* xs = (i == 0 && cfg.blocks <= 1) ? bnf(dbn0, base, 2) : nullptr;
-    const float* xb = (i == 0 && cfg.blocks <= 1) ? bnf(dbn0, base, 3) : nullptr;
+    const float* xs = (i == 0 && cfg.blocks <= 1) ? r0.scale : nullptr;
+    const float* xb = (i == 0 && cfg.blocks <= 1) ? r0.shift : nullptr;
+    const BnRows r1 = ps.rows(B.b1), r2 = ps.rows(B.b2);
+    const Shortcut sc = ps.shortcut(B, xin);
     const int ds = i & 1;          // dy set of this block (see encoder_bwd)
     if (i + 2 <= nd - 1) MM_TRY(side_wait_mark(i + 2, s));
     const bool from_tail = tail_fused && i == nd - 1;
-    const void* ysp = B.identity ? xin : base + B.ys;
-    const float* ssc = B.identity ? ones(base) : bnf(B.bs, base, 2);
-    const float* ssh = B.identity ? zeros(base) : bnf(B.bs, base, 3);
     // an identity shortcut's gradient is the masked incoming gradient itself: it goes straight into the block-input gradient
     const long dyso = B.identity ? P.g[cur ^ 1] : P.dys[ds];
     if (from_tail) {
-      np = launch_tail_join_bwd_reduce(dt(), d_raw, params + tail.off, cfg.out_ch, N, Sd, Sd, bnf(B.b2, base, 2), bnf(B.b2, base, 3), bnf(B.bs, base, 2),
-                                       bnf(B.bs, base, 3), base + B.y2, base + B.ys, part, s, tail_wg_in_reduce ? wscratch_ : nullptr, store8 ? 1 : 0);
+      np = launch_tail_join_bwd_reduce(dt(), d_raw, params + tail.off, cfg.out_ch, N, Sd, Sd, r2.scale, r2.shift, sc.scale, sc.shift, base + B.y2,
+                                       sc.y, part, s, tail_wg_in_reduce ? ps.wscratch : nullptr, store8 ? 1 : 0);
       if (tail_wg_in_reduce && np > 0) {
         MM_TRY(side_fork(s));
-        MM_TRY(launch_tail_wgrad_finalize(wscratch_, np, grads + tail.off, wgrad_stream(s)));
+        MM_TRY(launch_tail_wgrad_finalize(ps.wscratch, np, grads + tail.off, wgrad_stream(s)));
       }
     } else if (jg)
-      np = launch_bn_bwd_reduce(dt(), base + P.g[cur], nullptr, nullptr, nullptr, base + B.y2, ysp, npo, B.C, part, s, nullptr, nullptr);
+      np = launch_bn_bwd_reduce(dt(), base + P.g[cur], nullptr, nullptr, nullptr, base + B.y2, sc.y, npo, B.C, part, s, nullptr, nullptr);
     else
-      np = launch_bn_bwd_reduce(dt(), base + P.g[cur], nullptr, bnf(B.b2, base, 2), bnf(B.b2, base, 3), base + B.y2, ysp, npo, B.C, part, s, ssc, ssh);
+      np = launch_bn_bwd_reduce(dt(), base + P.g[cur], nullptr, r2.scale, r2.shift, base + B.y2, sc.y, npo, B.C, part, s, sc.scale, sc.shift);
     MM_TRY(np);
-    if (B.identity) MM_TRY(bn_backward_coefs(B.b2, params, grads, base, np, 2, 0, (double)npo, s));
-    else MM_TRY(bn_backward_coefs_join(B.b2, B.bs, params, grads, base, np, (double)npo, s));
+    if (B.identity) MM_TRY(bn_backward_coefs(ps, B.b2, np, 2, 0, (double)npo, s));
+    else MM_TRY(bn_backward_coefs_join(ps, B.b2, B.bs, np, (double)npo, s));
     // The last up-block in one pass (conv_joinbwd.hip): dy2 / dys are produced row by row inside the kernel that consumes them -- both
     // ConvTranspose2d weight gradients, both data gradients, bn1's backward sums -- and never stored; conv1 (1x1) follows once bn1's
     // sums are final.
     if (from_tail && !B.identity && !B.c2.fp8 && !B.cs.fp8 && !B.c1.fp8 && B.Cin == 16 && join_bwd_stream_ok(dt(), cfg.out_ch, B.C, B.Hin, B.Hout)) {
       float* ws2 = reinterpret_cast<float*>(base + P.wscratch2);
       JoinBwdLaunch L;
-      L.d_raw = d_raw; L.w_tail = params + tail.off; L.y2 = base + B.y2; L.ys = base + B.ys;
-      L.ms2 = bnf(B.b2, base, 2); L.mb2 = bnf(B.b2, base, 3); L.mss = bnf(B.bs, base, 2); L.mbs = bnf(B.bs, base, 3);
-      L.A2 = bnf(B.b2, base, 4); L.B2 = bnf(B.b2, base, 5); L.C2 = bnf(B.b2, base, 6);
-      L.As = bnf(B.bs, base, 4); L.Bs = bnf(B.bs, base, 5); L.Cs = bnf(B.bs, base, 6);
-      L.y1 = base + B.y1; L.p1s = bnf(B.b1, base, 2); L.p1b = bnf(B.b1, base, 3);
-      L.wd2 = base + plan_.packed + B.c2.packD * (long)esz(); L.da1 = base + P.da1; L.part2 = ws2; L.bn_part = part;
-      L.xin = xin; L.pxs = xs; L.pxb = xb; L.wds = base + plan_.packed + B.cs.packD * (long)esz(); L.gin = base + P.g[cur ^ 1];
+      L.d_raw = d_raw; L.w_tail = params + tail.off; L.y2 = base + B.y2; L.ys = sc.y;
+      L.ms2 = r2.scale; L.mb2 = r2.shift; L.mss = sc.scale; L.mbs = sc.shift;
+      L.A2 = r2.A; L.B2 = r2.B; L.C2 = r2.C;
+      L.As = sc.A; L.Bs = sc.B; L.Cs = sc.C;
+      L.y1 = base + B.y1; L.p1s = r1.scale; L.p1b = r1.shift;
+      L.wd2 = ps.packed(B.c2.packD); L.da1 = base + P.da1; L.part2 = ws2; L.bn_part = part;
+      L.xin = xin; L.pxs = xs; L.pxb = xb; L.wds = ps.packed(B.cs.packD); L.gin = base + P.g[cur ^ 1];
       L.parts = ws2 + 1024L * 4096;                        // (at most 1024 blocks, one [16][16][16] partial image per conv each)
       L.N = N; L.f8in = store8 ? 1 : 0;
       const int nb = launch_join_bwd_stream(L, s);
       MM_TRY(nb);
-      auto reduce16 = [&](const float* parts, int nparts, const ConvW& w, int ntaps) {
-        WgradReduceArgs u; std::memset(&u, 0, sizeof(u));
-        u.part = parts; u.dW = grads + w.off; u.Ca = w.D0; u.Cb = w.D1; u.ntaps = ntaps; u.nparts = nparts;
-        u.Ca_valid = w.D0; u.Cb_valid = w.D1; u.sA = w.D1 * ntaps; u.sB = ntaps; u.scale = w.wscale;
-        for (int t = 0; t < ntaps; ++t) u.tap_off[t] = t;
-        return launch_wgrad_reduce(u, s);
-      };
-      MM_TRY(reduce16(L.part2, nb, B.c2, 16));
-      MM_TRY(reduce16(L.parts, nb, B.cs, 16));
-      MM_TRY(bn_backward_coefs(B.b1, params, grads, base, nb, 1, 0, (double)npi, s));
+      MM_TRY(reduce_wgrad_parts(ps, B.c2, L.part2, nb, 16, s));
+      MM_TRY(reduce_wgrad_parts(ps, B.cs, L.parts, nb, 16, s));
+      MM_TRY(bn_backward_coefs(ps, B.b1, nb, 1, 0, (double)npi, s));
       Conv1BwdLaunch C1;
-      C1.da1 = base + P.da1; C1.y1 = base + B.y1; C1.ms = bnf(B.b1, base, 2); C1.mb = bnf(B.b1, base, 3);
-      C1.A = bnf(B.b1, base, 4); C1.B = bnf(B.b1, base, 5); C1.C = bnf(B.b1, base, 6);
-      C1.xin = xin; C1.pxs = xs; C1.pxb = xb; C1.w1u = base + plan_.packed + B.c1.packU * (long)esz();
+      C1.da1 = base + P.da1; C1.y1 = base + B.y1; C1.ms = r1.scale; C1.mb = r1.shift;
+      C1.A = r1.A; C1.B = r1.B; C1.C = r1.C;
+      C1.xin = xin; C1.pxs = xs; C1.pxb = xb; C1.w1u = ps.packed(B.c1.packU);
       C1.gin = base + P.g[cur ^ 1]; C1.part = ws2; C1.nrows = (long)N * B.Hin;
       C1.mask_out = jg_block(i - 1) ? 1 : 0;
       g_masked = C1.mask_out != 0;
       const int nb1 = launch_conv1_bwd_stream(C1, s);
       MM_TRY(nb1);
-      {   // conv1: Conv2d weight (out = 16, in = Cin): partial images [out][in]
-        WgradReduceArgs u; std::memset(&u, 0, sizeof(u));
-        u.part = ws2; u.dW = grads + B.c1.off; u.Ca = B.c1.D0; u.Cb = B.c1.D1; u.ntaps = 1; u.nparts = nb1;
-        u.Ca_valid = B.c1.D0; u.Cb_valid = B.c1.D1; u.sA = B.c1.D1; u.sB = 1; u.scale = B.c1.wscale;
-        MM_TRY(launch_wgrad_reduce(u, s));
-      }
+      MM_TRY(reduce_wgrad_parts(ps, B.c1, ws2, nb1, 1, s));   // conv1: Conv2d weight (out = 16, in = Cin): partial images [out][in]
       MM_TRY(side_mark(i));
       cur ^= 1;
       continue;
@@ -1111,23 +1068,19 @@ int Net::decoder_bwd(int N, const float* d_recon, const float* params, float* gr
     if (jg) {
       // (no apply pass: the two fused passes below evaluate dy2 / dys from g[cur], y2 / ys and the coefficients)
     } else if (from_tail)
-      MM_TRY(launch_tail_join_bwd_apply(dt(), d_raw, params + tail.off, cfg.out_ch, N, Sd, Sd, bnf(B.b2, base, 2), bnf(B.b2, base, 3), bnf(B.bs, base, 2),
-                                        bnf(B.bs, base, 3), base + B.y2, bnf(B.b2, base, 4), bnf(B.b2, base, 5), bnf(B.b2, base, 6), base + P.dy2[ds],
-                                        base + B.ys, bnf(B.bs, base, 4), bnf(B.bs, base, 5), bnf(B.bs, base, 6), base + P.dys[ds], s));
+      MM_TRY(launch_tail_join_bwd_apply(dt(), d_raw, params + tail.off, cfg.out_ch, N, Sd, Sd, r2.scale, r2.shift, sc.scale, sc.shift, base + B.y2,
+                                        r2.A, r2.B, r2.C, base + P.dy2[ds], sc.y, sc.A, sc.B, sc.C, base + P.dys[ds], s));
     else
-      MM_TRY(launch_bn_bwd_apply(dt(), base + P.g[cur], nullptr, bnf(B.b2, base, 2), bnf(B.b2, base, 3), base + B.y2, bnf(B.b2, base, 4), bnf(B.b2, base, 5),
-                                 bnf(B.b2, base, 6), base + P.dy2[ds], ysp, B.identity ? ones(base) : bnf(B.bs, base, 4),
-                                 B.identity ? zeros(base) : bnf(B.bs, base, 5), B.identity ? zeros(base) : bnf(B.bs, base, 6), base + dyso, npo, B.C, s,
-                                 ssc, ssh));
+      MM_TRY(launch_bn_bwd_apply(dt(), base + P.g[cur], nullptr, r2.scale, r2.shift, base + B.y2, r2.A, r2.B, r2.C, base + P.dy2[ds], sc.y, sc.A,
+                                 sc.B, sc.C, base + dyso, npo, B.C, s, sc.scale, sc.shift));
     hipStream_t wsm = wgrad_stream(s);
     MM_TRY(side_fork(s));
     bool fuse_c2 = false, fuse_cs = false;
     int np_b1 = 0;                       // rows of bn1's backward sums when the fused pass has left them in `part`
     if (B.identity) {
       // conv2 (3x3 Conv2d): wgrad(P = dy2, G = a1 with BN+ReLU prologue); dgrad -> d_a1
-      MM_TRY(run_wgrad(B.c2, N, base + P.dy2[ds], B.Hout, B.Wout, nullptr, nullptr, base + B.y1, B.Hin, B.Win, bnf(B.b1, base, 2), bnf(B.b1, base, 3),
-                       grads, wsm));
-      MM_TRY(run_up(B.c2, base, N, base + P.dy2[ds], B.Hout, B.Wout, base + P.da1, B.Hin, B.Win, nullptr, nullptr, 0, nullptr, 0, s));
+      MM_TRY(run_wgrad(ps, B.c2, base + P.dy2[ds], B.Hout, B.Wout, nullptr, nullptr, base + B.y1, B.Hin, B.Win, r1.scale, r1.shift, wsm));
+      MM_TRY(run_up(ps, B.c2, base + P.dy2[ds], B.Hout, B.Wout, base + P.da1, B.Hin, B.Win, nullptr, nullptr, 0, nullptr, 0, s));
     } else {
       // conv2 (ConvT k4 s2): wgrad(P = a1 small side with BN+ReLU prologue, G = dy2 large side); dgrad = strided conv -> d_a1
       // Where the shape allows (uplayer4 / uplayer5: 16 output channels, 16x16 -> 32x32 or 32x32 -> 64x64, bf16) dgrad and wgrad of a ConvT
@@ -1137,44 +1090,40 @@ int Net::decoder_bwd(int N, const float* d_recon, const float* params, float* gr
       fuse_cs = !B.cs.fp8 && op_bwd_fusable(dt(), geom(B.cs), N, B.Hin, B.Win, B.Hout, B.Wout) && B.C == 16;
       float* wsc2 = reinterpret_cast<float*>(base + P.wscratch2);
       if (!fuse_c2)
-        MM_TRY(run_wgrad(B.c2, N, base + B.y1, B.Hin, B.Win, bnf(B.b1, base, 2), bnf(B.b1, base, 3), base + P.dy2[ds], B.Hout, B.Wout, nullptr,
-                         nullptr, grads, wsm));
-      if (!fuse_cs) MM_TRY(run_wgrad(B.cs, N, xin, B.Hin, B.Win, xs, xb, base + P.dys[ds], B.Hout, B.Wout, nullptr, nullptr, grads, wsm));
+        MM_TRY(run_wgrad(ps, B.c2, base + B.y1, B.Hin, B.Win, r1.scale, r1.shift, base + P.dy2[ds], B.Hout, B.Wout, nullptr, nullptr, wsm));
+      if (!fuse_cs) MM_TRY(run_wgrad(ps, B.cs, xin, B.Hin, B.Win, xs, xb, base + P.dys[ds], B.Hout, B.Wout, nullptr, nullptr, wsm));
       if (jg && !(fuse_c2 && fuse_cs)) { set_error("decoder_bwd: the join-gradient form needs both fused passes"); return MMVAE_ERR_UNSUPPORTED; }
       if (fuse_c2) {
         // ... and bn1's backward sums come out of the same pass (the data gradient is in registers, y1 is the pass's P operand)
-        const JoinGrad j2{base + B.y2, bnf(B.b2, base, 4), bnf(B.b2, base, 5), bnf(B.b2, base, 6)};
-        const int rcf = op_run_bwd_fused(dt(), geom(B.c2), N, base + B.y1, B.Hin, B.Win, bnf(B.b1, base, 2), bnf(B.b1, base, 3), 1,
-                                         jg ? base + P.g[cur] : base + P.dy2[ds],
-                                         B.Hout, B.Wout, base + plan_.packed + B.c2.packD * (long)esz(), base + P.da1, nullptr, nullptr,
-                                         grads + B.c2.off, s, wsc2, B.c2.wscale, B.C == 16 ? part : nullptr, nullptr, 1.f, jg ? &j2 : nullptr);
+        const JoinGrad j2{base + B.y2, r2.A, r2.B, r2.C};
+        const int rcf = op_run_bwd_fused(dt(), geom(B.c2), N, base + B.y1, B.Hin, B.Win, r1.scale, r1.shift, 1,
+                                         jg ? base + P.g[cur] : base + P.dy2[ds], B.Hout, B.Wout, ps.packed(B.c2.packD), base + P.da1, nullptr,
+                                         nullptr, grads + B.c2.off, s, wsc2, B.c2.wscale, B.C == 16 ? part : nullptr, nullptr, 1.f, jg ? &j2 : nullptr);
         if (rcf <= 0) { if (rcf == 0) set_error("decoder_bwd: fused backward of %s not taken", "conv2"); return rcf < 0 ? rcf : MMVAE_ERR_UNSUPPORTED; }
         if (B.C == 16) np_b1 = rcf;
       } else
-        MM_TRY(run_down(B.c2, base, N, base + P.dy2[ds], B.Hout, B.Wout, base + P.da1, B.Hin, B.Win, nullptr, nullptr, 0, nullptr, 0, dt(), s));
+        MM_TRY(run_down(ps, B.c2, base + P.dy2[ds], B.Hout, B.Wout, base + P.da1, B.Hin, B.Win, nullptr, nullptr, 0, nullptr, 0, dt(), s));
     }
-    np = np_b1 > 0 ? np_b1 : launch_bn_bwd_reduce(dt(), base + P.da1, nullptr, bnf(B.b1, base, 2), bnf(B.b1, base, 3), base + B.y1, nullptr, npi, B.C, part, s);
+    np = np_b1 > 0 ? np_b1 : launch_bn_bwd_reduce(dt(), base + P.da1, nullptr, r1.scale, r1.shift, base + B.y1, nullptr, npi, B.C, part, s);
     MM_TRY(np);
-    MM_TRY(bn_backward_coefs(B.b1, params, grads, base, np, 1, 0, (double)npi, s));
-    MM_TRY(launch_bn_bwd_apply(dt(), base + P.da1, nullptr, bnf(B.b1, base, 2), bnf(B.b1, base, 3), base + B.y1, bnf(B.b1, base, 4),
-                               bnf(B.b1, base, 5), bnf(B.b1, base, 6), base + P.dy1[ds], nullptr, nullptr, nullptr, nullptr, nullptr, npi,
-                               B.C, s));
+    MM_TRY(bn_backward_coefs(ps, B.b1, np, 1, 0, (double)npi, s));
+    MM_TRY(launch_bn_bwd_apply(dt(), base + P.da1, nullptr, r1.scale, r1.shift, base + B.y1, r1.A, r1.B, r1.C, base + P.dy1[ds], nullptr, nullptr,
+                               nullptr, nullptr, nullptr, npi, B.C, s));
     // conv1 (1x1): wgrad(P = dy1, G = xin); upsample (ConvT): wgrad(P = xin, G = dys)
     MM_TRY(side_fork(s));
     // (with the fused shortcut pass below the 1x1 conv's weight gradient comes out of that pass: dy1 and the block input are its rows)
-    if (!fuse_cs) MM_TRY(run_wgrad(B.c1, N, base + P.dy1[ds], B.Hin, B.Win, nullptr, nullptr, xin, B.Hin, B.Win, xs, xb, grads, wsm));
+    if (!fuse_cs) MM_TRY(run_wgrad(ps, B.c1, base + P.dy1[ds], B.Hin, B.Win, nullptr, nullptr, xin, B.Hin, B.Win, xs, xb, wsm));
     MM_TRY(side_mark(i));
     if (B.identity)     // d_xin already holds the shortcut's share: the 1x1 conv's data gradient is added to it
-      MM_TRY(run_up(B.c1, base, N, base + P.dy1[ds], B.Hin, B.Win, base + P.g[cur ^ 1], B.Hin, B.Win, nullptr, nullptr, 0, nullptr, 1, s));
+      MM_TRY(run_up(ps, B.c1, base + P.dy1[ds], B.Hin, B.Win, base + P.g[cur ^ 1], B.Hin, B.Win, nullptr, nullptr, 0, nullptr, 1, s));
     else if (fuse_cs) {  // shortcut ConvT: weight gradient + data gradient + the 1x1 conv's share (dy1 (x) w1) and ITS weight gradient, one pass over dys
-      const JoinGrad js{base + B.ys, bnf(B.bs, base, 4), bnf(B.bs, base, 5), bnf(B.bs, base, 6)};
+      const JoinGrad js{sc.y, sc.A, sc.B, sc.C};
       const int rcf = op_run_bwd_fused(dt(), geom(B.cs), N, xin, B.Hin, B.Win, xs, xb, 1, jg ? base + P.g[cur] : base + P.dys[ds], B.Hout, B.Wout,
-                                       base + plan_.packed + B.cs.packD * (long)esz(), base + P.g[cur ^ 1], base + P.dy1[ds],
-                                       base + plan_.packed + B.c1.packU * (long)esz(), grads + B.cs.off, s,
+                                       ps.packed(B.cs.packD), base + P.g[cur ^ 1], base + P.dy1[ds], ps.packed(B.c1.packU), grads + B.cs.off, s,
                                        reinterpret_cast<float*>(base + P.wscratch2), B.cs.wscale, nullptr, grads + B.c1.off, B.c1.wscale, jg ? &js : nullptr);
       if (rcf <= 0) { if (rcf == 0) set_error("decoder_bwd: fused backward of %s not taken", "upsample"); return rcf < 0 ? rcf : MMVAE_ERR_UNSUPPORTED; }
     } else              // one kernel: the 1x1 conv's data gradient (dy1, already on this block's input grid) is a second source of the shortcut's
-      MM_TRY(run_down(B.cs, base, N, base + P.dys[ds], B.Hout, B.Wout, base + P.g[cur ^ 1], B.Hin, B.Win, nullptr, nullptr, 0, nullptr, 0, dt(), s,
+      MM_TRY(run_down(ps, B.cs, base + P.dys[ds], B.Hout, B.Wout, base + P.g[cur ^ 1], B.Hin, B.Win, nullptr, nullptr, 0, nullptr, 0, dt(), s,
                       &B.c1, base + P.dy1[ds]));
     cur ^= 1;
   }
@@ -1183,15 +1132,15 @@ int Net::decoder_bwd(int N, const float* d_recon, const float* params, float* gr
   const int ds = 1;
   {
     const long npix = (long)N * 4;
-    np = launch_bn_bwd_reduce(dt(), base + P.g[cur], nullptr, bnf(dbn0, base, 2), bnf(dbn0, base, 3), base + P.y0d, nullptr, npix, 128, part, s);
+    np = launch_bn_bwd_reduce(dt(), base + P.g[cur], nullptr, r0.scale, r0.shift, base + P.y0d, nullptr, npix, 128, part, s);
     MM_TRY(np);
-    MM_TRY(bn_backward_coefs(dbn0, params, grads, base, np, 1, 0, (double)npix, s));
-    MM_TRY(launch_bn_bwd_apply(dt(), base + P.g[cur], nullptr, bnf(dbn0, base, 2), bnf(dbn0, base, 3), base + P.y0d, bnf(dbn0, base, 4),
-                               bnf(dbn0, base, 5), bnf(dbn0, base, 6), base + P.dy1[ds], nullptr, nullptr, nullptr, nullptr, nullptr, npix, 128, s));
+    MM_TRY(bn_backward_coefs(ps, dbn0, np, 1, 0, (double)npix, s));
+    MM_TRY(launch_bn_bwd_apply(dt(), base + P.g[cur], nullptr, r0.scale, r0.shift, base + P.y0d, r0.A, r0.B, r0.C, base + P.dy1[ds], nullptr,
+                               nullptr, nullptr, nullptr, nullptr, npix, 128, s));
     MM_TRY(side_fork(s));
-    MM_TRY(run_wgrad(dstem, N, base + P.enc_t, 1, 1, nullptr, nullptr, base + P.dy1[ds], 2, 2, nullptr, nullptr, grads, wgrad_stream(s)));
+    MM_TRY(run_wgrad(ps, dstem, base + P.enc_t, 1, 1, nullptr, nullptr, base + P.dy1[ds], 2, 2, nullptr, nullptr, wgrad_stream(s)));
     if (d_enc) {
-      MM_TRY(run_down(dstem, base, N, base + P.dy1[ds], 2, 2, base + P.dh, 1, 1, nullptr, nullptr, 0, nullptr, 0, dt(), s));
+      MM_TRY(run_down(ps, dstem, base + P.dy1[ds], 2, 2, base + P.dh, 1, 1, nullptr, nullptr, 0, nullptr, 0, dt(), s));
       MM_TRY(launch_convert(dt(), DT_F32, base + P.dh, d_enc, (long)N * cfg.z, s));
     }
     if (!defer_join_) MM_TRY(side_join(s));

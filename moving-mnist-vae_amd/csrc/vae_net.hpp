@@ -2,6 +2,8 @@
 // Mirrors the layer structure of the reference model.py (VAE_Encoder :88-150, VAE_Decoder :153-209,
 // BasicBlock :23-55, DeconvBottleneck :57-85) but owns no tensors: parameters, BN buffers, gradients and
 // the activation workspace are caller-provided device pointers.
+// Each entry point binds those pointers once into a Net::Pass; the helpers take the Pass and the call sites name only what varies
+// (layer, operands, stream).  BatchNorm scratch rows and packed weights are reached by name: Pass::rows(), Pass::shortcut(), Pass::packed().
 #pragma once
 #include <string>
 #include <vector>
@@ -12,7 +14,8 @@
 
 namespace mmvae {
 
-struct NetCfg { int in_ch, z, out_ch, S, need_logvar, dtype, blocks, fp8; };   // fp8: forward convs of the deep layers on the fp8 MFMA   // blocks: residual blocks per stage (reference: 1)
+// blocks: residual blocks per stage (reference: 1); fp8: forward convs of the deep layers on the fp8 MFMA
+struct NetCfg { int in_ch, z, out_ch, S, need_logvar, dtype, blocks, fp8; };
 
 enum EntryKind : int { EK_PARAM = 0, EK_BN_F32 = 1, EK_BN_I64 = 2 };
 struct Entry { std::string name; int ndim; int shape[4]; int kind; long offset; };
@@ -24,7 +27,15 @@ struct Entry { std::string name; int ndim; int shape[4]; int kind; long offset; 
 // the static power-of-two weight scale wscale; its stored output is y' = wscale * y, which the BatchNorm behind it absorbs exactly
 // (BnFinalizeArgs::in_scale); the backward pass uses the bf16 kernels on wscale * w and scales the weight gradient by wscale.
 struct ConvW { long off; int D0, D1, k, s, p; long packD, packU; int Hl = 0; /* large-side map (square) */ bool tr = false; /* ConvTranspose2d: forward = up */ bool fp8 = false; float wscale = 1.f; };
-struct Bn { long g_off, b_off, rm_off, rv_off; int nbt_idx; int C; long ws; /* float offset of this BN's 7*C scratch */ };
+struct Bn {
+  long g_off, b_off, rm_off, rv_off; int nbt_idx; int C; long ws;   // ws: float offset of this BN's scratch in Plan::bnws
+  // the scratch: kRows rows of row_floats() floats -- batch statistics, the folded forward affine, the coefficients of dx = A*g + B*y + C
+  enum Row { MEAN, ISTD, SCALE, SHIFT, COEF_A, COEF_B, COEF_C, kRows };
+  long row_floats() const { return (C + 3L) / 4 * 4; }
+  long row(Row r) const { return ws + r * row_floats(); }
+  long scratch_floats() const { return kRows * row_floats(); }
+};
+struct BnRows { float *mean, *istd, *scale, *shift, *A, *B, *C; };   // device pointers to a Bn's scratch rows
 
 struct Block {   // encoder BasicBlock or decoder DeconvBottleneck (both: main c1->c2, shortcut cs, join)
   ConvW c1, c2, cs; Bn b1, b2, bs;
@@ -49,9 +60,9 @@ struct Plan {
                                                          // weight gradients on the side stream may lag one block behind)
   long wscratch;                                         // partial-image scratch of the weight gradients (serialised on the side stream)
   long wscratch2;                                        // partial images of the fused dgrad+wgrad passes (caller's stream)
-  long stem_R, stem_gram;
+  long stem_R, stem_gram;                                // stem backward: patch gram matrix (1024 doubles) and its per-block partials
   long cvec;                                             // constants: 256 ones, 256 zeros (identity shortcuts as a unit BatchNorm)
-  long act0d;                                            // blocks > 1: relu(bn(decoder stem)) materialised (an identity shortcut needs it)                                // stem backward: patch gram matrix (1024 doubles) and its per-block partials
+  long act0d;                                            // blocks > 1: relu(bn(decoder stem)) materialised (an identity shortcut needs it)
   long enc_ws_end;
 };
 
@@ -101,7 +112,33 @@ class Net {
 
  private:
   Plan plan_;
-  float* wscratch_ = nullptr;
+  // A block's shortcut operand at its join: the shortcut conv's output under its BatchNorm (B.ys, B.bs), or -- identity shortcut
+  // (model.py:40,52) -- the block input itself under a unit BatchNorm (scale 1, shift 0; backward A = 1, B = C = 0)
+  struct Shortcut { const void* y; const float *scale, *shift, *A, *B, *C; };
+  // What one entry-point call binds once: the plan, the caller's buffers and the workspace regions every helper needs
+  struct Pass {
+    const Plan* P; char* base; const float* params; float* grads; float* bnbuf; long long* nbt; int N; bool training;
+    float* part;              // reduction partials (second half at + kPartialFloats: the side stream's)
+    float* wscratch;          // partial-image scratch of the weight gradients on the side stream
+    size_t esz;
+    BnRows rows(const Bn& bn) const {
+      float* f = reinterpret_cast<float*>(base + P->bnws);
+      return BnRows{f + bn.row(Bn::MEAN), f + bn.row(Bn::ISTD), f + bn.row(Bn::SCALE), f + bn.row(Bn::SHIFT),
+                    f + bn.row(Bn::COEF_A), f + bn.row(Bn::COEF_B), f + bn.row(Bn::COEF_C)};
+    }
+    // packed-weight address of a slot: a ConvW's packD / packU, or one of the boundary layers' slots (stem_pack, head_pack_*, ...)
+    char* packed(long slot) const { return base + P->packed + slot * (long)esz; }
+    const float* ones() const { return reinterpret_cast<const float*>(base + P->cvec); }
+    const float* zeros() const { return ones() + 256; }
+    Shortcut shortcut(const Block& B, const void* xin) const {
+      if (B.identity) return Shortcut{xin, ones(), zeros(), ones(), zeros(), zeros()};
+      const BnRows r = rows(B.bs);
+      return Shortcut{base + B.ys, r.scale, r.shift, r.A, r.B, r.C};
+    }
+  };
+  // plan(N) + the workspace-size check of every entry point; enqueues nothing
+  int begin_pass(Pass& ps, int N, void* ws, size_t ws_bytes, const float* params = nullptr, float* grads = nullptr, float* bnbuf = nullptr,
+                 long long* nbt = nullptr, bool training = false);
   // weight gradients run on a side stream, concurrently with the dgrad / BatchNorm-backward chain of the same block
   // (the deep-layer kernels are latency-bound and leave most CUs idle)
   static constexpr int kForkEvents = 192;
@@ -123,35 +160,36 @@ class Net {
   Bn add_bn(const std::string& prefix, int C);
   void add_entry(const std::string& name, std::initializer_list<int> shape, int kind, long off);
 
-  int packs_enc_fwd(const float* params, char* base, hipStream_t s);
-  int packs_enc_bwd(const float* params, char* base, hipStream_t s);
-  int packs_dec_fwd(const float* params, char* base, hipStream_t s);
-  int packs_dec_bwd(const float* params, char* base, bool need_denc, hipStream_t s);
+  int packs_enc_fwd(const Pass& ps, hipStream_t s);
+  int packs_enc_bwd(const Pass& ps, hipStream_t s);
+  int packs_dec_fwd(const Pass& ps, hipStream_t s);
+  int packs_dec_bwd(const Pass& ps, bool need_denc, hipStream_t s);
   // fragment-major packing (deep2_conv_kernel) of the down / up form of a conv at its place in the net
   int frag_down(const ConvW& w) const;
   int frag_up(const ConvW& w) const;
-  int pack_down(const ConvW& w, const float* params, char* base, hipStream_t s);
-  int pack_up(const ConvW& w, const float* params, char* base, hipStream_t s);
+  int pack_down(const Pass& ps, const ConvW& w, hipStream_t s);
+  int pack_up(const Pass& ps, const ConvW& w, hipStream_t s);
   // w2 / x2 (optional): the 1x1 conv whose "up" form over x2 (a tensor on the small-side grid) is added in the same kernel
-  int run_down(const ConvW& w, char* base, int N, const void* L, int Hl, int Wl, void* S, int Hs, int Ws,
+  int run_down(const Pass& ps, const ConvW& w, const void* L, int Hl, int Wl, void* S, int Hs, int Ws,
                const float* pro_s, const float* pro_b, int relu, float* stats, int accumulate, int out_dt, hipStream_t s,
                const ConvW* w2 = nullptr, const void* x2 = nullptr);
-  int run_up(const ConvW& w, char* base, int N, const void* S, int Hs, int Ws, void* L, int Hl, int Wl,
+  int run_up(const Pass& ps, const ConvW& w, const void* S, int Hs, int Ws, void* L, int Hl, int Wl,
              const float* pro_s, const float* pro_b, int relu, float* stats, int accumulate, hipStream_t s,
              const ConvW* w2 = nullptr, const void* x2 = nullptr);
-  int run_wgrad(const ConvW& w, int N, const void* P, int Hs, int Ws, const float* proP_s, const float* proP_b,
-                const void* G, int Hl, int Wl, const float* proG_s, const float* proG_b, float* grads, hipStream_t s);
+  int run_wgrad(const Pass& ps, const ConvW& w, const void* P, int Hs, int Ws, const float* proP_s, const float* proP_b,
+                const void* G, int Hl, int Wl, const float* proG_s, const float* proG_b, hipStream_t s);
+  // sum of the partial images [D0][D1][ntaps] a fused backward pass left at `parts` -> w's weight gradient
+  int reduce_wgrad_parts(const Pass& ps, const ConvW& w, const float* parts, int nparts, int ntaps, hipStream_t s);
   // Last up-block forward as one kernel (join + tail conv, the joined activation is never stored); the backward then needs the
   // recomputing wgrad and the recomputing join backward.  Shapes it does not take keep join -> conv.
   bool tail_fwd_fused() const;
   bool stem_bwd_fused() const;       // stem backward as one pass (stem_bwd.hip)
   bool stem_dg_fused() const;        // ... with encoder.layer1's data gradient recomputed inside it (no stored gradient of the stem's output)
-  long stem_dy1_ = 0, stem_dys_ = 0; // workspace offsets of layer1's dy1 / dys of the running backward pass
   // decoder_bwd leaves its weight gradients running on the side stream; encoder_bwd (or join()) orders them before the caller's stream
   bool defer_join_ = false;
   int (*ar_fn_)(float*, long long, void*, void*) = nullptr; void* ar_user_ = nullptr; int ar_world_ = 1;
   Comm* comm_ = nullptr; Comm* comm_side_ = nullptr;
-  int sync_rows(char* base, const float* partials, int nparts, int width, hipStream_t s, float** out, int row_stride = 0);
+  int sync_rows(const Pass& ps, const float* partials, int nparts, int width, hipStream_t s, float** out, int row_stride = 0);
  public:
   void set_defer_join(bool v) { defer_join_ = v; }
   // the join-gradient form of a 16-wide block's backward (decoder_bwd: masked gradient handed down, dy evaluated by the consumers' loaders);
@@ -169,24 +207,19 @@ class Net {
   hipStream_t side() const { return side_state_ == 1 ? side_ : nullptr; }                       // nullptr: one stream
   hipStream_t fork(hipStream_t s) { return side_fork(s) == MMVAE_OK ? wgrad_stream(s) : s; }   // the side stream, ordered behind s
  private:
-  int bn_train(const Bn& bn, const float* params, float* bnbuf, long long* nbt, char* base, int nparts, double count, hipStream_t s, long part_off = 0,
-               float in_scale = 1.f);
-  int bn_eval(const Bn& bn, const float* params, const float* bnbuf, char* base, hipStream_t s, float in_scale = 1.f);
-  // eval mode: all BatchNorms of the encoder (which = 0) / decoder (1) folded to (scale, shift) in one launch; bn_eval() is then a no-op
-  int fold_bn_eval(int which, const float* params, const float* bnbuf, char* base, hipStream_t s);
+  // a forward BatchNorm behind the conv that left `nparts` rows of statistics at ps.part + part_off: training finalizes them into the
+  // rows (and the running statistics); eval mode only checks that fold_bn_eval() has written (scale, shift)
+  int bn_fwd(const Pass& ps, const Bn& bn, int nparts, double count, hipStream_t s, long part_off = 0, float in_scale = 1.f);
+  // eval mode: all BatchNorms of the encoder (which = 0) / decoder (1) folded to (scale, shift) in one launch
+  int fold_bn_eval(const Pass& ps, int which, hipStream_t s);
   bool l1_dgrad_stream() const;
   long l1c2_flip = 0;
   bool eval_folded_ = false;
   bool store8 = false;          // fp8 mode: the last up-block's branch outputs are stored as e4m3 bytes (see the constructor)
-  float* bnf(const Bn& bn, char* base, int which) const;   // 0 mean 1 istd 2 scale 3 shift 4 A 5 B 6 C
-  const float* ones(char* base) const { return reinterpret_cast<const float*>(base + plan_.cvec); }
-  const float* zeros(char* base) const { return reinterpret_cast<const float*>(base + plan_.cvec) + 256; }
-  int fill_consts(char* base, hipStream_t s);
-  int bn_backward_coefs(const Bn& bn, const float* params, float* grads, char* base, int nparts, int ny, int which, double count,
-                        hipStream_t s, float* dbias_conv = nullptr);
-  BnBwdFinalizeArgs bwd_finalize_args(const Bn& bn, const float* params, float* grads, char* base, const float* partials, int nparts, int ny,
-                                      int which, double count) const;
-  int bn_backward_coefs_join(const Bn& b2, const Bn& bs, const float* params, float* grads, char* base, int nparts, double count, hipStream_t s);
+  int fill_consts(const Pass& ps, hipStream_t s);
+  int bn_backward_coefs(const Pass& ps, const Bn& bn, int nparts, int ny, int which, double count, hipStream_t s, float* dbias_conv = nullptr);
+  BnBwdFinalizeArgs bwd_finalize_args(const Pass& ps, const Bn& bn, const float* partials, int nparts, int ny, int which, double count) const;
+  int bn_backward_coefs_join(const Pass& ps, const Bn& b2, const Bn& bs, int nparts, double count, hipStream_t s);
 };
 
 }  // namespace mmvae
