@@ -254,6 +254,30 @@ MMVAE_API int mmvae_kmeans1d_fit(const uint64_t* counts, int q, double* centres,
  * labels (utils.py:298-299: main.py's data_mean / data_std, unrounded).  ratios, label_mean, label_std may be NULL. */
 MMVAE_API int mmvae_quantiser_stats(const uint64_t* counts, const float* centres, int q, uint8_t* lut, double* ratios, double* label_mean,
                           double* label_std);
+/* The resize branch of the input transform (choose_transformer, main.py:33-38: ToPILImage -> Resize(S) -> ToTensor -> kmeans.predict).
+ * transforms.Resize is Pillow's 8-bit antialiased bilinear resample; a byte that is off by one next to a k-means boundary is another
+ * label, so the two calls below reproduce Pillow's bytes exactly.
+ * HOST function, every pointer host memory: the taps of ONE axis, in_size -> out_size, both in [1, 128] (else MMVAE_ERR_ARG), computed as
+ * Pillow's precompute_coeffs / normalize_coeffs_8bpc do (f64, triangle filter of support max(in / out, 1), weights divided by their
+ * sum, rounded to 22-bit fixed point).  *ksize = taps per output.  bounds [out_size][2] = {first input index, tap count <= ksize};
+ * coeffs [out_size][ksize], zero behind the tap count.  bounds == coeffs == NULL: only *ksize is written (size the buffers with it).
+ * A pass is out = clamp((2^21 + sum_x pixel[first + x] * coeffs[x]) >> 22, 0, 255); int32 suffices. */
+MMVAE_API int mmvae_resample_coeffs(int in_size, int out_size, int* ksize, int32_t* bounds, int32_t* coeffs);
+/* Resize + mmvae_quantise_normalise in one launch.  n_frames uint8 planes of in_h x in_w (rows contiguous, planes frame_stride_bytes
+ * apart, any alignment: 16-byte aligned frames and stride take the vector loads) are resized to out_h x out_w as Pillow mode-L images --
+ * the horizontal pass along in_w first, uint8 rounding behind each pass -- then quantised by mmvae_quantise_normalise's own f32 rule:
+ * for the same resized bytes the outputs equal that call's bit for bit.  Plane p is plane p % frames_per_clip of clip
+ * clip_index[p / frames_per_clip] (device int64, a gather of whole clips from a resident dataset; the CALLER keeps every index inside
+ * the buffer), or of clip p / frames_per_clip when clip_index is NULL (frames_per_clip = 1: plane p).  h_* are the DEVICE copies of
+ * mmvae_resample_coeffs(in_w, out_w), v_* of (in_h, out_h); h_ksize / v_ksize must be the values that call returns.  centres: q f32,
+ * needed for labels or image.  Outputs, dense [n_frames][out_h][out_w], each may be NULL but not all three (MMVAE_ERR_ARG): labels
+ * int64, image = ((float)label - mean) / stdv f32, resized uint8 (the bytes themselves).  n_frames == 0 is a no-op.  No atomics: the
+ * same bits every run. */
+MMVAE_API int mmvae_resize_quantise_normalise(const uint8_t* frames, int64_t frame_stride_bytes, const int64_t* clip_index,
+                                              int frames_per_clip, int64_t n_frames, int in_h, int in_w, int out_h, int out_w,
+                                              const int32_t* h_bounds, const int32_t* h_coeffs, int h_ksize, const int32_t* v_bounds,
+                                              const int32_t* v_coeffs, int v_ksize, const float* centres, int q, float mean, float stdv,
+                                              int64_t* labels, float* image, uint8_t* resized, void* stream);
 /* torch.optim.Adam defaults (main.py:468) over a flat buffer: bc1 = 1-beta1^t, bc2_sqrt = sqrt(1-beta2^t);
  * grad_scale multiplies the gradient first (1/world_size after a sum all-reduce). */
 MMVAE_API int mmvae_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,

@@ -68,6 +68,9 @@ PROTOTYPES = {
     "mmvae_u8_histogram": (c_int, [P, c_int64, P, c_int64, P, P]),
     "mmvae_kmeans1d_fit": (c_int, [P, c_int, P, P]),
     "mmvae_quantiser_stats": (c_int, [P, P, c_int, P, P, P, P]),
+    "mmvae_resample_coeffs": (c_int, [c_int, c_int, POINTER(c_int), P, P]),
+    "mmvae_resize_quantise_normalise": (c_int, [P, c_int64, P, c_int, c_int64, c_int, c_int, c_int, c_int, P, P, c_int, P, P, c_int, P, c_int,
+                                                c_float, c_float, P, P, P, P]),
     "mmvae_adam_step": (c_int, [P, P, P, P, c_int64, c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_float, P]),
     "mmvae_adam_step_dev": (c_int, [P, P, P, P, c_int64, c_float, c_float, c_float, c_float, c_float, P, c_float, P]),
     "mmvae_grad_norm_sq": (c_int, [P, c_int64, c_float, P, P, P]),

@@ -6,6 +6,7 @@
 #include "conv_ops.hpp"
 #include "pixel_net.hpp"
 #include "quantiser_fit.hpp"
+#include "resample.hpp"
 #include "vae_net.hpp"
 
 namespace mmvae { const char* last_error(); }
@@ -323,6 +324,18 @@ int mmvae_kmeans1d_fit(const uint64_t* counts, int q, double* centres, double* i
 int mmvae_quantiser_stats(const uint64_t* counts, const float* centres, int q, uint8_t* lut, double* ratios, double* label_mean,
                           double* label_std) {
   return quantiser_stats(counts, centres, q, lut, ratios, label_mean, label_std);
+}
+int mmvae_resample_coeffs(int in_size, int out_size, int* ksize, int32_t* bounds, int32_t* coeffs) {
+  return resample_coeffs(in_size, out_size, ksize, bounds, coeffs);
+}
+int mmvae_resize_quantise_normalise(const uint8_t* frames, int64_t frame_stride_bytes, const int64_t* clip_index, int frames_per_clip,
+                                    int64_t n_frames, int in_h, int in_w, int out_h, int out_w, const int32_t* h_bounds,
+                                    const int32_t* h_coeffs, int h_ksize, const int32_t* v_bounds, const int32_t* v_coeffs, int v_ksize,
+                                    const float* centres, int q, float mean, float stdv, int64_t* labels, float* image, uint8_t* resized,
+                                    void* st) {
+  return launch_resize_quantise_normalise(frames, (long)frame_stride_bytes, reinterpret_cast<const long long*>(clip_index), frames_per_clip,
+                                          (long)n_frames, in_h, in_w, out_h, out_w, h_bounds, h_coeffs, h_ksize, v_bounds, v_coeffs, v_ksize,
+                                          centres, q, mean, stdv, reinterpret_cast<long long*>(labels), image, resized, S(st));
 }
 int mmvae_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd, float bc1,
                     float bc2_sqrt, float grad_scale, void* st) {

@@ -129,6 +129,17 @@ __device__ __forceinline__ void block_sum(float (&v)[NV], float* smem) {
   }
 }
 
+// ---- pixel quantiser ------------------------------------------------------------
+// kmeans.predict of one byte (main.py:25) in f32: x = b / 255, smallest squared distance, the lowest index wins a tie.  The one
+// definition behind quantise_normalise_kernel and the label table of the resize kernel; quantiser_fit.cpp repeats it on the host.
+__device__ __forceinline__ int quantise_byte(unsigned char b, const float* __restrict__ centres, int q) {
+  const float x = (float)b / 255.0f;
+  int best = 0;
+  float bd = (x - centres[0]) * (x - centres[0]);
+  for (int k = 1; k < q; ++k) { const float d = (x - centres[k]) * (x - centres[k]); if (d < bd) { bd = d; best = k; } }
+  return best;
+}
+
 // ---- error plumbing (host); the MMVAE_* codes come from the public header
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);

@@ -405,6 +405,13 @@ int launch_quantise_normalise(const unsigned char* frames, long n, const float* 
 // [0, n_clips * clip_bytes) with clip_index == nullptr (quantiser.hip); any alignment of frames and clip_bytes
 int launch_u8_histogram(const unsigned char* frames, long clip_bytes, const long long* clip_index, long n_clips,
                         unsigned long long* counts, hipStream_t s);
+// Pillow's 8-bit antialiased bilinear resize of n_frames uint8 planes (horizontal pass first) fused with the quantiser above
+// (resize.hip); tables from resample_coeffs, on the device.  Plane p is plane p % frames_per_clip of clip clip_index[p / frames_per_clip]
+// (or of clip p / frames_per_clip), planes frame_stride bytes apart; outputs are dense, any of them may be null but not all
+int launch_resize_quantise_normalise(const unsigned char* frames, long frame_stride, const long long* clip_index, int frames_per_clip,
+                                     long n_frames, int in_h, int in_w, int out_h, int out_w, const int* h_bounds, const int* h_coeffs,
+                                     int h_ksize, const int* v_bounds, const int* v_coeffs, int v_ksize, const float* centres, int q,
+                                     float mean, float stdv, long long* labels, float* image, unsigned char* resized, hipStream_t s);
 int launch_convert(int dt_in, int dt_out, const void* in, void* out, long n, hipStream_t s);
 int launch_fill_f32(float* p, float v, long n, hipStream_t s);
 int launch_concat2_to_t(int dt, const float* a, const float* b, int rows, int ca, int cb, void* out, hipStream_t s);

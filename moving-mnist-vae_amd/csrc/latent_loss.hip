@@ -685,10 +685,7 @@ int launch_normalise(int dt, const void* labels, int label_bytes, long n, float 
 __global__ void quantise_normalise_kernel(const unsigned char* __restrict__ frames, long n, const float* __restrict__ centres, int q,
                                           float mean, float stdv, long long* __restrict__ labels, float* __restrict__ image) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const float x = (float)frames[i] / 255.0f;
-    int best = 0;
-    float bd = (x - centres[0]) * (x - centres[0]);
-    for (int k = 1; k < q; ++k) { const float d = (x - centres[k]) * (x - centres[k]); if (d < bd) { bd = d; best = k; } }
+    const int best = quantise_byte(frames[i], centres, q);
     if (labels) labels[i] = best;
     if (image) image[i] = ((float)best - mean) / stdv;
   }

@@ -337,6 +337,141 @@ def quantise_frames(frames_u8, centres, data_mean, data_std):
     return labels, image
 
 
+_RESAMPLE_TABLES = {}                  # (in_size, out_size, device) -> (bounds int32 [out, 2], coeffs int32 [out, ksize], ksize), on the device
+
+
+def _resample_tables(in_size, out_size, device):
+    """Device copy of mmvae_resample_coeffs(in_size, out_size), built once per (in, out, device): later calls copy nothing."""
+    from ._lib import check, lib
+    import ctypes
+    key = (int(in_size), int(out_size), str(device))
+    hit = _RESAMPLE_TABLES.get(key)
+    if hit is None:
+        ksize = ctypes.c_int(0)
+        check(lib().mmvae_resample_coeffs(key[0], key[1], ctypes.byref(ksize), None, None), "mmvae_resample_coeffs")
+        bounds = np.zeros((key[1], 2), dtype=np.int32)
+        coeffs = np.zeros((key[1], ksize.value), dtype=np.int32)
+        check(lib().mmvae_resample_coeffs(key[0], key[1], ctypes.byref(ksize), bounds.ctypes.data, coeffs.ctypes.data), "mmvae_resample_coeffs")
+        hit = (torch.from_numpy(bounds).to(device), torch.from_numpy(coeffs).to(device), int(ksize.value))
+        _RESAMPLE_TABLES[key] = hit
+    return hit
+
+
+def _size_pair(size):
+    if isinstance(size, (tuple, list)):
+        if len(size) != 2:
+            raise ValueError("size is an int or an (h, w) pair")
+        return int(size[0]), int(size[1])
+    return int(size), int(size)
+
+
+def _checked_clip_index(clip_index, n, device, what):
+    idx = torch.as_tensor(clip_index, dtype=torch.int64, device=device).reshape(-1).contiguous()
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n):
+        raise IndexError(f"{what}: clip_index outside [0, {n})")
+    return idx
+
+
+def _resize_launch(frames_u8, size, centres, data_mean, data_std, idx, want):
+    """One mmvae_resize_quantise_normalise launch.  frames_u8: uint8 device tensor [..., H, W]; idx: None, or trusted int64 device
+    indices into the leading axis of an (N, C, H, W) tensor (whole clips are gathered).  want: which of (labels, image, resized) to
+    produce.  Returns the three tensors (None where not wanted), shaped [..., S_h, S_w] (leading axis len(idx) under a gather)."""
+    from ._lib import check, lib, ptr
+    f = frames_u8
+    if f.dim() < 2:
+        raise ValueError("expected frames of shape [..., H, W]")
+    H, W = int(f.shape[-2]), int(f.shape[-1])
+    out_h, out_w = size
+    if idx is not None:
+        if f.dim() < 3:
+            raise ValueError("clip_index needs a leading clip axis: frames of shape (N, ..., H, W)")
+        f = f.contiguous()
+        per_clip = f[0].numel() // (H * W) if f.shape[0] else 1
+        lead, stride, n_frames = (idx.numel(),) + tuple(f.shape[1:-2]), H * W, idx.numel() * per_clip
+    elif f.dim() == 3 and f.stride(2) == 1 and f.stride(1) == W and f.stride(0) >= H * W:
+        per_clip, lead, stride, n_frames = 1, (f.shape[0],), int(f.stride(0)), int(f.shape[0])          # planes of a larger buffer, in place
+    else:
+        f = f.contiguous()
+        per_clip, lead, stride, n_frames = 1, tuple(f.shape[:-2]), H * W, f.numel() // (H * W) if H * W else 0
+    hb, hc, hk = _resample_tables(W, out_w, f.device)
+    vb, vc, vk = _resample_tables(H, out_h, f.device)
+    shape = tuple(lead) + (out_h, out_w)
+    labels = torch.empty(shape, dtype=torch.int64, device=f.device) if want[0] else None
+    image = torch.empty(shape, dtype=torch.float32, device=f.device) if want[1] else None
+    resized = torch.empty(shape, dtype=torch.uint8, device=f.device) if want[2] else None
+    if n_frames == 0:                            # nothing to launch (and empty tensors have no address to hand over)
+        return labels, image, resized
+    c = None
+    if want[0] or want[1]:
+        c = torch.as_tensor(centres, dtype=torch.float32, device=f.device).reshape(-1).contiguous()
+    with torch.cuda.device(f.device):
+        check(lib().mmvae_resize_quantise_normalise(ptr(f), stride, ptr(idx), per_clip, n_frames, H, W, out_h, out_w, ptr(hb), ptr(hc), hk,
+                                                    ptr(vb), ptr(vc), vk, ptr(c), 0 if c is None else c.numel(), float(data_mean),
+                                                    float(data_std), ptr(labels), ptr(image), ptr(resized),
+                                                    torch.cuda.current_stream().cuda_stream), "mmvae_resize_quantise_normalise")
+    return labels, image, resized
+
+
+def _resize_args(frames_u8, size, clip_index, what):
+    if not isinstance(frames_u8, torch.Tensor) or frames_u8.dtype != torch.uint8 or not frames_u8.is_cuda:
+        raise ValueError(f"{what} expects a uint8 tensor on the GPU")
+    if frames_u8.dim() < 2:
+        raise ValueError(f"{what} expects frames of shape [..., H, W]")
+    size = _size_pair(size)
+    idx = None
+    if clip_index is not None:
+        if frames_u8.dim() < 3:
+            raise ValueError(f"{what}: clip_index needs a leading clip axis")
+        idx = _checked_clip_index(clip_index, frames_u8.shape[0], frames_u8.device, what)
+    native = size == (int(frames_u8.shape[-2]), int(frames_u8.shape[-1]))
+    return size, idx, native
+
+
+def resize_frames(frames_u8, size, clip_index=None):
+    """``transforms.Resize`` of the reference's input transform (main.py:33-36) on the device: every (H, W) plane of the uint8 device
+    tensor ``frames_u8`` [..., H, W] is resized as a PIL mode-``L`` image, independently -- what the reference does to an MNIST image
+    (its resize branch cannot take a 20-channel Moving-MNIST item: ToPILImage stops at 4 channels).  The bytes are PIL's
+    ``Image.resize(..., Image.BILINEAR)`` exactly: antialiased triangle filter, 22-bit fixed-point taps, the horizontal pass first,
+    uint8 rounding behind each pass.  ``size``: an int S (S x S; the reference only ever resizes square images) or an ``(h, w)``
+    pair; sides up to 128.  ``clip_index`` (int64 indices into the leading axis, checked against it first: one device -> host read)
+    resizes only those clips, in that order, without materialising the gather.  Returns uint8 [..., S_h, S_w]; at the native size
+    the input comes back (gathered if asked) and nothing is launched."""
+    size, idx, native = _resize_args(frames_u8, size, clip_index, "resize_frames")
+    if native:
+        return frames_u8 if idx is None else frames_u8.index_select(0, idx)
+    return _resize_launch(frames_u8, size, None, 0.0, 1.0, idx, (False, False, True))[2]
+
+
+def resize_quantise_frames(frames_u8, size, centres, data_mean, data_std, clip_index=None):
+    """``resize_frames`` fused with ``quantise_frames``: one launch from resident uint8 planes to ``(labels int64, image f32)`` at
+    ``size`` (the second branch of the reference's choose_transformer plus the normalisation of main.py:383-387).  Equal, bit for
+    bit, to ``quantise_frames(resize_frames(frames_u8, size), centres, data_mean, data_std)``.  At the native size this IS
+    ``quantise_frames``."""
+    size, idx, native = _resize_args(frames_u8, size, clip_index, "resize_quantise_frames")
+    if native:
+        return quantise_frames(frames_u8 if idx is None else frames_u8.index_select(0, idx), centres, data_mean, data_std)
+    labels, image, _ = _resize_launch(frames_u8, size, centres, data_mean, data_std, idx, (True, True, False))
+    return labels, image
+
+
+def choose_transformer(centres, args):
+    """The reference's dispatch rule (choose_transformer, main.py:27-38) over device uint8 batches: MNIST at 28 and MovingMNIST at 64
+    only quantise, every other ``args.input_image_size`` resizes to it first.  Returns a callable: uint8 device batch (B, ..., H, W)
+    -> int64 k-means labels of shape (B, -1), what the reference's loader yields per item."""
+    dataset, size = getattr(args, "dataset", "MovingMNIST"), int(args.input_image_size)
+    c = torch.as_tensor(centres, dtype=torch.float32).reshape(-1)
+    if (dataset == "MNIST" and size == 28) or (dataset == "MovingMNIST" and size == 64):
+        def transform(batch_u8):
+            labels, _ = quantise_frames(batch_u8, c, 0.0, 1.0)
+            return labels.view(labels.shape[0], -1)
+    else:
+        def transform(batch_u8):
+            _resize_args(batch_u8, size, None, "choose_transformer")
+            labels = _resize_launch(batch_u8, (size, size), c, 0.0, 1.0, None, (True, False, False))[0]
+            return labels.view(labels.shape[0], -1)
+    return transform
+
+
 def pixel_histogram(frames_u8, clip_index=None):
     """Byte histogram of uint8 frames on the device: a (256,) int64 device tensor, ``counts[b]`` = occurrences of byte ``b``
     (exact; integer atomics, so the same bits every run).  ``frames_u8``: a contiguous uint8 device tensor of any alignment whose
@@ -470,9 +605,13 @@ class MovingMNISTClips:
 
     source: a folder holding movingmnisttrain.npz / movingmnisttest.npz, or an (N, C, W, H) uint8 array in the file's layout.
     centres: the q k-means centres on the ToTensor scale [0, 1] (kmeans_dict['kmeans'].cluster_centers_.ravel()), or None: call
-    ``fit_quantiser`` before iterating."""
+    ``fit_quantiser`` before iterating.
+    image_size: None or the clips' own H: as above.  Another S: the reference's resize branch (``--input_image_size`` S, its default
+    being 32) -- the gather, ``resize_frames`` and the quantiser are ONE launch and the iterator yields labels of shape (B, C*S*S).
+    ``fit_quantiser`` still fits on the native bytes, as the reference's save_kmeans_file does; for label statistics at S fit on
+    ``resize_frames(loader.clips, S)`` instead (``fit_quantiser(resize_frames(loader.clips, S), q)``)."""
 
-    def __init__(self, source, centres, batch_size, device, train=True, shuffle=True, seed=None, drop_last=False):
+    def __init__(self, source, centres, batch_size, device, train=True, shuffle=True, seed=None, drop_last=False, image_size=None):
         import os
         if isinstance(source, (str, os.PathLike)):
             path = os.path.join(source, "movingmnisttrain.npz" if train else "movingmnisttest.npz")
@@ -484,6 +623,9 @@ class MovingMNISTClips:
         self.train_data = self.clips                  # len(dataset.train_data) is read by main.py:506
         self.centres = None if centres is None else torch.as_tensor(centres, dtype=torch.float32).reshape(-1)
         self.batch_size, self.shuffle, self.drop_last = int(batch_size), bool(shuffle), bool(drop_last)
+        self.image_size = None if image_size is None else _size_pair(image_size)
+        if self.image_size is not None and self.image_size[0] != self.image_size[1]:
+            raise ValueError("image_size is one int S (the model's input_image_size)")
         self._gen = torch.Generator(device="cpu")
         if seed is not None:
             self._gen.manual_seed(int(seed))
@@ -505,8 +647,12 @@ class MovingMNISTClips:
         n = self.clips.shape[0]
         order = torch.randperm(n, generator=self._gen) if self.shuffle else torch.arange(n)
         order = order.to(self.device)
+        resize = self.image_size is not None and self.image_size != tuple(self.clips.shape[-2:])
         for i in range(len(self)):
             idx = order[i * self.batch_size:(i + 1) * self.batch_size]
-            frames = self.clips.index_select(0, idx)
-            labels, _ = quantise_frames(frames, self.centres, 0.0, 1.0)
+            if resize:                           # gather + resize + quantise in one launch (idx comes from `order`: in range)
+                labels = _resize_launch(self.clips, self.image_size, self.centres, 0.0, 1.0, idx.contiguous(), (True, False, False))[0]
+            else:
+                frames = self.clips.index_select(0, idx)
+                labels, _ = quantise_frames(frames, self.centres, 0.0, 1.0)
             yield labels.view(labels.shape[0], -1)
