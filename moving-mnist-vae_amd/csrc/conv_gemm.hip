@@ -397,7 +397,7 @@ static size_t deep2_lds_for(int dt, int Cin, int Cout, int hw, int HiWi, int nta
   b.Cin = Cin; b.Hi = HiWi; b.Wi = 1; b.ipt = npt * 16 / hw; b.npt = npt; b.ntaps_all = ntaps_all; b.nw = Cout / 32 < 8 ? Cout / 32 : 8;
   return deep2_conv_lds_bytes(b, dt);
 }
-bool deep2_shape_ok(int dt, int Cin, int Cout, int Hq, int Wq, int Hi, int Wi, int ntaps_all, int fp8) {
+static bool deep2_shape_ok(int dt, int Cin, int Cout, int Hq, int Wq, int Hi, int Wi, int ntaps_all, int fp8) {
   if (fp8 && dt != DT_BF16) return false;
   const int ES = fp8 ? 1 : dt == DT_F32 ? 4 : 2;
   const int cpt = Cin * ES / 64;
@@ -413,7 +413,9 @@ bool deep2_shape_ok(int dt, int Cin, int Cout, int Hq, int Wq, int Hi, int Wi, i
   if (fp8 && cpt > 4) return false;
   return deep2_lds_for(dt, Cin, Cout, hw, Hi * Wi, ntaps_all, npt_min, fp8) <= 150 * 1024;
 }
-static int try_deep2(int dt, int out_dt, const GatherArgs& a, hipStream_t s) {
+// dry (here and in try_pos): stop in front of the launch and return 1 -- "would this kernel take the launch?" for the callers that settle a
+// layer's weight layout (gather_deep2_takes / gather_pos_takes); no stream is used and no data pointer is looked at
+static int try_deep2(int dt, int out_dt, const GatherArgs& a, hipStream_t s, bool dry = false) {
   if (a.x_planar || a.y_planes || a.x2) return 0;
   if (a.fp8 && (!a.wfrag || a.accumulate || dt != DT_BF16 || out_dt != DT_BF16)) return 0;
   int Hq = 0, Wq = 0, ntaps_all = 0;
@@ -460,6 +462,7 @@ static int try_deep2(int dt, int out_dt, const GatherArgs& a, hipStream_t s) {
       best = npt;
     }
   if (!best) return 0;
+  if (dry) return 1;
   b.npt = best; b.ipt = best * 16 / hw;
   if (b.ipt > a.N) b.ipt = a.N;
   b.ntiles = (a.N + b.ipt - 1) / b.ipt;
@@ -468,11 +471,11 @@ static int try_deep2(int dt, int out_dt, const GatherArgs& a, hipStream_t s) {
 }
 
 // pos_conv_kernel (conv_pos.inc): q-grids up to 4x4, MFMA columns = images, padded (position, tap) pairs not computed
-static int try_pos(int dt, int out_dt, const GatherArgs& a, hipStream_t s) {
+static int try_pos(int dt, int out_dt, const GatherArgs& a, hipStream_t s, bool dry = false) {
   if (dt != DT_BF16 || out_dt != DT_BF16 || !a.wfrag || a.fp8 || a.gup == 0) return 0;
-  if (a.x_planar || a.y_planes || a.x2 || a.bias || a.Hi != a.Wi || a.Ho != a.Wo || a.Cout % 32 != 0) return 0;
+  if (a.x_planar || a.y_planes || a.x2 || a.bias || a.Hi != a.Wi || a.Ho != a.Wo || a.Cout < 32 || a.Cout % 32 != 0) return 0;
+  if (a.Cin < 8 || a.Cin % 8 != 0) return 0;      // (the dispatcher has checked this; a layout query comes here unchecked)
   const int up = a.gup == 2 ? 1 : 0;
-  if (!pos_conv_takes(a.gk, a.gs, a.gp, up, a.Hi, a.Ho, a.Cin)) return 0;
   if (up && a.gs > 1 && a.gk < a.gs && !a.accumulate) return 0;      // stride phases without a tap would have to be zero-filled
   if (a.Hi >= 8 && a.Cout < 128) return 0;      // an 8x8 input tile is 131 KB of LDS (one block per CU): with two waves per block deep2 wins (measured)
   if ((long)a.N * a.Ho * a.Wo * a.Cout >= (1L << 32)) return 0;
@@ -481,8 +484,10 @@ static int try_pos(int dt, int out_dt, const GatherArgs& a, hipStream_t s) {
   b.stats = a.stats; b.accumulate = a.accumulate; b.N = a.N; b.Cout = a.Cout;
   b.nw = a.Cout / 32 < 8 ? a.Cout / 32 : 8;
   if ((a.Cout / 32) % b.nw != 0 || (64 * b.nw) % (a.Cin / 8) != 0) return 0;
-  return launch_pos_conv(a.gk, a.gs, a.gp, up, a.Hi, a.Ho, a.Cin, b, s);
+  return launch_pos_conv(a.gk, a.gs, a.gp, up, a.Hi, a.Ho, a.Cin, dry ? nullptr : &b, s);
 }
+bool gather_deep2_takes(int dt, int out_dt, const GatherArgs& a) { return try_deep2(dt, out_dt, a, nullptr, true) > 0; }
+bool gather_pos_takes(int dt, int out_dt, const GatherArgs& a) { return try_pos(dt, out_dt, a, nullptr, true) > 0; }
 
 // the second source as its own accumulate launch (shapes the patch-tile kernel does not merge)
 static int launch_x2_separately(int dt, int out_dt, const GatherArgs& a, hipStream_t s) {

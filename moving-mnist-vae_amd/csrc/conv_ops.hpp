@@ -13,14 +13,20 @@ struct ConvGeom { int D0, D1, k, s, p; };
 inline int conv_down_size(int H, int k, int s, int p) { return (H + 2 * p - k) / s + 1; }
 // packed element counts (both equal numel(weight)); 16-byte alignment is the caller's job
 // scale multiplies the weights (fp8 layers: the static per-layer scale); fp8 = 1 writes e4m3 bytes (batched packing only)
-// frag = 1: fragment-major order (PackArgs::frag) -- what deep2_conv_kernel reads; op_deep2_down_ok / op_deep2_up_ok say whether the
-// run_down / run_up launch of this geometry (large-side map Hl x Wl) goes to that kernel (fp8: its e4m3 form), i.e. whether to pack and
-// run with the flag set.
+// frag = 1: fragment-major order (PackArgs::frag) -- what deep2_conv_kernel and pos_conv_kernel read; op_down_layout / op_up_layout say
+// whether to pack and run with the flag set.
 int op_pack_down(int dt, const ConvGeom& g, const float* w, void* dst, hipStream_t s, float scale = 1.f, int fp8 = 0, int frag = 0);
 int op_pack_up(int dt, const ConvGeom& g, const float* w, void* dst, hipStream_t s, float scale = 1.f, int fp8 = 0, int frag = 0);
-int op_deep2_down_ok(int dt, const ConvGeom& g, int Hl, int Wl, int fp8 = 0);
+// Where the run_down / run_up launch of this geometry (large-side map Hl x Wl) goes, asked of the dispatcher itself with the launch's own
+// GatherArgs (gather_deep2_takes / gather_pos_takes, kernels.hpp):
+struct ConvLayout {
+  bool frag = false;   // deep2_conv_kernel takes it: pack fragment-major and run with wfrag set
+  bool fp8 = false;    // the e4m3 form of deep2_conv_kernel takes it (bf16 storage, non-accumulating launches)
+  bool pos = false;    // with fragment-major bf16 weights the position-major kernel, which is offered the launch first, takes it
+};
+ConvLayout op_down_layout(int dt, const ConvGeom& g, int Hl, int Wl);
 // allow_empty_phases: the launch accumulates (or is a second source), so stride phases without a tap are skipped, not zero-filled
-int op_deep2_up_ok(int dt, const ConvGeom& g, int Hl, int Wl, int allow_empty_phases = 0, int fp8 = 0);
+ConvLayout op_up_layout(int dt, const ConvGeom& g, int Hl, int Wl, int allow_empty_phases = 0);
 // x2 / w2 / Cin2 (optional): a second tensor on the q grid (= S for run_down, = the S-resolution grid for run_up) whose 1x1
 // convolution with the packed [Cout][Cin2] matrix w2 is added into the result (phase (0,0) of run_up) in the same kernel.
 struct SecondSrc {
@@ -40,6 +46,7 @@ int op_run_wgrad_pair(int dt, const ConvGeom& g, const ConvGeom& gs, int N, cons
                       const float* proG_s, const float* proG_b, int proG_relu, float* dW, float* dW2, hipStream_t s, float* scratch, float scale,
                       float scale2);
 
+bool op_bwd_fusable(int dt, const ConvGeom& g, int N, int Hs, int Ws, int Hl, int Wl);
 // Weight gradient AND the data gradient w.r.t. the small-side tensor P in ONE pass over G (wgrad_stream_kernel with DG; the 16 -> 16
 // channel k4 s2 layers on 32x32 -> 64x64 maps, bf16):  dW += P^T (x) G;  dP = down(G) with the conv's packed down form (+ x2 (x) w2,
 // the 1x1 shortcut's share, x2 on P's grid with 16 channels, w2 its packed up form).  Returns 1 when taken, 0 when the shape is not
@@ -48,8 +55,6 @@ int op_run_wgrad_pair(int dt, const ConvGeom& g, const ConvGeom& gs, int N, cons
 // Taken: returns the number of rows (> 0).  scratch: kWgradScratchBytes, not shared with a concurrent wgrad.
 // dW2 (optional, with x2): the weight gradient of the 1x1 conv itself, [16][D0] row-major (Conv2d (out, in, 1, 1)) += scale2 * x2^T (x) pro(P):
 // both rows are in LDS for the pass anyway.
-bool op_pos_fwd_takes(const ConvGeom& g, int Hl, bool transposed);   // the bf16 position-major kernel takes the layer's forward launch
-bool op_bwd_fusable(int dt, const ConvGeom& g, int N, int Hs, int Ws, int Hl, int Wl);
 int op_run_bwd_fused(int dt, const ConvGeom& g, int N, const void* P, int Hs, int Ws, const float* proP_s, const float* proP_b, int proP_relu,
                      const void* G, int Hl, int Wl, const void* packed_down, void* dP, const void* x2, const void* w2_packed, float* dW,
                      hipStream_t s, float* scratch, float scale = 1.f, float* bn_part = nullptr, float* dW2 = nullptr, float scale2 = 1.f,

@@ -22,8 +22,7 @@ static int pos_dispatch(int K, int S, int P, int up, int HI, int HO, int CIN, co
   if (rc == 0) rc = pos_conv_tu_c(K, S, P, up, HI, HO, CIN, a, s);
   return rc;
 }
-bool pos_conv_takes(int K, int S, int P, int up, int HI, int HO, int CIN) { return pos_dispatch(K, S, P, up, HI, HO, CIN, nullptr, nullptr) > 0; }
-int launch_pos_conv(int K, int S, int P, int up, int HI, int HO, int CIN, const PosArgs& a, hipStream_t s) {
-  return pos_dispatch(K, S, P, up, HI, HO, CIN, &a, s);
+int launch_pos_conv(int K, int S, int P, int up, int HI, int HO, int CIN, const PosArgs* a, hipStream_t s) {
+  return pos_dispatch(K, S, P, up, HI, HO, CIN, a, s);
 }
 }  // namespace mmvae

@@ -39,11 +39,13 @@ struct GatherArgs {
   int wfrag, wfrag2;       // 1: w (w2) is packed fragment-major (PackArgs::frag); only deep2_conv_kernel / pos_conv_kernel read it (else an error)
   int gk, gs, gp, gup;     // the conv-like weight's (k, s, p) and the form (1: down, 2: up) when the launch comes from op_run_down / op_run_up (0: unknown)
 };
-// Shapes deep2_conv_kernel takes (conv_deep2.inc): the layers whose weights are packed fragment-major.  q grid Hq x Wq per phase
-// and image, input map Hi x Wi, ntaps over all phases.
-bool deep2_shape_ok(int dt, int Cin, int Cout, int Hq, int Wq, int Hi, int Wi, int ntaps_all, int fp8 = 0);   // fp8: e4m3 weights / LDS (bf16 storage)
 // out_dt: dtype of y (may be DT_F32 while x/w are bf16).  Returns the number of stats partial rows (>0) or an error (<0).
 int launch_gather_gemm(int dt, int out_dt, GatherArgs a, hipStream_t s);
+// Whether deep2_conv_kernel (conv_deep2.inc; a.fp8: its e4m3 form) / pos_conv_kernel (conv_pos.inc) takes the launch when the dispatcher offers
+// it: the dispatcher's own code, stopped in front of the launch.  These two read fragment-major weights (a.wfrag), so whoever packs a layer asks
+// here.  The data pointers of `a` are not looked at (they may be null), except that a.x2 / a.bias / a.pro_scale say whether there is one.
+bool gather_deep2_takes(int dt, int out_dt, const GatherArgs& a);
+bool gather_pos_takes(int dt, int out_dt, const GatherArgs& a);
 constexpr int kGatherMaxGridX = 1024;
 
 // ---------------------------------------------------------------- wgrad
@@ -189,9 +191,8 @@ struct PosArgs {
   int ntiles;                  // set by the launcher
 };
 // up = 0: "down" form (Conv2d forward / ConvT data gradient), up = 1: "up" form; HI / HO input / output map size.  Returns stats rows (> 0),
-// 0 when no instantiation takes the geometry, < 0 on error.
-int launch_pos_conv(int K, int S, int P, int up, int HI, int HO, int CIN, const PosArgs& a, hipStream_t s);
-bool pos_conv_takes(int K, int S, int P, int up, int HI, int HO, int CIN);
+// 0 when no instantiation takes the geometry, < 0 on error.  a == nullptr: nothing is launched, 1 when an instantiation takes the geometry.
+int launch_pos_conv(int K, int S, int P, int up, int HI, int HO, int CIN, const PosArgs* a, hipStream_t s);
 
 // ---------------------------------------------------------------- weight packing
 // dst[(col*ntaps + t)*K + k] = T(scale * src[col*s_col + k*s_k + tap_off[t]])

@@ -34,7 +34,7 @@ ConvW Net::add_conv(const std::string& name, int D0, int D1, int k, int s, int p
   if (numel > max_w) max_w = numel;
   if (pack) { w.packD = n_packed; n_packed += align_up(numel, 8); w.packU = n_packed; n_packed += align_up(numel, 8); }
   if (cfg.fp8 && pack && D0 >= 64 && D1 >= 64 && D0 % 64 == 0 && D1 % 64 == 0) {
-    // candidate; settle_fp8() confirms it once the layer's place in the net (Hl) is known
+    // candidate; settle_layout() confirms it once the layer's place in the net (Hl) is known
     // static scale: PyTorch's default init is U(+-1/sqrt(D1*k*k)) for both weight layouts; bring that bound to ~16..32 (e4m3 normal range)
     w.fp8 = true;
     int e = 0; while ((float)(1 << e) < 16.f * std::sqrt((float)D1 * k * k)) ++e;
@@ -47,11 +47,18 @@ ConvW Net::add_conv(const std::string& name, int D0, int D1, int k, int s, int p
 // takes the layer's FORWARD launch (e.g. z = 192 makes decoder.conv1 a 3-chunk row, which it does not) -- the others stay bf16 layers.
 // So do the layers on 2x2 / 4x4 maps whose forward the bf16 position-major kernel takes: it is faster there than the e4m3 deep2 form (with them
 // in fp8 the mode ran at 0.96x of bf16 in round 4) -- fp8 arithmetic stays where it pays.
-void Net::settle_fp8(ConvW& w) const {
-  if (!w.fp8) return;
-  const bool ok = w.Hl > 0 && !op_pos_fwd_takes(ConvGeom{w.D0, w.D1, w.k, w.s, w.p}, w.Hl, w.tr) && (w.tr ? op_deep2_up_ok(DT_BF16, ConvGeom{w.D0, w.D1, w.k, w.s, w.p}, w.Hl, w.Hl, 1, 1)
-                                    : op_deep2_down_ok(DT_BF16, ConvGeom{w.D0, w.D1, w.k, w.s, w.p}, w.Hl, w.Hl, 1));
-  if (!ok) { w.fp8 = false; w.wscale = 1.f; }
+//
+// The layouts of the two packs follow: fragment-major where deep2_conv_kernel takes the launch of that form at the layer's place in the net
+// (the e4m3 form for the forward direction of an fp8 layer).  The up form of a 1x1 stride-2 shortcut has stride phases without a tap: in this
+// net it only ever accumulates into (or rides along with) the main path's data gradient, so those phases are skipped.
+void Net::settle_layout(ConvW& w) const {
+  if (w.Hl <= 0) { if (w.fp8) { w.fp8 = false; w.wscale = 1.f; } return; }
+  const ConvGeom g{w.D0, w.D1, w.k, w.s, w.p};
+  const ConvLayout dn = op_down_layout(dt(), g, w.Hl, w.Hl), up = op_up_layout(dt(), g, w.Hl, w.Hl, 1);
+  const ConvLayout& fwd = w.tr ? up : dn;
+  if (w.fp8 && (fwd.pos || !fwd.fp8)) { w.fp8 = false; w.wscale = 1.f; }
+  w.fragD = (w.fp8 && !w.tr) ? dn.fp8 : dn.frag;
+  w.fragU = (w.fp8 && w.tr) ? up.fp8 : up.frag;
 }
 
 Bn Net::add_bn(const std::string& prefix, int C) {
@@ -157,9 +164,9 @@ Net::Net(const NetCfg& c) : cfg(c) {
       L.c2.wscale = 16.f; L.cs.wscale = 16.f;
     }
   }
-  settle_fp8(dstem);
-  for (Block& B : enc) { settle_fp8(B.c1); settle_fp8(B.c2); settle_fp8(B.cs); }
-  for (Block& B : dec) { settle_fp8(B.c1); settle_fp8(B.c2); settle_fp8(B.cs); }
+  settle_layout(dstem);
+  for (Block& B : enc) { settle_layout(B.c1); settle_layout(B.c2); if (!B.identity) settle_layout(B.cs); }
+  for (Block& B : dec) { settle_layout(B.c1); settle_layout(B.c2); if (!B.identity) settle_layout(B.cs); }
   tail = add_conv("decoder.conv2.weight", c.out_ch, 16, 3, 1, 1, false);
   tail_bias = n_params; add_entry("decoder.conv2.bias", {c.out_ch}, EK_PARAM, n_params); n_params += c.out_ch;
   bn_out = add_bn("decoder.bn2", c.out_ch);
@@ -244,17 +251,13 @@ int Net::fill_consts(const Pass& ps, hipStream_t s) {
 // ------------------------------------------------------------------------------------------------ conv helpers
 static inline ConvGeom geom(const ConvW& w) { return ConvGeom{w.D0, w.D1, w.k, w.s, w.p}; }
 
-// The pack that feeds a conv's FORWARD direction (down for Conv2d, up for ConvTranspose2d) is e4m3 bytes on an fp8 layer (fragment-major
-// when the fp8 form of the kernel takes the shape); every pack of an fp8 layer carries its weight scale.
-// The up form of a 1x1 stride-2 shortcut has stride phases without a tap: in this net it only ever accumulates into (or rides along
-// with) the main path's data gradient, so those phases are skipped.
-int Net::frag_down(const ConvW& w) const { return w.Hl > 0 ? op_deep2_down_ok(dt(), geom(w), w.Hl, w.Hl, (w.fp8 && !w.tr) ? 1 : 0) : 0; }
-int Net::frag_up(const ConvW& w) const { return w.Hl > 0 ? op_deep2_up_ok(dt(), geom(w), w.Hl, w.Hl, 1, (w.fp8 && w.tr) ? 1 : 0) : 0; }
+// The pack that feeds a conv's FORWARD direction (down for Conv2d, up for ConvTranspose2d) is e4m3 bytes on an fp8 layer; every pack of an
+// fp8 layer carries its weight scale.  Fragment-major or plain: settled per layer in settle_layout().
 int Net::pack_down(const Pass& ps, const ConvW& w, hipStream_t s) {
-  return op_pack_down(dt(), geom(w), ps.params + w.off, ps.packed(w.packD), s, w.wscale, (w.fp8 && !w.tr) ? 1 : 0, frag_down(w));
+  return op_pack_down(dt(), geom(w), ps.params + w.off, ps.packed(w.packD), s, w.wscale, (w.fp8 && !w.tr) ? 1 : 0, w.fragD);
 }
 int Net::pack_up(const Pass& ps, const ConvW& w, hipStream_t s) {
-  return op_pack_up(dt(), geom(w), ps.params + w.off, ps.packed(w.packU), s, w.wscale, (w.fp8 && w.tr) ? 1 : 0, frag_up(w));
+  return op_pack_up(dt(), geom(w), ps.params + w.off, ps.packed(w.packU), s, w.wscale, (w.fp8 && w.tr) ? 1 : 0, w.fragU);
 }
 int Net::run_down(const Pass& ps, const ConvW& w, const void* L, int Hl, int Wl, void* S, int Hs, int Ws,
                   const float* pro_s, const float* pro_b, int relu, float* stats, int accumulate, int out_dt, hipStream_t s,
@@ -262,7 +265,7 @@ int Net::run_down(const Pass& ps, const ConvW& w, const void* L, int Hl, int Wl,
   SecondSrc q;
   if (w2) { q.x2 = x2; q.w2 = ps.packed(w2->packU); q.Cin2 = w2->D0; }
   q.fp8 = (w.fp8 && !w.tr) ? 1 : 0;               // a Conv2d's forward
-  q.wfrag = frag_down(w); q.wfrag2 = w2 ? frag_up(*w2) : 0;
+  q.wfrag = w.fragD; q.wfrag2 = w2 ? w2->fragU : 0;
   return op_run_down(dt(), out_dt, geom(w), ps.packed(w.packD), ps.N, L, Hl, Wl, S, Hs, Ws, pro_s, pro_b, relu, stats, accumulate, s, q);
 }
 int Net::run_up(const Pass& ps, const ConvW& w, const void* S, int Hs, int Ws, void* L, int Hl, int Wl,
@@ -271,7 +274,7 @@ int Net::run_up(const Pass& ps, const ConvW& w, const void* S, int Hs, int Ws, v
   SecondSrc q;
   if (w2) { q.x2 = x2; q.w2 = ps.packed(w2->packU); q.Cin2 = w2->D0; }
   q.fp8 = (w.fp8 && w.tr) ? 1 : 0;                // a ConvTranspose2d's forward
-  q.wfrag = frag_up(w); q.wfrag2 = w2 ? frag_up(*w2) : 0;
+  q.wfrag = w.fragU; q.wfrag2 = w2 ? w2->fragU : 0;
   return op_run_up(dt(), geom(w), ps.packed(w.packU), ps.N, S, Hs, Ws, L, Hl, Wl, pro_s, pro_b, relu, stats, accumulate, s, q);
 }
 hipStream_t Net::wgrad_stream(hipStream_t s) {
@@ -355,7 +358,7 @@ bool Net::stem_dg_fused() const {
   if (enc.empty() || !stem_bwd_fused() || !stem_bwd_dg_ok(dt(), cfg.S)) return false;
   const Block& B = enc[0];
   return !B.identity && B.Cin == 32 && B.C == 32 && B.c1.k == 3 && B.c1.s == 2 && B.c1.p == 1 && B.cs.k == 1 && B.cs.s == 2 && B.cs.p == 0 &&
-         !B.c1.fp8 && !B.cs.fp8 && B.c1.wscale == 1.f && B.cs.wscale == 1.f && frag_up(B.c1) == 0 && frag_up(B.cs) == 0 && H1 == 32 && B.Hout == 16;
+         !B.c1.fp8 && !B.cs.fp8 && B.c1.wscale == 1.f && B.cs.wscale == 1.f && !B.c1.fragU && !B.cs.fragU && H1 == 32 && B.Hout == 16;
 }
 
 bool Net::tail_fwd_fused() const {
@@ -880,7 +883,7 @@ int Net::decoder_fwd(int N, const float* encv, const float* params, float* bnbuf
     // the join, fused with the next block's 1x1 conv1 and bn1's statistics where that block's conv1 is 16-wide (uplayer3 -> 4, uplayer4 -> 5):
     // the joined row is the conv's operand while it is in LDS -- one launch and one pass over `out` fewer than join -> conv
     const bool fuse_c1 = i + 1 < nd && !B.identity && !dec[i + 1].identity && !dec[i + 1].c1.fp8 && dec[i + 1].c1.k == 1 && dec[i + 1].c1.s == 1 &&
-                         dec[i + 1].c1.D1 == B.C && frag_down(dec[i + 1].c1) == 0 && dec[i + 1].c1.wscale == 1.f &&
+                         dec[i + 1].c1.D1 == B.C && !dec[i + 1].c1.fragD && dec[i + 1].c1.wscale == 1.f &&
                          join_conv1_fwd_ok(dt(), B.C, dec[i + 1].c1.D0, (long)N * B.Hout * B.Wout);
     if (fuse_c1) {
       c1_done = launch_join_conv1_fwd(B.C, base + B.y2, r2.scale, r2.shift, sc.y, sc.scale, sc.shift, ps.packed(dec[i + 1].c1.packD),

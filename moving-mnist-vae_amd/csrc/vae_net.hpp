@@ -26,7 +26,8 @@ struct Entry { std::string name; int ndim; int shape[4]; int kind; long offset; 
 // fp8 (BASELINE configs[4]): the conv's FORWARD runs on the fp8 MFMA (e4m3 weights x e4m3 activations, f32 accumulate) with
 // the static power-of-two weight scale wscale; its stored output is y' = wscale * y, which the BatchNorm behind it absorbs exactly
 // (BnFinalizeArgs::in_scale); the backward pass uses the bf16 kernels on wscale * w and scales the weight gradient by wscale.
-struct ConvW { long off; int D0, D1, k, s, p; long packD, packU; int Hl = 0; /* large-side map (square) */ bool tr = false; /* ConvTranspose2d: forward = up */ bool fp8 = false; float wscale = 1.f; };
+struct ConvW { long off; int D0, D1, k, s, p; long packD, packU; int Hl = 0; /* large-side map (square) */ bool tr = false; /* ConvTranspose2d: forward = up */ bool fp8 = false; float wscale = 1.f;
+               bool fragD = false, fragU = false; /* the down / up form is packed fragment-major (Net::settle_layout) */ };
 struct Bn {
   long g_off, b_off, rm_off, rv_off; int nbt_idx; int C; long ws;   // ws: float offset of this BN's scratch in Plan::bnws
   // the scratch: kRows rows of row_floats() floats -- batch statistics, the folded forward affine, the coefficients of dx = A*g + B*y + C
@@ -156,7 +157,7 @@ class Net {
   int dt() const { return cfg.dtype; }
   size_t esz() const { return dtype_size(cfg.dtype); }
   ConvW add_conv(const std::string& name, int D0, int D1, int k, int s, int p, bool pack, bool transposed = false);
-  void settle_fp8(ConvW& w) const;
+  void settle_layout(ConvW& w) const;
   Bn add_bn(const std::string& prefix, int C);
   void add_entry(const std::string& name, std::initializer_list<int> shape, int kind, long off);
 
@@ -164,9 +165,6 @@ class Net {
   int packs_enc_bwd(const Pass& ps, hipStream_t s);
   int packs_dec_fwd(const Pass& ps, hipStream_t s);
   int packs_dec_bwd(const Pass& ps, bool need_denc, hipStream_t s);
-  // fragment-major packing (deep2_conv_kernel) of the down / up form of a conv at its place in the net
-  int frag_down(const ConvW& w) const;
-  int frag_up(const ConvW& w) const;
   int pack_down(const Pass& ps, const ConvW& w, hipStream_t s);
   int pack_up(const Pass& ps, const ConvW& w, hipStream_t s);
   // w2 / x2 (optional): the 1x1 conv whose "up" form over x2 (a tensor on the small-side grid) is added in the same kernel
