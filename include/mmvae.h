@@ -278,6 +278,43 @@ MMVAE_API int mmvae_resize_quantise_normalise(const uint8_t* frames, int64_t fra
                                               const int32_t* h_bounds, const int32_t* h_coeffs, int h_ksize, const int32_t* v_bounds,
                                               const int32_t* v_coeffs, int v_ksize, const float* centres, int q, float mean, float stdv,
                                               int64_t* labels, float* image, uint8_t* resized, void* stream);
+/* ------------------------------------------------------------------ picture panels (the plot branch, main.py:205-359, utils.py:77-83)
+ * Pick rule, shared by the two calls below: the Q f32 logits of one pixel -> a label in [0, Q).  1 <= Q <= 16 (else
+ * MMVAE_ERR_UNSUPPORTED).  MMVAE_PICK_ARGMAX: the lowest index among equal maxima (strict > scan from index 0; a NaN never wins, an
+ * all-NaN pixel gives 0).  MMVAE_PICK_SAMPLE: f32 softmax (maximum subtracted, expf, sum in channel order), then
+ * label = #{k in [0, Q-2] : cdf_k <= u}, cdf accumulated in channel order -- the draw rule of mmvae_pixelcnn_sample. */
+#define MMVAE_PICK_ARGMAX 0
+#define MMVAE_PICK_SAMPLE 1
+/* logits f32 planar [N][Q][HW] (what the forward passes return); uniforms f32 [N][HW] in [0, 1), read in sample mode only (may be NULL
+ * otherwise); labels int64 [N][HW]. */
+MMVAE_API int mmvae_logits_to_labels(const float* logits, int N, int Q, int HW, int mode, const float* uniforms, int64_t* labels,
+                                     void* stream);
+/* One column of a contact sheet: n planes of S x S.  src by kind:
+ *   LABELS_U8 / LABELS_I64  [n][S*S]: byte = lut[label]; a label outside [0, Q) gives 0;
+ *   LOGITS_ARGMAX / _SAMPLE [n][Q][S*S] f32: the pick rule above (uniforms [n][S*S] for _SAMPLE), then lut;
+ *   IMAGE_F32               [n][S*S] f32: x = (v - lo) / (hi - lo) * 255 in f32, byte = clamp(floor(x + 0.5), 0, 255), NaN gives 0; needs
+ *                           hi > lo; Q, lut and uniforms are ignored.
+ * lut: Q device bytes (the grey of each class). */
+#define MMVAE_PANEL_LABELS_U8 0
+#define MMVAE_PANEL_LABELS_I64 1
+#define MMVAE_PANEL_LOGITS_ARGMAX 2
+#define MMVAE_PANEL_LOGITS_SAMPLE 3
+#define MMVAE_PANEL_IMAGE_F32 4
+#define MMVAE_PANEL_MAX_COLS 8
+typedef struct mmvae_panel_col {
+  int32_t kind;
+  const void* src;
+  int32_t Q;
+  const float* uniforms;
+  const uint8_t* lut;
+  float lo, hi;
+} mmvae_panel_col;
+/* The whole sheet in one launch: out uint8 [n * S][ncols * S], row-major; column c fills bytes [:, c*S : (c+1)*S] with its n planes
+ * stacked vertically (the reference's x[:6].view(-1, S) strip).  cols: HOST array of ncols descriptors, copied into the launch (it may
+ * be freed when the call returns); the pointers inside are device pointers.  1 <= ncols <= MMVAE_PANEL_MAX_COLS, n >= 1,
+ * 1 <= S <= 64.  Every byte of out is written exactly once, none outside it; no atomics: the same bytes every run. */
+MMVAE_API int mmvae_panel_sheet(const mmvae_panel_col* cols, int ncols, int n, int S, uint8_t* out, void* stream);
+
 /* torch.optim.Adam defaults (main.py:468) over a flat buffer: bc1 = 1-beta1^t, bc2_sqrt = sqrt(1-beta2^t);
  * grad_scale multiplies the gradient first (1/world_size after a sum all-reduce). */
 MMVAE_API int mmvae_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,

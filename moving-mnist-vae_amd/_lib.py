@@ -71,6 +71,8 @@ PROTOTYPES = {
     "mmvae_resample_coeffs": (c_int, [c_int, c_int, POINTER(c_int), P, P]),
     "mmvae_resize_quantise_normalise": (c_int, [P, c_int64, P, c_int, c_int64, c_int, c_int, c_int, c_int, P, P, c_int, P, P, c_int, P, c_int,
                                                 c_float, c_float, P, P, P, P]),
+    "mmvae_logits_to_labels": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P]),
+    "mmvae_panel_sheet": (c_int, [P, c_int, c_int, c_int, P, P]),
     "mmvae_adam_step": (c_int, [P, P, P, P, c_int64, c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_float, P]),
     "mmvae_adam_step_dev": (c_int, [P, P, P, P, c_int64, c_float, c_float, c_float, c_float, c_float, P, c_float, P]),
     "mmvae_grad_norm_sq": (c_int, [P, c_int64, c_float, P, P, P]),
@@ -113,6 +115,17 @@ PROTOTYPES = {
 
 class MmvaeError(RuntimeError):
     pass
+
+
+PICK_ARGMAX, PICK_SAMPLE = 0, 1                                  # MMVAE_PICK_*
+PANEL_LABELS_U8, PANEL_LABELS_I64, PANEL_LOGITS_ARGMAX, PANEL_LOGITS_SAMPLE, PANEL_IMAGE_F32 = range(5)      # MMVAE_PANEL_*
+PANEL_MAX_COLS, PANEL_MAX_Q, PANEL_MAX_S = 8, 16, 64
+
+
+class PanelCol(ctypes.Structure):
+    """mmvae_panel_col of include/mmvae.h: one column of mmvae_panel_sheet (the pointers are device pointers)."""
+    _fields_ = [("kind", c_int32), ("src", c_void_p), ("Q", c_int32), ("uniforms", c_void_p), ("lut", c_void_p), ("lo", c_float),
+                ("hi", c_float)]
 
 
 def lib():

@@ -336,6 +336,13 @@ int mmvae_resize_quantise_normalise(const uint8_t* frames, int64_t frame_stride_
                                           (long)n_frames, in_h, in_w, out_h, out_w, h_bounds, h_coeffs, h_ksize, v_bounds, v_coeffs, v_ksize,
                                           centres, q, mean, stdv, reinterpret_cast<long long*>(labels), image, resized, stream_of(st));
 }
+// ---- picture panels (pointers and ranges are checked in the launchers, before anything is enqueued)
+int mmvae_logits_to_labels(const float* logits, int N, int Q, int HW, int mode, const float* uniforms, int64_t* labels, void* st) {
+  return launch_logits_to_labels(logits, N, Q, HW, mode, uniforms, reinterpret_cast<long long*>(labels), stream_of(st));
+}
+int mmvae_panel_sheet(const mmvae_panel_col* cols, int ncols, int n, int S, uint8_t* out, void* st) {
+  return launch_panel_sheet(cols, ncols, n, S, out, stream_of(st));
+}
 int mmvae_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd, float bc1,
                     float bc2_sqrt, float grad_scale, void* st) {
   AdamArgs a{p, g, m, v, (long)n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale};

@@ -413,6 +413,10 @@ int launch_resize_quantise_normalise(const unsigned char* frames, long frame_str
                                      long n_frames, int in_h, int in_w, int out_h, int out_w, const int* h_bounds, const int* h_coeffs,
                                      int h_ksize, const int* v_bounds, const int* v_coeffs, int v_ksize, const float* centres, int q,
                                      float mean, float stdv, long long* labels, float* image, unsigned char* resized, hipStream_t s);
+// picture panels (panels.hip): logits [N][Q][HW] -> labels by the shared pick rule (mode: MMVAE_PICK_*), and a whole uint8 contact sheet
+// [n * S][ncols * S] from ncols column descriptors (host array, passed to the kernel by value)
+int launch_logits_to_labels(const float* logits, int N, int Q, int HW, int mode, const float* uniforms, long long* labels, hipStream_t s);
+int launch_panel_sheet(const mmvae_panel_col* cols, int ncols, int n, int S, unsigned char* out, hipStream_t s);
 int launch_convert(int dt_in, int dt_out, const void* in, void* out, long n, hipStream_t s);
 int launch_fill_f32(float* p, float v, long n, hipStream_t s);
 int launch_concat2_to_t(int dt, const float* a, const float* b, int rows, int ca, int cb, void* out, hipStream_t s);

@@ -168,6 +168,36 @@ def draw_labels(probs, u):
     return (cdf <= u.unsqueeze(-1)).sum(dim=-1)
 
 
+@torch.no_grad()
+def decode_labels(logits, mode="argmax", uniforms=None, generator=None):
+    """Class labels of a logits tensor (N, Q, H, W) -- what ``forward``, ``get_reconstruction`` and ``run_pixelcnn`` return for a
+    categorical model -- as int64 (N, H, W), one kernel (mmvae_logits_to_labels), 1 <= Q <= 16.  ``mode="argmax"``: the lowest index
+    among equal maxima (``logits.argmax(dim=1)`` away from ties; a NaN never wins).  ``mode="sample"``: one draw per pixel from the
+    f32 softmax by ``draw_labels``'s rule with ``u = uniforms[n, h * W + w]``; ``uniforms=None`` draws them with
+    ``torch.rand((N, H * W), generator=generator)`` (the reference's utils.sample_from_recostruction, utils.py:77-83, with another
+    random stream than torch.multinomial)."""
+    if mode not in ("argmax", "sample"):
+        raise ValueError("mode is 'argmax' or 'sample'")
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 4 or not logits.is_cuda:
+        raise ValueError("decode_labels expects logits of shape (N, Q, H, W) on the GPU")
+    x = logits.detach().contiguous().float()
+    N, Q, H, W = x.shape
+    u = None
+    if mode == "sample":
+        if uniforms is None:
+            uniforms = torch.rand((N, H * W), device=x.device, generator=generator)
+        u = uniforms.to(x.device).contiguous().float()
+        if u.numel() != N * H * W:
+            raise ValueError(f"uniforms must hold N * H * W = {N * H * W} values, got {tuple(uniforms.shape)}")
+    labels = torch.empty((N, H, W), dtype=torch.int64, device=x.device)
+    if labels.numel() == 0:
+        return labels
+    with torch.cuda.device(x.device):
+        check(lib().mmvae_logits_to_labels(ptr(x), N, Q, H * W, 1 if mode == "sample" else 0, ptr(u), ptr(labels), _stream()),
+              "mmvae_logits_to_labels")
+    return labels
+
+
 class _PixelFn(torch.autograd.Function):
     """PixelCNN.forward (model.py:248-255) through mmvae_pixelcnn_fwd / _bwd."""
 
@@ -835,6 +865,10 @@ class VAE(nn.Module):
         if self._hp is None:
             return decoder_output
         return self.run_pixelcnn(torch.cat([decoder_output, sample.to(decoder_output.dtype)], dim=1))
+
+    def decode_labels(self, logits, mode="argmax", uniforms=None, generator=None):
+        """``decode_labels`` of this module: class labels int64 (N, H, W) of a logits tensor (N, Q, H, W), by argmax or one draw per pixel."""
+        return decode_labels(logits, mode=mode, uniforms=uniforms, generator=generator)
 
     def kl_divergence(self, encoding_mu, encoding_logvar):     # model.py:364-365
         acc = torch.zeros(1 + SUM_PARTIALS, dtype=torch.float64, device=encoding_mu.device)       # the sum, then its scratch
