@@ -315,6 +315,32 @@ typedef struct mmvae_panel_col {
  * 1 <= S <= 64.  Every byte of out is written exactly once, none outside it; no atomics: the same bytes every run. */
 MMVAE_API int mmvae_panel_sheet(const mmvae_panel_col* cols, int ncols, int n, int S, uint8_t* out, void* stream);
 
+/* ------------------------------------------------------------------ latent diagnostics (scatter_plot, main.py:166-183)
+ * Density panel of n 2-D points, the picture behind the reference's scatter plot of q(z|x) against p(z): point p is
+ * (pts[p*stride + col_x], pts[p*stride + col_y]) (an (N, z, 1, 1) encoding in place: stride = z; the reference plots dimensions 0, 1).
+ * xform: 4 DEVICE floats {xlim, ylim, sx, sy} (the caller computes the limits with tensor operations, no host read; sx = 8*side/xlim,
+ * sy = 8*side/ylim map [-lim, lim] onto 16 sub-positions per pixel; the kernel does not recompute them).  In f32, in exactly this order
+ * (an add, then a multiply: nothing contracts to an fma):
+ *   qx = (int)floorf((x + xlim) * sx),   qy = (int)floorf((ylim - y) * sy)          (y points up)
+ * Pixel (row i, column j) is covered by the point iff (16 j + 8 - qx)^2 + (16 i + 8 - qy)^2 <= radius16^2, in integers.  With k(i, j) the
+ * number of covering points, out[i * out_row_stride + j] = tone[min(k, 255)] for 0 <= i, j < side (tone: 256 device bytes): every byte of
+ * the panel is written, none outside it (the row stride lets two panels share a sheet).  A point with a non-finite coordinate, or whose
+ * disc misses the panel, is skipped; a huge finite value cannot overflow.  n = 0 gives tone[0] everywhere.  One launch, integer counts
+ * in LDS: no global atomics, no zero-filled buffer, the same bytes every run and for every order of the points.
+ * side: a multiple of 16 in [16, 512], radius16 in [12, 128] (sixteenths of a pixel; at 12 every point inside the panel covers its own
+ * pixel) -- else MMVAE_ERR_UNSUPPORTED; n >= 0, stride >= 1, 0 <= col_x, col_y < stride, out_row_stride >= side, no NULL pointer (pts
+ * may be NULL when n = 0) -- else MMVAE_ERR_ARG.  Nothing is enqueued on an error.
+ * This is a density image under the rule above, not a pixel copy of a matplotlib figure (no antialiased marker edges, axes or labels). */
+MMVAE_API int mmvae_scatter_panel(const float* pts, int64_t n, int stride, int col_x, int col_y, const float* xform, int side, int radius16,
+                                  const uint8_t* tone, uint8_t* out, int64_t out_row_stride, void* stream);
+/* Per-dimension sums over the N images of a batch, acc f64 [6][d]; mu, logvar, enc f32 [N][d]; every term is formed in double from the
+ * f32 inputs.  Rows: 0 sum mu, 1 sum mu^2, 2 sum 0.5 (exp(logvar) + mu^2 - logvar - 1) (the KL of each dimension), 3 sum exp(logvar),
+ * 4 sum enc, 5 sum enc^2.  logvar NULL: rows 2, 3 are zero; enc NULL: rows 4, 5 are zero.  accumulate = 0 writes the rows, 1 adds to
+ * what is there (carry one accumulator over a data loader).  Fixed order, no atomics: the bits depend on the inputs only.
+ * 1 <= d <= 512 (else MMVAE_ERR_UNSUPPORTED), N >= 1, accumulate in {0, 1}, mu and acc not NULL (else MMVAE_ERR_ARG). */
+MMVAE_API int mmvae_latent_stats(const float* mu, const float* logvar, const float* enc, int N, int d, int accumulate, double* acc,
+                                 void* stream);
+
 /* torch.optim.Adam defaults (main.py:468) over a flat buffer: bc1 = 1-beta1^t, bc2_sqrt = sqrt(1-beta2^t);
  * grad_scale multiplies the gradient first (1/world_size after a sum all-reduce). */
 MMVAE_API int mmvae_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,

@@ -343,6 +343,14 @@ int mmvae_logits_to_labels(const float* logits, int N, int Q, int HW, int mode, 
 int mmvae_panel_sheet(const mmvae_panel_col* cols, int ncols, int n, int S, uint8_t* out, void* st) {
   return launch_panel_sheet(cols, ncols, n, S, out, stream_of(st));
 }
+// ---- latent diagnostics (arguments are checked in the launchers)
+int mmvae_scatter_panel(const float* pts, int64_t n, int stride, int col_x, int col_y, const float* xform, int side, int radius16,
+                        const uint8_t* tone, uint8_t* out, int64_t out_row_stride, void* st) {
+  return launch_scatter_panel(pts, (long)n, stride, col_x, col_y, xform, side, radius16, tone, out, (long)out_row_stride, stream_of(st));
+}
+int mmvae_latent_stats(const float* mu, const float* logvar, const float* enc, int N, int d, int accumulate, double* acc, void* st) {
+  return launch_latent_stats(mu, logvar, enc, N, d, accumulate, acc, stream_of(st));
+}
 int mmvae_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd, float bc1,
                     float bc2_sqrt, float grad_scale, void* st) {
   AdamArgs a{p, g, m, v, (long)n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale};

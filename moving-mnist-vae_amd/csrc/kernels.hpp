@@ -417,6 +417,13 @@ int launch_resize_quantise_normalise(const unsigned char* frames, long frame_str
 // [n * S][ncols * S] from ncols column descriptors (host array, passed to the kernel by value)
 int launch_logits_to_labels(const float* logits, int N, int Q, int HW, int mode, const float* uniforms, long long* labels, hipStream_t s);
 int launch_panel_sheet(const mmvae_panel_col* cols, int ncols, int n, int S, unsigned char* out, hipStream_t s);
+// latent diagnostics (latent_diag.hip): the density panel of n 2-D points pts[p * stride + col_x / col_y] (xform: device {xlim, ylim, sx, sy};
+// byte = tone[min(#covering discs, 255)], out rows out_row_stride bytes apart), and acc[6][d] f64 per-dimension sums over N images of
+// mu, mu^2, the KL term, exp(logvar), enc, enc^2 (logvar / enc nullable: their rows are zero; accumulate: add to acc instead of writing).
+// Both check their arguments before anything is enqueued.
+int launch_scatter_panel(const float* pts, long n, int stride, int col_x, int col_y, const float* xform, int side, int radius16,
+                         const unsigned char* tone, unsigned char* out, long out_row_stride, hipStream_t s);
+int launch_latent_stats(const float* mu, const float* logvar, const float* enc, int N, int d, int accumulate, double* acc, hipStream_t s);
 int launch_convert(int dt_in, int dt_out, const void* in, void* out, long n, hipStream_t s);
 int launch_fill_f32(float* p, float v, long n, hipStream_t s);
 int launch_concat2_to_t(int dt, const float* a, const float* b, int rows, int ca, int cb, void* out, hipStream_t s);

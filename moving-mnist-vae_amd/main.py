@@ -8,8 +8,11 @@ plotting branch (``main.py:401-424``) hangs off ``args.plot_callback``:
 (``plot_vae`` / ``plot_pixelcnn`` / ``plot_pixelvae``, ``main.py:205-359``) as
 8-bit greyscale contact sheets on the device (``render_sheet``, one kernel
 launch per sheet) and writes them as PNG files (``write_png_gray``, standard
-library only).  matplotlib figures, the scatter plot and wandb stay with the
-caller: the callback keeps what they need in ``.last``.
+library only).  The reference's scatter plot of q(z|x) against p(z)
+(``scatter_plot``, ``main.py:166-183``) is rendered on the device as well, as a
+density panel (``scatter_panel``; opt-in from the plot functions with
+``scatter=True``).  matplotlib figures and wandb stay with the caller: the
+callback keeps what they need in ``.last``.
 
 Nothing here does arithmetic on the hot path when the model is the HIP
 ``VAE`` of this package: batch preparation, forward, loss, backward and the
@@ -106,7 +109,7 @@ def train(model, data_loader, optimizer, device, args, epoch=0, data_mean=0, dat
 
 
 def evaluate(model, data_loader, device, args, data_mean=0, data_std=1, iw_samples=0, weighted=False, generator=None,
-             return_per_image=False) -> dict:
+             return_per_image=False, latent_stats=False) -> dict:
     """Held-out evaluation of the HIP model (the reference builds a test loader, main.py:497, and never reads it): one eval-mode pass
     over ``data_loader`` under ``torch.no_grad()``; the model's train / eval mode is restored afterwards and no parameter or buffer
     changes.  Batches are prepared as in ``train``.  Per-image terms come from ``model.per_image_terms`` (and ``model.iw_bound``
@@ -117,7 +120,15 @@ def evaluate(model, data_loader, device, args, data_mean=0, data_std=1, iw_sampl
     ``elbo`` = -(nll + kl), ``iw_bound`` (None when ``iw_samples`` == 0) and ``bits_per_dim`` = nll / (C S S ln 2) for categorical
     models (None for Gaussian ones: a density, not a code length).  A PixelCNN on its own has no latent: ``kl``, ``elbo`` and
     ``iw_bound`` are None.  ``generator`` (a device generator) draws every noise tensor; None uses the global one.
-    ``return_per_image=True`` adds ``per_image``: {'nll', 'kl', 'iw_bound'} as concatenated f64 device tensors (or None)."""
+    ``return_per_image=True`` adds ``per_image``: {'nll', 'kl', 'iw_bound'} as concatenated f64 device tensors (or None).
+    ``latent_stats=True`` adds ``latent``: per-dimension diagnostics of the latent code (f64 numpy arrays of length z) from one
+    ``latent_stats`` accumulator carried over the loader and read once at the end -- ``kl_per_dim`` (mean per image of each dimension's
+    KL; which dimensions have collapsed to the prior), ``mu_mean`` / ``mu_var`` (mean and population variance of the posterior means),
+    ``active_units`` (dimensions with ``mu_var > 0.01``, Burda et al. 2016), ``mean_posterior_var`` (mean of exp(logvar)), ``z_mean`` /
+    ``z_var`` (of the sampled codes: the aggregate posterior's moments).  Without a logvar ``kl_per_dim`` and ``mean_posterior_var`` are
+    None; a PixelCNN on its own has ``latent`` None.  Under this flag ``kl`` (and ``elbo``) are taken from the same accumulator, whose
+    terms are formed in f64: ``sum(kl_per_dim) == kl`` up to f64 summation order, and ``kl`` moves by the f32 rounding of the
+    per-image kernel's terms (a few 1e-8 relative) against the value without the flag."""
     if not hasattr(model, "per_image_terms"):
         raise TypeError("evaluate() drives the HIP VAE of this package (it needs model.per_image_terms)")
     latent = not model.only_pixelcnn
@@ -125,6 +136,7 @@ def evaluate(model, data_loader, device, args, data_mean=0, data_std=1, iw_sampl
     weight = getattr(args, "data_ratio_of_labels", None) if (weighted and categorical) else None
     was_training = bool(model.training)
     sums = None                                    # f64 device: nll, kl, iw
+    want_latent, acc = bool(latent_stats) and latent, None      # acc: f64 device [6][z], see latent_stats()
     kept = {"nll": [], "kl": [], "iw_bound": []}
     n_images = 0
     model.eval()
@@ -139,11 +151,13 @@ def evaluate(model, data_loader, device, args, data_mean=0, data_std=1, iw_sampl
                     model.injected_eps = torch.randn((N, model.z_dimensions, 1, 1), device=image.device, dtype=torch.float32, generator=generator)
                     injected = True
                 try:
-                    mu, logvar, _, reconstruction = model(image, sample=image)          # PixelVAE: teacher-forced on the image itself
+                    mu, logvar, encoding, reconstruction = model(image, sample=image)   # PixelVAE: teacher-forced on the image itself
                 finally:
                     if injected:
                         model.injected_eps = None
                 nll, kl = model.per_image_terms(target, mu, logvar, reconstruction, weight=weight)
+                if want_latent:
+                    acc, have_lv = _latent_stats_into(model, mu, logvar, encoding, acc), logvar is not None
                 iw = model.iw_bound(image, target, iw_samples, generator=generator, weight=weight) if iw_samples else None
                 if sums is None:
                     sums = torch.zeros(3, dtype=torch.float64, device=nll.device)
@@ -164,12 +178,64 @@ def evaluate(model, data_loader, device, args, data_mean=0, data_std=1, iw_sampl
     if n_images == 0:
         raise ValueError("evaluate(): the data loader yielded no batch")
     s_nll, s_kl, s_iw = (v / n_images for v in sums.tolist())                           # the one device -> host copy
+    latent_out = None
+    if want_latent:
+        a = acc.cpu().numpy()                                                           # ... and the accumulator's
+        mu_mean, z_mean = a[0] / n_images, a[4] / n_images
+        mu_var = np.maximum(a[1] / n_images - mu_mean * mu_mean, 0.0)
+        latent_out = {"kl_per_dim": a[2] / n_images if have_lv else None, "mu_mean": mu_mean, "mu_var": mu_var,
+                      "active_units": int((mu_var > 0.01).sum()), "mean_posterior_var": a[3] / n_images if have_lv else None,
+                      "z_mean": z_mean, "z_var": np.maximum(a[5] / n_images - z_mean * z_mean, 0.0)}
+        if have_lv:
+            s_kl = float(a[2].sum()) / n_images
     dims = model.in_channels * model.input_image_size ** 2
     out = {"n_images": n_images, "nll": s_nll, "kl": s_kl if latent else None, "elbo": -(s_nll + s_kl) if latent else None,
            "iw_bound": s_iw if iw_samples else None, "bits_per_dim": s_nll / (dims * float(np.log(2.0))) if categorical else None}
     if return_per_image:
         out["per_image"] = {k: (torch.cat(v) if v else None) for k, v in kept.items()}
+    if latent_stats:
+        out["latent"] = latent_out
     return out
+
+
+def _latent_stats_into(model, mu, logvar, encoding, acc):
+    from . import _lib as L
+    d = int(model.z_dimensions)
+    if mu is None:
+        raise ValueError("latent_stats needs the posterior means (a PixelCNN on its own has no latent)")
+    dev = mu.device
+    N = int(mu.shape[0])
+
+    def rows(t, what):
+        if t is None:
+            return None
+        t = t.detach().float().contiguous()
+        if t.device != dev or t.numel() != N * d:
+            raise ValueError(f"latent_stats: {what} {tuple(t.shape)} on {t.device} does not hold {N} x {d} values on {dev}")
+        return t
+
+    m, lv, enc = rows(mu, "mu"), rows(logvar, "logvar"), rows(encoding, "encoding")
+    accumulate = acc is not None
+    if acc is None:
+        acc = torch.empty((L.LATENT_STATS_ROWS, d), dtype=torch.float64, device=dev)
+    elif (not isinstance(acc, torch.Tensor) or acc.dtype != torch.float64 or tuple(acc.shape) != (L.LATENT_STATS_ROWS, d)
+          or acc.device != dev or not acc.is_contiguous()):
+        raise ValueError(f"latent_stats: acc must be a contiguous float64 ({L.LATENT_STATS_ROWS}, {d}) tensor on {dev}")
+    with torch.cuda.device(dev):
+        L.check(L.lib().mmvae_latent_stats(L.ptr(m), L.ptr(lv), L.ptr(enc), N, d, int(accumulate), L.ptr(acc),
+                                           torch.cuda.current_stream().cuda_stream), "mmvae_latent_stats")
+    return acc
+
+
+def latent_stats(model, mu, logvar, encoding, acc=None):
+    """Per-dimension f64 sums over the images of a batch, on the device in one launch (mmvae_latent_stats), no host read: a (6, z)
+    float64 device tensor with rows sum ``mu``, sum ``mu^2``, sum ``0.5 (exp(logvar) + mu^2 - logvar - 1)`` (each dimension's KL), sum
+    ``exp(logvar)``, sum ``encoding``, sum ``encoding^2``, every term formed in double from the f32 inputs.  ``mu`` / ``logvar`` /
+    ``encoding``: what ``model(image)`` returns, (N, z, 1, 1) or (N, z); ``logvar`` / ``encoding`` may be None (their rows are zero).
+    ``acc=None`` returns a fresh accumulator; passing the one an earlier call returned ADDS this batch to it, so one tensor is carried
+    over a data loader and divided by the image count at the end (``evaluate(..., latent_stats=True)`` does that).  Fixed order, no
+    atomics: the same bits every run."""
+    return _latent_stats_into(model, mu, logvar, encoding, acc)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -832,6 +898,133 @@ def write_png_gray(path, sheet):
     return path
 
 
+_SCATTER_TONES = {}                    # device -> scatter_tone() there (the default table is copied once per device)
+
+
+def scatter_tone(alpha=0.1):
+    """The grey of a pixel under k overlapping markers, a uint8 (256,) host tensor: ``tone[k] = round(255 (1 - alpha)^k)`` -- black
+    ink of opacity ``alpha`` (the reference's ``alpha=0.1``, main.py:172-173) composited k times over white; counts saturate at 255."""
+    alpha = float(alpha)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError("scatter_tone: alpha must lie in [0, 1]")
+    k = np.arange(256, dtype=np.float64)
+    return torch.from_numpy(np.floor(255.0 * (1.0 - alpha) ** k + 0.5).astype(np.uint8))
+
+
+def _scatter_points(points, what):
+    if not isinstance(points, torch.Tensor) or not points.is_cuda:
+        raise ValueError(f"{what} expects a float32 tensor on the GPU")
+    if points.dtype != torch.float32:
+        raise ValueError(f"{what}: expected float32 points, got {points.dtype}")
+    if points.dim() == 4 and points.shape[2] == 1 and points.shape[3] == 1:
+        points = points.reshape(points.shape[0], points.shape[1])
+    if points.dim() != 2 or points.shape[1] < 1:
+        raise ValueError(f"{what}: expected points of shape (N, z) or (N, z, 1, 1), got {tuple(points.shape)}")
+    return points.detach().contiguous()
+
+
+def _scatter_xform(pts, dims, lims, side):
+    """The four device floats of mmvae_scatter_panel, {xlim, ylim, 8 side / xlim, 8 side / ylim}, without a host read.  lims None:
+    ``max|.| + 4`` per axis (main.py:170-171; 4 for no points)."""
+    if lims is None:
+        if pts.shape[0] == 0:
+            lim = torch.full((2,), 4.0, dtype=torch.float32, device=pts.device)
+        else:
+            lim = pts[:, list(dims)].abs().amax(dim=0) + 4.0
+    else:
+        lim = torch.as_tensor(lims, dtype=torch.float32).to(pts.device).reshape(-1)
+        if lim.numel() != 2:
+            raise ValueError("scatter_panel: lims is (xlim, ylim)")
+    return torch.cat([lim, float(8 * side) / lim]).contiguous()
+
+
+def _scatter_launch(pts, dims, xform, side, radius16, tone, out):
+    from . import _lib as L
+    with torch.cuda.device(pts.device):
+        L.check(L.lib().mmvae_scatter_panel(L.ptr(pts) if pts.shape[0] else None, pts.shape[0], pts.shape[1], dims[0], dims[1], L.ptr(xform),
+                                            side, radius16, L.ptr(tone), L.ptr(out), out.stride(0), torch.cuda.current_stream().cuda_stream),
+                "mmvae_scatter_panel")
+    return out
+
+
+def _scatter_args(points, dims, side, radius, tone, out, what):
+    from . import _lib as L
+    pts = _scatter_points(points, what)
+    dims = tuple(int(v) for v in dims)
+    if len(dims) != 2 or not all(0 <= v < pts.shape[1] for v in dims):
+        raise ValueError(f"{what}: dims {dims} outside the {pts.shape[1]} columns of the points")
+    side = int(side)
+    if side % 16 or not 16 <= side <= L.SCATTER_MAX_SIDE:
+        raise ValueError(f"{what}: side {side} unsupported (a multiple of 16 in 16..{L.SCATTER_MAX_SIDE})")
+    radius16 = int(round(float(radius) * 16.0))
+    if not L.SCATTER_MIN_RADIUS16 <= radius16 <= L.SCATTER_MAX_RADIUS16:
+        raise ValueError(f"{what}: radius {radius} unsupported ({L.SCATTER_MIN_RADIUS16 / 16}..{L.SCATTER_MAX_RADIUS16 / 16} pixels)")
+    if tone is None:
+        tone = _SCATTER_TONES.get(pts.device)
+        if tone is None:
+            tone = _SCATTER_TONES[pts.device] = scatter_tone().to(pts.device)
+    else:
+        tone = torch.as_tensor(tone)
+        if tone.dtype != torch.uint8 or tone.numel() != 256:
+            raise ValueError(f"{what}: tone is 256 uint8 values (scatter_tone())")
+        tone = tone.reshape(-1).to(pts.device).contiguous()
+    if out is None:
+        out = torch.empty((side, side), dtype=torch.uint8, device=pts.device)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (side, side) or out.device != pts.device
+          or out.stride(1) != 1 or out.stride(0) < side):
+        raise ValueError(f"{what}: out must be a uint8 ({side}, {side}) tensor on {pts.device} with contiguous rows (a slice of a sheet will do)")
+    return pts, dims, side, radius16, tone, out
+
+
+def scatter_panel(points, *, dims=(0, 1), lims=None, side=256, radius=4.0, tone=None, out=None):
+    """Density panel of 2-D points on the device, ONE launch (mmvae_scatter_panel): a uint8 (side, side) device tensor.  ``points``:
+    float32 (N, z) or (N, z, 1, 1) on the GPU, read in place; ``dims`` picks the two plotted columns (the reference plots latent
+    dimensions 0 and 1).  The panel spans [-xlim, xlim] x [-ylim, ylim], y pointing up; ``lims=None`` takes ``max|.| + 4`` per axis
+    as main.py:170-171 does, computed on the device without a host read; otherwise ``(xlim, ylim)`` as floats or a tensor.  Every point
+    is a disc of ``radius`` pixels (0.75 .. 8, in sixteenths) placed on a grid of 16 sub-positions per pixel; a pixel whose centre lies
+    under k discs gets ``tone[k]`` (``scatter_tone()`` by default: k markers of alpha 0.1 over white).  Points with a non-finite
+    coordinate or outside the limits by more than their radius are skipped.  ``out``: a uint8 (side, side) view with contiguous rows
+    to render into (half of a sheet).  Integer counts: the same bytes every run and for every order of the points.  This is a density
+    image under that rule, not a pixel copy of a matplotlib figure: no antialiased marker edges, axes, titles or tick labels."""
+    pts, dims, side, radius16, tone, out = _scatter_args(points, dims, side, radius, tone, out, "scatter_panel")
+    return _scatter_launch(pts, dims, _scatter_xform(pts, dims, lims, side), side, radius16, tone, out)
+
+
+def scatter_plot(encoding, directory, epoch, plot_count, *, generator=None, prior=None, side=256, radius=4.0, save=True,
+                 return_tensors=False):
+    """main.py:166-183 on the device: one uint8 (side, 2 * side) sheet, ``p(z)`` on the left and ``q(z|x)`` on the right, written as
+    ``<directory>/scatter-<epoch>-<plot_count>.png`` with ``save``.  ``encoding``: (N, z) or (N, z, 1, 1) float32 on the GPU; its
+    dimensions 0 and 1 are plotted.  The prior points are ``torch.randn(N, 2)`` drawn through ``generator`` (``prior``: (N, 2) points
+    to use instead).  Both halves share the limits of ``q(z|x)``, ``max|.| + 4`` per axis (the reference's axes are sharex / sharey and
+    its limits come from the encoding).  Two ``scatter_panel`` launches into the halves of one sheet, no host read before the PNG.
+    ``return_tensors=True`` returns ``(sheet, {'prior', 'xform'})``: the prior points and the four device floats {xlim, ylim, sx, sy}
+    both panels were rendered with.  A density image, not a copy of the matplotlib figure (see ``scatter_panel``)."""
+    sheet_side = int(side)
+    pts, dims, side, radius16, tone, _ = _scatter_args(encoding, (0, 1), sheet_side, radius, None, None, "scatter_plot")
+    if pts.shape[1] < 2:
+        raise ValueError("scatter_plot needs at least two latent dimensions")
+    if prior is None:
+        prior = _draw(torch.randn, (pts.shape[0], 2), pts.device, generator)
+    prior = _scatter_points(prior.to(pts.device), "scatter_plot")
+    if prior.shape[1] != 2:
+        raise ValueError(f"scatter_plot: prior must be (N, 2), got {tuple(prior.shape)}")
+    xform = _scatter_xform(pts, dims, None, side)
+    sheet = torch.empty((side, 2 * side), dtype=torch.uint8, device=pts.device)
+    _scatter_launch(prior, (0, 1), xform, side, radius16, tone, sheet[:, :side])
+    _scatter_launch(pts, dims, xform, side, radius16, tone, sheet[:, side:])
+    if save:
+        import os
+        os.makedirs(directory, exist_ok=True)
+        write_png_gray(os.path.join(directory, "scatter-{}-{}.png".format(epoch, plot_count)), sheet)
+    return (sheet, {"prior": prior, "xform": xform}) if return_tensors else sheet
+
+
+def _add_scatter(sheets, tensors, encoding, generator):
+    """``scatter=True`` of the plot functions: the last sheet, from the last draw taken from ``generator``."""
+    sheets["scatter"], t = scatter_plot(encoding.detach().float(), None, 0, 0, generator=generator, save=False, return_tensors=True)
+    tensors["scatter_prior"], tensors["scatter_xform"] = t["prior"], t["xform"]
+
+
 def sample_from_reconstruction(reconstruction, uniforms=None, generator=None):
     """The reference's legacy ``utils.sample_from_recostruction`` (utils.py:77-83): one draw per pixel from the softmax of a logits tensor
     (N, Q, H, W), on the device (``decode_labels`` in sample mode).  Returns the int64 labels (N, H, W) -- the reference goes on to
@@ -904,7 +1097,7 @@ def _finish_plot(sheets, tensors, directory, epoch, plot_count, save, return_ten
 
 
 def plot_vae(model, device, image, reconstruction, encoding, directory, epoch, plot_count, *, data_mean=0.0, data_std=1.0, centres=None,
-             rows=6, generator=None, save=True, return_tensors=False, lo=None, hi=None):
+             rows=6, generator=None, save=True, return_tensors=False, lo=None, hi=None, scatter=False):
     """main.py:205-245 on the device.  Sheets (uint8 device tensors, written as ``<directory>/<name>-<epoch>-<plot_count>.png`` with
     ``save``): ``recon`` = Input | Reconstruction, ``normal_sampling`` = ``get_reconstruction(z)`` of ``z ~ N(0, I)`` drawn through
     ``generator``.  A categorical decoder (``decoder_out_channels > in_channels``) is rendered as the per-pixel argmax through
@@ -912,9 +1105,10 @@ def plot_vae(model, device, image, reconstruction, encoding, directory, epoch, p
     label 0 and label Q - 1, ``(k - data_mean) / data_std`` (the reference's plot_vae takes no statistics and lets imshow autoscale:
     pass the ones ``train`` was given).  Runs in eval mode under ``torch.no_grad()`` and restores the model's mode; no parameter or
     buffer changes.  ``rows``: images per column (the reference's 6; fewer if the batch is smaller).  At an odd ``input_image_size`` the
-    decoder's crop leaves one row and column too many (model.py:307-310); the sheet shows the leading S x S.  The reference's scatter plot of
-    ``encoding`` stays with the host (2N numbers the caller already holds).  ``return_tensors=True`` returns ``(sheets, tensors)``
-    with every tensor the columns were rendered from."""
+    decoder's crop leaves one row and column too many (model.py:307-310); the sheet shows the leading S x S.  ``scatter=True`` appends the
+    reference's scatter plot of the WHOLE ``encoding`` (main.py:244) as a last sheet, ``scatter`` (``scatter_plot``); its prior draw is the
+    last one taken from ``generator``, so the other sheets do not depend on the flag.  ``return_tensors=True`` returns
+    ``(sheets, tensors)`` with every tensor the columns were rendered from."""
     with _plot_mode(model):
         lo, hi, lut = _plot_setup(model, data_mean, data_std, centres, lo, hi)
         img = image[:rows].detach().float()
@@ -932,6 +1126,8 @@ def plot_vae(model, device, image, reconstruction, encoding, directory, epoch, p
                   "normal_sampling": render_sheet([col(output_random_encoding)], n)}
         tensors = {"image": img, "reconstruction": rec, "random_encoding": random_encoding,
                    "output_random_encoding": output_random_encoding, "lut": lut, "lo": lo, "hi": hi}
+        if scatter:
+            _add_scatter(sheets, tensors, encoding, generator)
     return _finish_plot(sheets, tensors, directory, epoch, plot_count, save, return_tensors)
 
 
@@ -957,13 +1153,14 @@ def plot_pixelcnn(model, device, image, reconstruction, directory, epoch, plot_c
 
 
 def plot_pixelvae(model, device, image, reconstruction, encoding, directory, epoch, plot_count, data_mean, data_std, *, centres=None,
-                  rows=6, generator=None, save=True, return_tensors=False, lo=None, hi=None):
+                  rows=6, generator=None, save=True, return_tensors=False, lo=None, hi=None, scatter=False):
     """main.py:283-359 on the device.  ``recon_z_`` = Input | z_image (one column per decoder channel) | argmax of the teacher-forced
     ``reconstruction`` | argmax of the free-running sampler's last logits | its drawn labels; ``normal-recon`` = the same five from
     ``z ~ N(0, I)``, the teacher-forced column being ``run_pixelcnn(cat([random_z_image, image[:rows]]))`` (main.py:343).  At most 4
-    decoder channels fit the 8 columns of a sheet.  Two deliberate deviations: each free-running pass starts from a fresh zero
-    ``sample`` (the reference hands the second pass the first one's filled sample, whose stale pixels its InstanceNorm then sees), and
-    the scatter plot stays with the host.  Sample columns are rendered from the drawn labels.  Otherwise as ``plot_vae``."""
+    decoder channels fit the 8 columns of a sheet.  One deliberate deviation: each free-running pass starts from a fresh zero
+    ``sample`` (the reference hands the second pass the first one's filled sample, whose stale pixels its InstanceNorm then sees).
+    Sample columns are rendered from the drawn labels.  ``scatter=True`` appends the ``scatter`` sheet of the whole ``encoding``
+    (main.py:358), its prior draw being the last one taken from ``generator``.  Otherwise as ``plot_vae``."""
     with _plot_mode(model):
         lo, hi, lut = _plot_setup(model, data_mean, data_std, centres, lo, hi)
         img, rec, enc = image[:rows].detach().float(), reconstruction[:rows].detach(), encoding[:rows].detach()
@@ -992,6 +1189,8 @@ def plot_pixelvae(model, device, image, reconstruction, encoding, directory, epo
                    "uniforms": uniforms, "random_encoding": random_encoding, "random_z_image": random_z_image,
                    "random_tf_logits": random_tf_logits, "random_free_logits": random_free_logits,
                    "random_free_labels": random_free_labels, "random_uniforms": random_uniforms, "lut": lut, "lo": lo, "hi": hi}
+        if scatter:
+            _add_scatter(sheets, tensors, encoding, generator)
     return _finish_plot(sheets, tensors, directory, epoch, plot_count, save, return_tensors)
 
 
@@ -1030,8 +1229,9 @@ def latent_slide(model, z_first, z_end, steps=6, *, data_mean=0.0, data_std=1.0,
 class _PlotCallback:
     """What ``make_plot_callback`` returns."""
 
-    def __init__(self, data_mean, data_std, centres, rows, generator, save):
+    def __init__(self, data_mean, data_std, centres, rows, generator, save, scatter=False):
         self.data_mean, self.data_std, self.centres, self.rows, self.generator, self.save = data_mean, data_std, centres, rows, generator, save
+        self.scatter = bool(scatter)
         self.plot_count, self.last, self._epoch = 0, None, None
 
     def __call__(self, *, model, image, reconstruction, encoding, epoch, index, directory, running):
@@ -1041,22 +1241,24 @@ class _PlotCallback:
         device = image.device
         if model.pixelcnn is None:                             # main.py:405-416
             sheets = plot_vae(model, device, image, reconstruction, encoding, directory, epoch, self.plot_count, data_mean=self.data_mean,
-                              data_std=self.data_std, **kw)
+                              data_std=self.data_std, scatter=self.scatter, **kw)
         elif model.only_pixelcnn:
             sheets = plot_pixelcnn(model, device, image, reconstruction, directory, epoch, self.plot_count, self.data_mean, self.data_std, **kw)
         else:
             sheets = plot_pixelvae(model, device, image, reconstruction, encoding, directory, epoch, self.plot_count, self.data_mean,
-                                   self.data_std, **kw)
+                                   self.data_std, scatter=self.scatter, **kw)
         self.last = {"sheets": sheets, "encoding": encoding, "running": running, "epoch": epoch, "index": index, "plot_count": self.plot_count}
         self.plot_count += 1
         return sheets
 
 
-def make_plot_callback(data_mean, data_std, centres=None, rows=6, generator=None, save=True):
+def make_plot_callback(data_mean, data_std, centres=None, rows=6, generator=None, save=True, scatter=False):
     """The plot branch of the reference's loop (main.py:401-424) as a callable for ``args.plot_callback``: ``train`` calls it every
     ``plot_every`` steps with the keywords ``model, image, reconstruction, encoding, epoch, index, directory, running``; it renders the
     sheets of ``plot_vae`` / ``plot_pixelcnn`` / ``plot_pixelvae`` (chosen as main.py:405-416 chooses), writes them under ``directory``
     with ``save``, numbers them with its own ``plot_count`` (restarting with every epoch, as the reference's does) and keeps the last
-    products in ``.last`` ({'sheets', 'encoding', 'running', 'epoch', 'index', 'plot_count'}: what a host-side scatter plot or logger
-    needs).  Pass a ``generator`` of its own to keep the plots' random draws out of the training's random stream."""
-    return _PlotCallback(data_mean, data_std, centres, rows, generator, save)
+    products in ``.last`` ({'sheets', 'encoding', 'running', 'epoch', 'index', 'plot_count'}: what a logger needs).  ``scatter=True``
+    adds the reference's scatter plot of the encoding (main.py:244, :358; the one item both branches log as 'Scatter Plot') as a last
+    sheet, ``scatter``, for models with a latent.  Pass a ``generator`` of its own to keep the plots' random draws out of the
+    training's random stream."""
+    return _PlotCallback(data_mean, data_std, centres, rows, generator, save, scatter)
