@@ -4,11 +4,12 @@ The directory name carries a hyphen (it mirrors the upstream repository name), s
 with ``importlib.import_module("moving-mnist-vae_amd")``.  Importing the package does not need
 a GPU; constructing / running the model does, and fails loudly when the HIP library is absent.
 """
-from .main import (MovingMNISTClips, QuantiserFit, checkpoint_variant, choose_transformer, clips_from_npz_array, column, evaluate, fit_quantiser,  # noqa: F401
-                   generate, generate_only_pixelcnn, gray_lut, latent_slide, latent_stats, load_checkpoint, load_kmeans_file,
-                   make_plot_callback, pixel_histogram, plot_pixelcnn, plot_pixelvae, plot_vae, quantise_frames, render_sheet,
-                   resize_frames, resize_quantise_frames, sample_from_reconstruction, save_checkpoint, save_kmeans_file, scatter_panel,
-                   scatter_plot, scatter_tone, select_model, train, write_png_gray)
+from .data import (MovingMNISTClips, QuantiserFit, choose_transformer, clips_from_npz_array, fit_quantiser, load_kmeans_file,  # noqa: F401
+                   pixel_histogram, quantise_frames, resize_frames, resize_quantise_frames, save_kmeans_file)
+from .main import (checkpoint_variant, evaluate, generate, generate_only_pixelcnn, latent_stats, load_checkpoint, save_checkpoint,  # noqa: F401
+                   select_model, train)
+from .panels import (column, gray_lut, latent_slide, make_plot_callback, plot_pixelcnn, plot_pixelvae, plot_vae, render_sheet,  # noqa: F401
+                     sample_from_reconstruction, scatter_panel, scatter_plot, scatter_tone, write_png_gray)
 
 
 def __getattr__(name):

@@ -181,6 +181,13 @@ def check(rc: int, what: str) -> int:
     return rc
 
 
+def call(name: str, device, *args) -> int:
+    """One launch off the train step: ``lib().<name>(*args, stream)`` on ``device``'s current stream, return code checked."""
+    import torch
+    with torch.cuda.device(device):
+        return check(getattr(lib(), name)(*args, torch.cuda.current_stream().cuda_stream), name)
+
+
 def ptr(t):
     """Device/host pointer of a tensor (None -> NULL)."""
     return None if t is None else t.data_ptr()

@@ -21,7 +21,7 @@ from typing import List, Optional
 import torch
 from torch import nn
 
-from ._lib import SUM_PARTIALS, MmvaeError, check, lib, ptr
+from ._lib import SUM_PARTIALS, MmvaeError, call, check, lib, ptr
 
 _DTYPES = {"f32": 0, "fp32": 0, "float32": 0, "bf16": 1, "bfloat16": 1, "fp8": 2}
 
@@ -192,9 +192,7 @@ def decode_labels(logits, mode="argmax", uniforms=None, generator=None):
     labels = torch.empty((N, H, W), dtype=torch.int64, device=x.device)
     if labels.numel() == 0:
         return labels
-    with torch.cuda.device(x.device):
-        check(lib().mmvae_logits_to_labels(ptr(x), N, Q, H * W, 1 if mode == "sample" else 0, ptr(u), ptr(labels), _stream()),
-              "mmvae_logits_to_labels")
+    call("mmvae_logits_to_labels", x.device, ptr(x), N, Q, H * W, 1 if mode == "sample" else 0, ptr(u), ptr(labels))
     return labels
 
 

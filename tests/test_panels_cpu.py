@@ -157,3 +157,14 @@ def test_new_names_are_exported(pkg):
                  "make_plot_callback", "sample_from_reconstruction", "decode_labels"):
         assert callable(getattr(pkg, name)), name
     assert "plot_callback" in importlib.import_module("moving-mnist-vae_amd.main").__doc__
+
+
+def test_main_carries_every_name_the_package_imports(pkg):
+    """The drop-in promise is "swap the import": the reference's main.py holds the input pipeline and the plot functions too, so
+    ``main`` re-exports what ``data`` and ``panels`` define -- the very objects the package hands out."""
+    import types
+    main = importlib.import_module("moving-mnist-vae_amd.main")
+    names = [n for n, v in vars(pkg).items() if not n.startswith("_") and not isinstance(v, types.ModuleType)]
+    assert len(names) >= 33 and {"train", "plot_vae", "scatter_plot", "quantise_frames", "MovingMNISTClips"} <= set(names)
+    for name in names:
+        assert getattr(pkg, name) is getattr(main, name), name

@@ -55,7 +55,7 @@ def _image_of(pkg, resized_np, centres, mean, std):
 
 def _raw(L, pkg, frames, stride, index, per_clip, n, in_hw, out_hw, centres, labels, image, resized, mean=0.0, std=1.0):
     """The C entry point itself, on the caller's outputs."""
-    M = importlib.import_module("moving-mnist-vae_amd.main")
+    M = importlib.import_module("moving-mnist-vae_amd.data")
     hb, hc, hk = M._resample_tables(in_hw[1], out_hw[1], "cuda:0")
     vb, vc, vk = M._resample_tables(in_hw[0], out_hw[0], "cuda:0")
     rc = L.lib().mmvae_resize_quantise_normalise(L.ptr(frames), stride, L.ptr(index), per_clip, n, in_hw[0], in_hw[1], out_hw[0], out_hw[1],
@@ -259,7 +259,7 @@ def test_two_calls_give_the_same_bits(pkg):
 
 
 def test_tables_are_built_once(pkg):
-    M = importlib.import_module("moving-mnist-vae_amd.main")
+    M = importlib.import_module("moving-mnist-vae_amd.data")
     x = torch.zeros((1, 24, 24), dtype=torch.uint8, device="cuda")
     pkg.resize_frames(x, 11)
     first = M._resample_tables(24, 11, x.device)

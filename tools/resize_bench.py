@@ -61,7 +61,7 @@ if a.host_only:
 import torch
 
 pkg = importlib.import_module("moving-mnist-vae_amd")
-M = importlib.import_module("moving-mnist-vae_amd.main")
+M = importlib.import_module("moving-mnist-vae_amd.data")
 assert torch.cuda.is_available(), "resize_bench needs a GPU"
 dev = torch.device("cuda:0")
 planes = torch.from_numpy(strokes_np(PLANES, 1)).to(dev)
