@@ -382,6 +382,25 @@ MMVAE_API int mmvae_conv2d_fwd(int dtype, int transposed, const void* x, const f
 /* dx [N,H,W,Cin] from dy [N,Ho,Wo,Cout] */
 MMVAE_API int mmvae_conv2d_dgrad(int dtype, int transposed, const void* dy, const float* weight, void* dx, int N, int H, int W, int Cin,
                        int Cout, int k, int stride, int pad, void* scratch, void* stream);
+/* The same data gradient with the two options the network's backward pass launches it with (mmvae_conv2d_dgrad is this call with neither,
+ * but for bf16 32 -> 32 3x3 stride 1 on 16x16 maps, which it runs as a per-wave stream):
+ *   accumulate != 0: dx += (dx must hold valid data of `dtype`) -- the identity blocks' main path onto the shortcut's share;
+ *   dy2 / w2 (nullable, both or neither): a second source.  w2 is a Conv2d weight (C2,Cin,1,1) f32 acting on the same input x as the main
+ *     layer, and its data gradient is added into dx by the same call (one kernel where the patch-tile kernel merges it, else a second,
+ *     accumulating launch):
+ *       transposed == 0: the 1x1 conv has the main layer's stride and pad 0 (encoder downsample.0); dy2 [N,Ho,Wo,C2]; its gradient lands on
+ *                        stride phase (0,0) of dx.  A stride-2 second source needs even H and W;
+ *       transposed == 1: the 1x1 conv has stride 1 (decoder conv1); dy2 [N,H,W,C2], on dx's grid.
+ * MMVAE_ERR_ARG, with nothing enqueued and dx untouched: accumulate together with a second source, dy2 without w2 (or w2 without dy2),
+ * an odd H or W under a stride-2 second source, a null dy / weight / dx / scratch.
+ * scratch: MMVAE_DGRAD_EX_SCRATCH_BYTES(numel(weight), numel(w2), sizeof(dtype)) bytes -- the packed main weights, then (256-byte aligned)
+ * the packed w2; with numel(w2) = 0 no more than mmvae_conv2d_dgrad's. */
+#define MMVAE_DGRAD_EX_W2_OFFSET(numel_w, esize) ((((size_t)(numel_w) * (esize) + 255) / 256) * 256)
+#define MMVAE_DGRAD_EX_SCRATCH_BYTES(numel_w, numel_w2, esize) \
+  ((numel_w2) > 0 ? MMVAE_DGRAD_EX_W2_OFFSET(numel_w, esize) + (size_t)(numel_w2) * (esize) : (size_t)(numel_w) * (esize))
+MMVAE_API int mmvae_conv2d_dgrad_ex(int dtype, int transposed, const void* dy, const float* weight, void* dx, int N, int H, int W, int Cin,
+                          int Cout, int k, int stride, int pad, int accumulate, const void* dy2, const float* w2, int C2, void* scratch,
+                          void* stream);
 /* dW (f32, weight layout) += ... ; pro_* as in fwd (applied to x).  scratch: MMVAE_WGRAD_SCRATCH_BYTES of device memory
  * (per-block partial images, summed by a second kernel: no atomics, bit-reproducible), owned by the caller. */
 #define MMVAE_WGRAD_SCRATCH_BYTES (64u << 20)

@@ -81,6 +81,7 @@ PROTOTYPES = {
     "mmvae_adam_step_guarded": (c_int, [P, P, P, P, c_int64, c_float, c_float, c_float, c_float, c_float, P, P, c_float, c_float, P]),
     "mmvae_conv2d_fwd": (c_int, [c_int, c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P, P]),
     "mmvae_conv2d_dgrad": (c_int, [c_int, c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
+    "mmvae_conv2d_dgrad_ex": (c_int, [c_int, c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P]),
     "mmvae_conv2d_wgrad": (c_int, [c_int, c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P]),
     "mmvae_conv2d_wgrad_pair": (c_int, [c_int, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P]),
     "mmvae_rbf_kernel": (c_int, [P, P, c_int, c_int, c_int, P, P]),

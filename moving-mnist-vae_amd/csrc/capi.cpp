@@ -410,9 +410,6 @@ int mmvae_conv2d_fwd(int dt, int transposed, const void* x, const float* w, void
 }
 int mmvae_conv2d_dgrad(int dt, int transposed, const void* dy, const float* w, void* dx, int N, int H, int W, int Cin, int Cout, int k,
                        int s, int p, void* scratch, void* st) {
-  const ConvGeom g = geom_for(transposed, Cin, Cout, k, s, p);
-  const int Ho = out_size(transposed, H, k, s, p), Wo = out_size(transposed, W, k, s, p);
-  SecondSrc q;
   if (!transposed && s == 1 && conv3_stream_ok(dt, Cin, Cout, k, s, p, H, W)) {
     // encoder.layer1.conv2's shape: the data gradient as a forward conv over dy with the weights packed [cin][flipped tap][cout]
     PackArgs pf; std::memset(&pf, 0, sizeof(pf));
@@ -422,14 +419,46 @@ int mmvae_conv2d_dgrad(int dt, int transposed, const void* dy, const float* w, v
     rc = launch_conv3_stream(dt, 1, dy, scratch, nullptr, dx, nullptr, nullptr, nullptr, 0, nullptr, nullptr, N, H, stream_of(st));
     return rc < 0 ? rc : MMVAE_OK;
   }
+  // everything else: the launch Net::run_up / Net::run_down make, with neither option
+  return mmvae_conv2d_dgrad_ex(dt, transposed, dy, w, dx, N, H, W, Cin, Cout, k, s, p, 0, nullptr, nullptr, 0, scratch, st);
+}
+// The data-gradient launches of Net::run_up / Net::run_down with their two options: accumulate (the identity blocks' main path onto the
+// shortcut's share) and the second source (the 1x1 branch of a residual join, riding along or as its own accumulating launch).  Layouts as
+// Net::settle_layout settles them.  (No per-wave stream form here: the network takes that one through launch_conv3_stream_bwd, never
+// through run_up.)  Every refusal returns before anything is enqueued.
+int mmvae_conv2d_dgrad_ex(int dt, int transposed, const void* dy, const float* w, void* dx, int N, int H, int W, int Cin, int Cout, int k,
+                          int s, int p, int accumulate, const void* dy2, const float* w2, int C2, void* scratch, void* st) {
+  if (dt != MMVAE_F32 && dt != MMVAE_BF16) { set_error("conv2d_dgrad: dtype=%d unsupported", dt); return MMVAE_ERR_ARG; }
+  if (!dy || !w || !dx || !scratch || N < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || k < 1 || s < 1 || p < 0) {
+    set_error("conv2d_dgrad: bad argument"); return MMVAE_ERR_ARG;
+  }
+  if ((dy2 != nullptr) != (w2 != nullptr)) { set_error("conv2d_dgrad: dy2 and w2 go together"); return MMVAE_ERR_ARG; }
+  if (dy2 && accumulate) { set_error("conv2d_dgrad: accumulate with a second source is not a launch of the network"); return MMVAE_ERR_ARG; }
+  if (dy2 && C2 < 1) { set_error("conv2d_dgrad: C2=%d", C2); return MMVAE_ERR_ARG; }
+  if (dy2 && !transposed && s == 2 && ((H | W) & 1)) {
+    set_error("conv2d_dgrad: a stride-2 second source needs even H and W (%d x %d): its phase (0, 0) is the q grid", H, W); return MMVAE_ERR_ARG;
+  }
+  const ConvGeom g = geom_for(transposed, Cin, Cout, k, s, p);
+  const int Ho = out_size(transposed, H, k, s, p), Wo = out_size(transposed, W, k, s, p);
+  char* sc = static_cast<char*>(scratch);
+  SecondSrc q;
+  if (dy2) {
+    // Conv2d (C2, Cin, 1, 1) on the main layer's input: with the main Conv2d's stride (encoder downsample.0), stride 1 beside a ConvTranspose2d
+    // (decoder conv1).  Its data gradient is an up launch on dx's grid either way; packed behind the main weights.
+    const ConvGeom g2 = geom_for(0, Cin, C2, 1, transposed ? 1 : s, 0);
+    q.wfrag2 = op_up_layout(dt, g2, H, W, 1).frag;
+    void* w2p = sc + MMVAE_DGRAD_EX_W2_OFFSET(numel_w(Cin, Cout, k), dtype_size(dt));
+    int rc = op_pack_up(dt, g2, w2, w2p, stream_of(st), 1.f, 0, q.wfrag2); if (rc < 0) return rc;
+    q.x2 = dy2; q.w2 = w2p; q.Cin2 = C2;
+  }
   if (!transposed) {
-    q.wfrag = op_up_layout(dt, g, H, W).frag;
+    q.wfrag = op_up_layout(dt, g, H, W, accumulate != 0).frag;
     int rc = op_pack_up(dt, g, w, scratch, stream_of(st), 1.f, 0, q.wfrag); if (rc < 0) return rc;
-    return op_run_up(dt, g, scratch, N, dy, Ho, Wo, dx, H, W, nullptr, nullptr, 0, nullptr, 0, stream_of(st), q);
+    return op_run_up(dt, g, scratch, N, dy, Ho, Wo, dx, H, W, nullptr, nullptr, 0, nullptr, accumulate != 0, stream_of(st), q);
   }
   q.wfrag = op_down_layout(dt, g, Ho, Wo).frag;
   int rc = op_pack_down(dt, g, w, scratch, stream_of(st), 1.f, 0, q.wfrag); if (rc < 0) return rc;
-  return op_run_down(dt, dt, g, scratch, N, dy, Ho, Wo, dx, H, W, nullptr, nullptr, 0, nullptr, 0, stream_of(st), q);
+  return op_run_down(dt, dt, g, scratch, N, dy, Ho, Wo, dx, H, W, nullptr, nullptr, 0, nullptr, accumulate != 0, stream_of(st), q);
 }
 int mmvae_conv2d_wgrad(int dt, int transposed, const void* x, const void* dy, float* dw, int N, int H, int W, int Cin, int Cout, int k,
                        int s, int p, const float* ps, const float* pb, int relu, void* scratch, void* st) {
