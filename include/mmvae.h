@@ -341,6 +341,22 @@ MMVAE_API int mmvae_scatter_panel(const float* pts, int64_t n, int stride, int c
 MMVAE_API int mmvae_latent_stats(const float* mu, const float* logvar, const float* enc, int N, int d, int accumulate, double* acc,
                                  void* stream);
 
+/* ------------------------------------------------------------------ nearest training frames of a sample (memorised or drawn?)
+ * Exact k nearest neighbours of M query planes among F resident frames.  queries [M][D], frames [F][D]: dense device uint8, 16-byte
+ * aligned.  d(m, f) = sum_{i<D} (queries[m][i] - t(frames[f][i]))^2 with t the identity when lut is NULL and lut[.] (256 device bytes)
+ * otherwise: the lut is applied to `frames` only, the caller hands `queries` already in the compared space.  Exact integer arithmetic
+ * (D * 255^2 <= 16384 * 65025 = 1 065 369 600 fits int32); no floating point is used anywhere.  For every query the frames are ordered by
+ * the pair (d, f) ascending -- equal distances fall to the lower frame index -- and the first k go to out_dist[m][0..k) (int32) and
+ * out_index[m][0..k) (int64).  Every output element is written exactly once, none outside the [M][k] arrays, nothing outside
+ * scratch_bytes of `scratch` (16-byte aligned device memory of at least mmvae_nearest_frames_scratch_bytes(M, F, D, k) bytes, a function
+ * of the shape alone; 0 for a shape the call refuses).  The same bits come out every run, whatever the grid.
+ * Supported: 1 <= M <= 64, 1 <= k <= 8, k <= F <= 2^31 - 1, D a multiple of 16 in [16, 16384].  A non-positive M, F, D or k, k > F, a
+ * NULL or misaligned pointer (lut may be NULL): MMVAE_ERR_ARG; a too-small scratch: MMVAE_ERR_WORKSPACE; M > 64, k > 8, any other D,
+ * F > 2^31 - 1: MMVAE_ERR_UNSUPPORTED.  On an error nothing is enqueued and mmvae_last_error() names the offending value. */
+MMVAE_API size_t mmvae_nearest_frames_scratch_bytes(int M, int64_t F, int D, int k);
+MMVAE_API int mmvae_nearest_frames(const uint8_t* queries, int M, const uint8_t* frames, int64_t F, int D, const uint8_t* lut, int k,
+                                   int32_t* out_dist, int64_t* out_index, void* scratch, size_t scratch_bytes, void* stream);
+
 /* torch.optim.Adam defaults (main.py:468) over a flat buffer: bc1 = 1-beta1^t, bc2_sqrt = sqrt(1-beta2^t);
  * grad_scale multiplies the gradient first (1/world_size after a sum all-reduce). */
 MMVAE_API int mmvae_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,

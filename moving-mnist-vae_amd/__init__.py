@@ -5,11 +5,11 @@ with ``importlib.import_module("moving-mnist-vae_amd")``.  Importing the package
 a GPU; constructing / running the model does, and fails loudly when the HIP library is absent.
 """
 from .data import (MovingMNISTClips, QuantiserFit, choose_transformer, clips_from_npz_array, fit_quantiser, load_kmeans_file,  # noqa: F401
-                   pixel_histogram, quantise_frames, resize_frames, resize_quantise_frames, save_kmeans_file)
+                   nearest_frames, pixel_histogram, quantise_frames, resize_frames, resize_quantise_frames, save_kmeans_file)
 from .main import (checkpoint_variant, evaluate, generate, generate_only_pixelcnn, latent_stats, load_checkpoint, save_checkpoint,  # noqa: F401
                    select_model, train)
-from .panels import (column, gray_lut, latent_slide, make_plot_callback, plot_pixelcnn, plot_pixelvae, plot_vae, render_sheet,  # noqa: F401
-                     sample_from_reconstruction, scatter_panel, scatter_plot, scatter_tone, write_png_gray)
+from .panels import (column, gray_lut, latent_slide, make_plot_callback, neighbour_sheet, plot_neighbours, plot_pixelcnn, plot_pixelvae,  # noqa: F401
+                     plot_vae, render_sheet, sample_from_reconstruction, scatter_panel, scatter_plot, scatter_tone, write_png_gray)
 
 
 def __getattr__(name):

@@ -75,6 +75,8 @@ PROTOTYPES = {
     "mmvae_panel_sheet": (c_int, [P, c_int, c_int, c_int, P, P]),
     "mmvae_scatter_panel": (c_int, [P, c_int64, c_int, c_int, c_int, P, c_int, c_int, P, P, c_int64, P]),
     "mmvae_latent_stats": (c_int, [P, P, P, c_int, c_int, c_int, P, P]),
+    "mmvae_nearest_frames_scratch_bytes": (c_size_t, [c_int, c_int64, c_int, c_int]),
+    "mmvae_nearest_frames": (c_int, [P, c_int, P, c_int64, c_int, P, c_int, P, P, P, c_size_t, P]),
     "mmvae_adam_step": (c_int, [P, P, P, P, c_int64, c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_float, P]),
     "mmvae_adam_step_dev": (c_int, [P, P, P, P, c_int64, c_float, c_float, c_float, c_float, c_float, P, c_float, P]),
     "mmvae_grad_norm_sq": (c_int, [P, c_int64, c_float, P, P, P]),
@@ -125,6 +127,7 @@ PANEL_LABELS_U8, PANEL_LABELS_I64, PANEL_LOGITS_ARGMAX, PANEL_LOGITS_SAMPLE, PAN
 PANEL_MAX_COLS, PANEL_MAX_Q, PANEL_MAX_S = 8, 16, 64
 SCATTER_MAX_SIDE, SCATTER_MIN_RADIUS16, SCATTER_MAX_RADIUS16 = 512, 12, 128      # mmvae_scatter_panel's accepted ranges
 LATENT_STATS_ROWS, LATENT_STATS_MAX_D = 6, 512                                   # mmvae_latent_stats: rows of acc, widest latent
+NEAREST_MAX_M, NEAREST_MAX_K, NEAREST_MAX_D = 64, 8, 16384                       # mmvae_nearest_frames: queries, neighbours, bytes per plane
 
 
 class PanelCol(ctypes.Structure):

@@ -351,6 +351,13 @@ int mmvae_scatter_panel(const float* pts, int64_t n, int stride, int col_x, int 
 int mmvae_latent_stats(const float* mu, const float* logvar, const float* enc, int N, int d, int accumulate, double* acc, void* st) {
   return launch_latent_stats(mu, logvar, enc, N, d, accumulate, acc, stream_of(st));
 }
+// ---- nearest training frames (arguments are checked in the launcher)
+size_t mmvae_nearest_frames_scratch_bytes(int M, int64_t F, int D, int k) { return nearest_frames_scratch_bytes(M, (long)F, D, k); }
+int mmvae_nearest_frames(const uint8_t* queries, int M, const uint8_t* frames, int64_t F, int D, const uint8_t* lut, int k, int32_t* out_dist,
+                         int64_t* out_index, void* scratch, size_t scratch_bytes, void* st) {
+  return launch_nearest_frames(queries, M, frames, (long)F, D, lut, k, out_dist, reinterpret_cast<long long*>(out_index), scratch, scratch_bytes,
+                               stream_of(st));
+}
 int mmvae_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd, float bc1,
                     float bc2_sqrt, float grad_scale, void* st) {
   AdamArgs a{p, g, m, v, (long)n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale};

@@ -424,6 +424,12 @@ int launch_panel_sheet(const mmvae_panel_col* cols, int ncols, int n, int S, uns
 int launch_scatter_panel(const float* pts, long n, int stride, int col_x, int col_y, const float* xform, int side, int radius16,
                          const unsigned char* tone, unsigned char* out, long out_row_stride, hipStream_t s);
 int launch_latent_stats(const float* mu, const float* logvar, const float* enc, int N, int d, int accumulate, double* acc, hipStream_t s);
+// exact k nearest frames of M uint8 query planes among F frames of D bytes (neighbours.hip): squared distances in integers, ties to the
+// lower frame index, lut (nullable, 256 device bytes) applied to the frames only.  The scratch size is a function of the shape alone
+// (0 for a shape the launcher refuses); both check their arguments before anything is enqueued.
+size_t nearest_frames_scratch_bytes(int M, long F, int D, int k);
+int launch_nearest_frames(const unsigned char* queries, int M, const unsigned char* frames, long F, int D, const unsigned char* lut, int k,
+                          int* out_dist, long long* out_index, void* scratch, size_t scratch_bytes, hipStream_t s);
 int launch_convert(int dt_in, int dt_out, const void* in, void* out, long n, hipStream_t s);
 int launch_fill_f32(float* p, float v, long n, hipStream_t s);
 int launch_concat2_to_t(int dt, const float* a, const float* b, int rows, int ca, int cb, void* out, hipStream_t s);

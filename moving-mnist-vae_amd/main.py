@@ -28,9 +28,9 @@ import numpy as np
 import torch
 
 from .data import (KMEANS_FILE_NOTE, MovingMNISTClips, QuantiserFit, choose_transformer, clips_from_npz_array, fit_quantiser,  # noqa: F401
-                   load_kmeans_file, pixel_histogram, quantise_frames, resize_frames, resize_quantise_frames, save_kmeans_file)
-from .panels import (column, gray_lut, latent_slide, make_plot_callback, plot_pixelcnn, plot_pixelvae, plot_vae, render_sheet,  # noqa: F401
-                     sample_from_reconstruction, scatter_panel, scatter_plot, scatter_tone, write_png_gray)
+                   load_kmeans_file, nearest_frames, pixel_histogram, quantise_frames, resize_frames, resize_quantise_frames, save_kmeans_file)
+from .panels import (column, gray_lut, latent_slide, make_plot_callback, neighbour_sheet, plot_neighbours, plot_pixelcnn, plot_pixelvae,  # noqa: F401
+                     plot_vae, render_sheet, sample_from_reconstruction, scatter_panel, scatter_plot, scatter_tone, write_png_gray)
 
 
 def _is_categorical(model) -> bool:

@@ -308,6 +308,45 @@ def _add_scatter(sheets, tensors, encoding, generator):
     tensors["scatter_prior"], tensors["scatter_xform"] = t["prior"], t["xform"]
 
 
+def neighbour_sheet(queries, frames, k=5, lut=None, display_lut=None):
+    """Each query next to its ``k`` nearest training frames: one ``nearest_frames`` call, one gather of the M * k neighbour planes
+    (with ``lut`` applied, so the sheet shows the values that were compared) and one ``render_sheet`` launch.  Returns
+    ``(sheet, dist, index)``: the uint8 (M * S, (k + 1) * S) device sheet -- column 0 the queries, columns 1..k the neighbours, nearest
+    first -- and what ``nearest_frames`` returned.  ``display_lut``: a uint8 table of at most 16 greys for compared values that are class
+    labels (``gray_lut(Q, centres)``); every column then goes through the 'labels' kind.  Without it the compared bytes are shown as
+    greys ('image' columns with lo = 0, hi = 255: the byte itself).  Square planes of side <= 64, ``k <= 7`` (a sheet has 8 columns);
+    otherwise as ``nearest_frames``.  Everything is checked before anything is launched; a violation raises ValueError."""
+    from .data import _nearest_args, _nearest_launch
+    if not 1 <= int(k) <= L.PANEL_MAX_COLS - 1:
+        raise ValueError(f"neighbour_sheet: k={int(k)} unsupported (1..{L.PANEL_MAX_COLS - 1}: a sheet has {L.PANEL_MAX_COLS} columns)")
+    if display_lut is not None:
+        display_lut = torch.as_tensor(display_lut)
+        if display_lut.dtype != torch.uint8 or not 1 <= display_lut.numel() <= L.PANEL_MAX_Q:
+            raise ValueError(f"neighbour_sheet: display_lut is 1..{L.PANEL_MAX_Q} uint8 greys")
+    q, f, k, lut, (H, W) = _nearest_args(queries, frames, k, lut, "neighbour_sheet")
+    if H != W or H > L.PANEL_MAX_S:
+        raise ValueError(f"neighbour_sheet: planes of {H} x {W}, a sheet shows square planes of side 1..{L.PANEL_MAX_S}")
+    dist, index = _nearest_launch(q, f, k, lut)
+    planes = f.index_select(0, index.reshape(-1))
+    if lut is not None:
+        planes = lut[planes.long()]
+    planes = planes.view(q.shape[0], k, -1)
+    sources = [q] + [planes[:, j] for j in range(k)]
+    if display_lut is not None:
+        cols = [column("labels", t, display_lut) for t in sources]
+    else:
+        cols = [column("image", t.float(), lo=0.0, hi=255.0) for t in sources]
+    return render_sheet(cols, q.shape[0]), dist, index
+
+
+def plot_neighbours(queries, frames, directory, epoch, plot_count, **kw):
+    """``neighbour_sheet(queries, frames, **kw)`` written as ``<directory>/neighbours-<epoch>-<plot_count>.png``; returns
+    ``(sheet, dist, index)``."""
+    sheet, dist, index = neighbour_sheet(queries, frames, **kw)
+    _save_sheets({"neighbours": sheet}, directory, epoch, plot_count)
+    return sheet, dist, index
+
+
 def sample_from_reconstruction(reconstruction, uniforms=None, generator=None):
     """The reference's legacy ``utils.sample_from_recostruction`` (utils.py:77-83): one draw per pixel from the softmax of a logits tensor
     (N, Q, H, W), on the device (``decode_labels`` in sample mode).  Returns the int64 labels (N, H, W) -- the reference goes on to
