@@ -357,6 +357,39 @@ MMVAE_API size_t mmvae_nearest_frames_scratch_bytes(int M, int64_t F, int D, int
 MMVAE_API int mmvae_nearest_frames(const uint8_t* queries, int M, const uint8_t* frames, int64_t F, int D, const uint8_t* lut, int k,
                                    int32_t* out_dist, int64_t* out_index, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ------------------------------------------------------------------ per-tensor histograms of a flat buffer (wandb.hook_torch, main.py:456)
+ * 64-bin histograms and exact statistics of T segments of one flat f32 device buffer -- every parameter's gradient, weight or Adam
+ * moment in one call.  segments: T pairs (offset, numel) of int64, in elements of `flat`; any alignment, gaps and numel = 0 allowed.
+ * chunks: n_chunks triples (segment, start, length) of int64 -- the unit of work, one block each; the chunks of a segment must tile
+ * [0, numel) exactly once (mmvae_tensor_hist_chunks builds such a list; an element no chunk covers is not counted, one covered twice is
+ * counted twice).  Both tables are passed twice: the HOST copy is checked before anything is enqueued, the DEVICE copy is what the
+ * kernels read; they must hold the same values.
+ * Per segment t, every operation a correctly rounded f32 operation:
+ *   lo, hi = min / max over the FINITE elements.  No finite element (or numel = 0): lo[t] = hi[t] = 0, all counts 0.
+ *   lo == hi: the range becomes lo - 1 .. hi + 1 (torch.histc), and that is what lo[t], hi[t] report.
+ *   a finite x goes to bin min((int)(((x - lo) * 64.0f) / (hi - lo)), 63)   (ATen's device histc: multiply first, an IEEE division);
+ *   NaN and +-inf are counted in n_nonfinite and in no bin.  The bin index is clamped to 0..63 whatever the data; the counts of a range
+ *   whose width overflows f32 (or of a constant so large that lo - 1 == lo) are unspecified, nothing is written out of bounds.
+ * counts int32 [T][64], lo / hi f32 [T], stats f64 [T][MMVAE_TENSOR_HIST_STATS]: n_finite, n_nonfinite, n_zero (finite and == 0, either
+ * sign), sum and sum of squares of the finite values (terms formed in f64), mean = sum / n_finite, rms = sqrt(sumsq / n_finite) (0 when
+ * n_finite = 0), 0.  Every output element is written by every call.  Three launches on `stream` (per-chunk range and sums, a
+ * per-segment finalize in a fixed order, per-chunk bins merged with integer atomics): no host read, no allocation, no floating-point
+ * atomics -- capturable, and the same input gives the same bits every run.
+ * scratch: at least mmvae_tensor_hist_scratch_bytes(T, n_chunks) bytes of 8-byte aligned device memory.
+ * Errors, nothing enqueued: a NULL pointer (chunks / chunks_dev may be NULL when n_chunks = 0), T <= 0, n_chunks < 0, a negative offset
+ * or numel, a segment that leaves [0, flat_numel), a chunk of an unknown segment or one that leaves its segment: MMVAE_ERR_ARG; a
+ * too-small scratch: MMVAE_ERR_WORKSPACE. */
+#define MMVAE_TENSOR_HIST_BINS 64
+#define MMVAE_TENSOR_HIST_STATS 8
+/* Host only: the chunk list of a HOST segment table, segments in order, each cut into pieces of at most chunk_elems elements (none for
+ * numel = 0).  Returns the number of chunks; writes them when chunks != NULL and capacity (in chunks) suffices, else only counts.
+ * -1 (MMVAE_ERR_ARG) for NULL segments, T <= 0, chunk_elems <= 0 or a negative offset / numel. */
+MMVAE_API int64_t mmvae_tensor_hist_chunks(const int64_t* segments, int T, int64_t chunk_elems, int64_t* chunks, int64_t capacity);
+MMVAE_API size_t mmvae_tensor_hist_scratch_bytes(int T, int64_t n_chunks);
+MMVAE_API int mmvae_tensor_hist(const float* flat, int64_t flat_numel, const int64_t* segments, const int64_t* segments_dev, int T,
+                                const int64_t* chunks, const int64_t* chunks_dev, int64_t n_chunks, int32_t* counts, float* lo, float* hi,
+                                double* stats, void* scratch, size_t scratch_bytes, void* stream);
+
 /* torch.optim.Adam defaults (main.py:468) over a flat buffer: bc1 = 1-beta1^t, bc2_sqrt = sqrt(1-beta2^t);
  * grad_scale multiplies the gradient first (1/world_size after a sum all-reduce). */
 MMVAE_API int mmvae_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,

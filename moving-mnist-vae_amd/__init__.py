@@ -8,6 +8,7 @@ from .data import (MovingMNISTClips, QuantiserFit, choose_transformer, clips_fro
                    nearest_frames, pixel_histogram, quantise_frames, resize_frames, resize_quantise_frames, save_kmeans_file)
 from .main import (checkpoint_variant, evaluate, generate, generate_only_pixelcnn, latent_stats, load_checkpoint, save_checkpoint,  # noqa: F401
                    select_model, train)
+from .monitor import TensorHistograms, make_histogram_callback, tensor_histograms  # noqa: F401
 from .panels import (column, gray_lut, latent_slide, make_plot_callback, neighbour_sheet, plot_neighbours, plot_pixelcnn, plot_pixelvae,  # noqa: F401
                      plot_vae, render_sheet, sample_from_reconstruction, scatter_panel, scatter_plot, scatter_tone, write_png_gray)
 

@@ -77,6 +77,9 @@ PROTOTYPES = {
     "mmvae_latent_stats": (c_int, [P, P, P, c_int, c_int, c_int, P, P]),
     "mmvae_nearest_frames_scratch_bytes": (c_size_t, [c_int, c_int64, c_int, c_int]),
     "mmvae_nearest_frames": (c_int, [P, c_int, P, c_int64, c_int, P, c_int, P, P, P, c_size_t, P]),
+    "mmvae_tensor_hist_chunks": (c_int64, [P, c_int, c_int64, P, c_int64]),
+    "mmvae_tensor_hist_scratch_bytes": (c_size_t, [c_int, c_int64]),
+    "mmvae_tensor_hist": (c_int, [P, c_int64, P, P, c_int, P, P, c_int64, P, P, P, P, P, c_size_t, P]),
     "mmvae_adam_step": (c_int, [P, P, P, P, c_int64, c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_float, P]),
     "mmvae_adam_step_dev": (c_int, [P, P, P, P, c_int64, c_float, c_float, c_float, c_float, c_float, P, c_float, P]),
     "mmvae_grad_norm_sq": (c_int, [P, c_int64, c_float, P, P, P]),

@@ -358,6 +358,20 @@ int mmvae_nearest_frames(const uint8_t* queries, int M, const uint8_t* frames, i
   return launch_nearest_frames(queries, M, frames, (long)F, D, lut, k, out_dist, reinterpret_cast<long long*>(out_index), scratch, scratch_bytes,
                                stream_of(st));
 }
+// ---- per-tensor histograms of a flat buffer (arguments are checked in the launcher)
+int64_t mmvae_tensor_hist_chunks(const int64_t* segments, int T, int64_t chunk_elems, int64_t* chunks, int64_t capacity) {
+  return tensor_hist_chunks(reinterpret_cast<const long long*>(segments), T, (long long)chunk_elems, reinterpret_cast<long long*>(chunks),
+                            (long long)capacity);
+}
+size_t mmvae_tensor_hist_scratch_bytes(int T, int64_t n_chunks) { return tensor_hist_scratch_bytes(T, (long long)n_chunks); }
+int mmvae_tensor_hist(const float* flat, int64_t flat_numel, const int64_t* segments, const int64_t* segments_dev, int T, const int64_t* chunks,
+                      const int64_t* chunks_dev, int64_t n_chunks, int32_t* counts, float* lo, float* hi, double* stats, void* scratch,
+                      size_t scratch_bytes, void* st) {
+  return launch_tensor_hist(flat, (long long)flat_numel, reinterpret_cast<const long long*>(segments),
+                            reinterpret_cast<const long long*>(segments_dev), T, reinterpret_cast<const long long*>(chunks),
+                            reinterpret_cast<const long long*>(chunks_dev), (long long)n_chunks, counts, lo, hi, stats, scratch, scratch_bytes,
+                            stream_of(st));
+}
 int mmvae_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd, float bc1,
                     float bc2_sqrt, float grad_scale, void* st) {
   AdamArgs a{p, g, m, v, (long)n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale};

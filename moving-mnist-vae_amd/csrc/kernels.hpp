@@ -430,6 +430,13 @@ int launch_latent_stats(const float* mu, const float* logvar, const float* enc, 
 size_t nearest_frames_scratch_bytes(int M, long F, int D, int k);
 int launch_nearest_frames(const unsigned char* queries, int M, const unsigned char* frames, long F, int D, const unsigned char* lut, int k,
                           int* out_dist, long long* out_index, void* scratch, size_t scratch_bytes, hipStream_t s);
+// 64-bin histograms and exact statistics of T segments (offset, numel) of a flat f32 buffer (tensor_hist.hip), work cut into chunks
+// (segment, start, length).  seg_host / chunk_host are checked before anything is enqueued, seg_dev / chunk_dev are what the kernels read.
+long long tensor_hist_chunks(const long long* segments, int T, long long chunk_elems, long long* chunks, long long capacity);
+size_t tensor_hist_scratch_bytes(int T, long long n_chunks);
+int launch_tensor_hist(const float* flat, long long flat_numel, const long long* seg_host, const long long* seg_dev, int T,
+                       const long long* chunk_host, const long long* chunk_dev, long long n_chunks, int* counts, float* lo, float* hi,
+                       double* stats, void* scratch, size_t scratch_bytes, hipStream_t s);
 int launch_convert(int dt_in, int dt_out, const void* in, void* out, long n, hipStream_t s);
 int launch_fill_f32(float* p, float v, long n, hipStream_t s);
 int launch_concat2_to_t(int dt, const float* a, const float* b, int rows, int ca, int cb, void* out, hipStream_t s);

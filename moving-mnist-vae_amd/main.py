@@ -8,7 +8,10 @@ grammar (``select_model``), the reference's samplers (``generate*``) and its
 checkpoint format.  The plotting branch (``main.py:401-424``) hangs off
 ``args.plot_callback``: ``make_plot_callback`` in ``panels.py`` returns one, and
 the picture panels (``plot_vae`` / ``plot_pixelcnn`` / ``plot_pixelvae``) and the
-scatter plot (``scatter_plot``) live there too.  The device-side input pipeline
+scatter plot (``scatter_plot``) live there too.  The per-parameter histograms of
+``wandb.hook_torch`` (``main.py:456``) hang off ``args.stats_callback``, called
+between ``backward`` and ``step``: ``make_histogram_callback`` in ``monitor.py``
+returns one.  The device-side input pipeline
 (``quantise_frames``, ``fit_quantiser``, ``MovingMNISTClips``, ...) lives in
 ``data.py``.  The reference's ``main.py`` carries those names, so this module
 re-exports them.
@@ -29,6 +32,7 @@ import torch
 
 from .data import (KMEANS_FILE_NOTE, MovingMNISTClips, QuantiserFit, choose_transformer, clips_from_npz_array, fit_quantiser,  # noqa: F401
                    load_kmeans_file, nearest_frames, pixel_histogram, quantise_frames, resize_frames, resize_quantise_frames, save_kmeans_file)
+from .monitor import TensorHistograms, make_histogram_callback, tensor_histograms  # noqa: F401
 from .panels import (column, gray_lut, latent_slide, make_plot_callback, neighbour_sheet, plot_neighbours, plot_pixelcnn, plot_pixelvae,  # noqa: F401
                      plot_vae, render_sheet, sample_from_reconstruction, scatter_panel, scatter_plot, scatter_tone, write_png_gray)
 
@@ -67,6 +71,7 @@ def train(model, data_loader, optimizer, device, args, epoch=0, data_mean=0, dat
     t0 = time.time()
     model.train(True)
     plot_callback = getattr(args, "plot_callback", None)
+    stats_callback = getattr(args, "stats_callback", None)
     # HIP model: the step scalars stay on the device (model._last_group) and are read back once, after the loop or
     # when the plot callback needs them -- the host never waits for the GPU in the middle of a step.
     pending = []                      # (position in the lists, scalar group)
@@ -98,6 +103,8 @@ def train(model, data_loader, optimizer, device, args, epoch=0, data_mean=0, dat
             mmds.append(mmd_v)
         optimizer.zero_grad()                                                # main.py:397-399
         loss.backward()
+        if stats_callback is not None:                                       # main.py:456 (wandb.hook_torch): the gradients, before the step
+            stats_callback(model=model, optimizer=optimizer, epoch=epoch, index=index)
         optimizer.step()
         if plot_callback is not None and index % plot_every == 0:            # main.py:401
             materialise()

@@ -1196,7 +1196,8 @@ class FusedAdam(torch.optim.Optimizer):
         """Number of steps skipped so far for a non-finite gradient (one small D2H copy)."""
         return int(round(float(self._guard_state()[2].item())))
 
-    def _flat_grads(self, model):
+    @staticmethod
+    def _flat_grads(model):
         first, last = model._ptable[0][1], model._ptable[-1][1]
         if first.grad is None:
             return None
