@@ -278,6 +278,44 @@ MMVAE_API int mmvae_resize_quantise_normalise(const uint8_t* frames, int64_t fra
                                               const int32_t* h_bounds, const int32_t* h_coeffs, int h_ksize, const int32_t* v_bounds,
                                               const int32_t* v_coeffs, int v_ksize, const float* centres, int q, float mean, float stdv,
                                               int64_t* labels, float* image, uint8_t* resized, void* stream);
+/* ------------------------------------------------------------------ data generator
+ * Moving MNIST is not a fixed corpus but a recipe (Srivastava et al. 2015): K glyphs bounce inside an S x S canvas for T frames and
+ * overlaps are composited with max.  The reference reads movingmnist{train,test}.npz and neither ships them nor says how they were made;
+ * this call makes the clips, on the device, at the rate the train step consumes them.  THE RULE BELOW IS PART OF THE INTERFACE: clip c
+ * is a pure function of (seed, c, bank, parameters), the same bits on every run, for every n_clips, first_clip split and launch
+ * geometry, so a file made from a seed can be made again.  It is stated in integers throughout.
+ *
+ * Parameters: S canvas side, a multiple of 16 in 16..64; G glyph side, 1..MMVAE_CLIPGEN_MAX_G; R = S - G >= 1; T frames,
+ * 1..MMVAE_CLIPGEN_MAX_T; K digits per clip, 1..MMVAE_CLIPGEN_MAX_K; D glyphs in the bank, 1..MMVAE_CLIPGEN_MAX_D (outside these:
+ * MMVAE_ERR_UNSUPPORTED, the message names the parameter).  bank: uint8 [D][G][G], any alignment.
+ *
+ * Random numbers (uint64, wrap-around):  mix64(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB;
+ * z ^= z >> 31.  For clip c >= 0 and digit k: n = 8c + k, GOLD = 0x9E3779B97F4A7C15, r1 = mix64(seed + GOLD * (2n + 1)),
+ * r2 = mix64(seed + GOLD * (2n + 2)).  Draws: glyph g = ((r1 >> 32) * D) >> 32; x = r2 & 0xFFFF; y = (r2 >> 16) & 0xFFFF; direction
+ * a = (r2 >> 32) & 0xFFF.
+ *
+ * Velocity: (vx, vy) = (vel[a][0], vel[a][1]), vel a DEVICE int32 table [MMVAE_CLIPGEN_DIRECTIONS][2] the caller computes once per speed
+ * in f64: vx[a] = rint(speed * 65536 * cos(2 pi a / 4096)), vy[a] the same with sin; speed in (0, 1] is the fraction of the free range
+ * travelled per frame (0.1 in the canonical data).  The device only reads the table (|entry| <= 65536 is the CALLER's promise).
+ *
+ * Trajectory: int32 coordinates, ONE = 65536 the whole free range.  For t = 0 .. T-1, update first, record afterwards:
+ *   x += vx; y += vy;  if (x <= 0) { x = 0; vx = -vx; }  if (x >= ONE) { x = ONE; vx = -vx; }  the same for y;
+ *   the glyph's top-left pixel in frame t is px = (x * R) >> 16, py = (y * R) >> 16, both in [0, R].
+ *
+ * Frame: out[c][t][row][col] = max over k of bank[g_k][row - py_k][col - px_k] where that index lies inside the glyph, else 0.
+ *
+ * Clips first_clip .. first_clip + n_clips - 1 (first_clip >= 0) are written; outputs are dense [n_clips][T][S][S], 16-byte aligned,
+ * each may be NULL but not all three (MMVAE_ERR_ARG): bytes uint8 (what MovingMNISTClips holds: (N, C, H, W)), and labels int64 /
+ * image f32 = exactly what mmvae_quantise_normalise(centres, q, mean, stdv) gives for those bytes, bit for bit (centres: q f32, needed
+ * for labels or image only).  n_clips == 0 is a no-op.  One launch on `stream`; no atomics, no scratch, no host read. */
+#define MMVAE_CLIPGEN_MAX_G 32
+#define MMVAE_CLIPGEN_MAX_T 32
+#define MMVAE_CLIPGEN_MAX_K 4
+#define MMVAE_CLIPGEN_MAX_D (1 << 24)
+#define MMVAE_CLIPGEN_DIRECTIONS 4096
+MMVAE_API int mmvae_generate_clips(const uint8_t* bank, int64_t D, int G, const int32_t* vel, uint64_t seed, int64_t first_clip,
+                                   int64_t n_clips, int T, int S, int K, const float* centres, int q, float mean, float stdv,
+                                   int64_t* labels, float* image, uint8_t* bytes, void* stream);
 /* ------------------------------------------------------------------ picture panels (the plot branch, main.py:205-359, utils.py:77-83)
  * Pick rule, shared by the two calls below: the Q f32 logits of one pixel -> a label in [0, Q).  1 <= Q <= 16 (else
  * MMVAE_ERR_UNSUPPORTED).  MMVAE_PICK_ARGMAX: the lowest index among equal maxima (strict > scan from index 0; a NaN never wins, an

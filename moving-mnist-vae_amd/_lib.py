@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (MMVAE_LIB_PATH: developer A/B runs of two builds on one box; the product always loads the in-tree library)
@@ -71,6 +71,7 @@ PROTOTYPES = {
     "mmvae_resample_coeffs": (c_int, [c_int, c_int, POINTER(c_int), P, P]),
     "mmvae_resize_quantise_normalise": (c_int, [P, c_int64, P, c_int, c_int64, c_int, c_int, c_int, c_int, P, P, c_int, P, P, c_int, P, c_int,
                                                 c_float, c_float, P, P, P, P]),
+    "mmvae_generate_clips": (c_int, [P, c_int64, c_int, P, c_uint64, c_int64, c_int64, c_int, c_int, c_int, P, c_int, c_float, c_float, P, P, P, P]),
     "mmvae_logits_to_labels": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P]),
     "mmvae_panel_sheet": (c_int, [P, c_int, c_int, c_int, P, P]),
     "mmvae_scatter_panel": (c_int, [P, c_int64, c_int, c_int, c_int, P, c_int, c_int, P, P, c_int64, P]),
@@ -131,6 +132,7 @@ PANEL_MAX_COLS, PANEL_MAX_Q, PANEL_MAX_S = 8, 16, 64
 SCATTER_MAX_SIDE, SCATTER_MIN_RADIUS16, SCATTER_MAX_RADIUS16 = 512, 12, 128      # mmvae_scatter_panel's accepted ranges
 LATENT_STATS_ROWS, LATENT_STATS_MAX_D = 6, 512                                   # mmvae_latent_stats: rows of acc, widest latent
 NEAREST_MAX_M, NEAREST_MAX_K, NEAREST_MAX_D = 64, 8, 16384                       # mmvae_nearest_frames: queries, neighbours, bytes per plane
+CLIPGEN_MAX_G, CLIPGEN_MAX_T, CLIPGEN_MAX_K, CLIPGEN_MAX_D, CLIPGEN_DIRECTIONS = 32, 32, 4, 1 << 24, 4096       # MMVAE_CLIPGEN_*
 
 
 class PanelCol(ctypes.Structure):

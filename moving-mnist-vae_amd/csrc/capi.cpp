@@ -336,6 +336,12 @@ int mmvae_resize_quantise_normalise(const uint8_t* frames, int64_t frame_stride_
                                           (long)n_frames, in_h, in_w, out_h, out_w, h_bounds, h_coeffs, h_ksize, v_bounds, v_coeffs, v_ksize,
                                           centres, q, mean, stdv, reinterpret_cast<long long*>(labels), image, resized, stream_of(st));
 }
+int mmvae_generate_clips(const uint8_t* bank, int64_t D, int G, const int32_t* vel, uint64_t seed, int64_t first_clip, int64_t n_clips, int T,
+                         int S, int K, const float* centres, int q, float mean, float stdv, int64_t* labels, float* image, uint8_t* bytes,
+                         void* st) {
+  return launch_generate_clips(bank, (long)D, G, vel, (unsigned long long)seed, (long)first_clip, (long)n_clips, T, S, K, centres, q, mean,
+                               stdv, reinterpret_cast<long long*>(labels), image, bytes, stream_of(st));
+}
 // ---- picture panels (pointers and ranges are checked in the launchers, before anything is enqueued)
 int mmvae_logits_to_labels(const float* logits, int N, int Q, int HW, int mode, const float* uniforms, int64_t* labels, void* st) {
   return launch_logits_to_labels(logits, N, Q, HW, mode, uniforms, reinterpret_cast<long long*>(labels), stream_of(st));

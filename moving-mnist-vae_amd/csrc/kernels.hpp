@@ -413,6 +413,14 @@ int launch_resize_quantise_normalise(const unsigned char* frames, long frame_str
                                      long n_frames, int in_h, int in_w, int out_h, int out_w, const int* h_bounds, const int* h_coeffs,
                                      int h_ksize, const int* v_bounds, const int* v_coeffs, int v_ksize, const float* centres, int q,
                                      float mean, float stdv, long long* labels, float* image, unsigned char* resized, hipStream_t s);
+// Moving MNIST clips first_clip .. first_clip + n_clips - 1 by the integer rule of mmvae.h (clipgen.hip), written as the quantiser's
+// outputs (labels, image) and / or the bytes, dense [n_clips][T][S][S]; any of the three may be null but not all.  vel: device int32
+// [4096][2].  Checks its arguments before anything is enqueued.
+constexpr int kClipGenMaxG = MMVAE_CLIPGEN_MAX_G, kClipGenMaxT = MMVAE_CLIPGEN_MAX_T, kClipGenMaxK = MMVAE_CLIPGEN_MAX_K;
+constexpr long kClipGenMaxD = MMVAE_CLIPGEN_MAX_D;
+int launch_generate_clips(const unsigned char* bank, long D, int G, const int* vel, unsigned long long seed, long first_clip, long n_clips,
+                          int T, int S, int K, const float* centres, int q, float mean, float stdv, long long* labels, float* image,
+                          unsigned char* bytes, hipStream_t s);
 // picture panels (panels.hip): logits [N][Q][HW] -> labels by the shared pick rule (mode: MMVAE_PICK_*), and a whole uint8 contact sheet
 // [n * S][ncols * S] from ncols column descriptors (host array, passed to the kernel by value)
 int launch_logits_to_labels(const float* logits, int N, int Q, int HW, int mode, const float* uniforms, long long* labels, hipStream_t s);

@@ -2,8 +2,10 @@
 
 uint8 frames resident on the device -> k-means labels and the normalised image (``quantise_frames``), with the reference's PIL
 ``Resize`` in front where it resizes (``resize_frames``, ``resize_quantise_frames``, ``choose_transformer``); the fit of the k-means
-quantiser itself (``pixel_histogram``, ``fit_quantiser``, ``save_kmeans_file`` / ``load_kmeans_file``); and the loader that feeds
-``main.train`` from HBM (``MovingMNISTClips``).
+quantiser itself (``pixel_histogram``, ``fit_quantiser``, ``save_kmeans_file`` / ``load_kmeans_file``); the loader that feeds
+``main.train`` from HBM (``MovingMNISTClips``); and the data itself: Moving MNIST clips generated on the device from a glyph bank
+(``generate_clips``, ``generate_batch``, the endless loader ``GeneratedClips``), MNIST's IDX file (``load_idx_images``) and the two
+dataset files the reference reads (``save_moving_mnist_files``).
 """
 from __future__ import annotations
 
@@ -402,3 +404,205 @@ class MovingMNISTClips:
                 frames = self.clips.index_select(0, idx)
                 labels, _ = quantise_frames(frames, self.centres, 0.0, 1.0)
             yield labels.view(labels.shape[0], -1)
+
+
+# ---- Moving MNIST generator (mmvae_generate_clips; the rule is stated in include/mmvae.h)
+
+_VELOCITY_TABLES = {}                  # (speed, device) -> int32 [4096, 2] on the device
+
+
+def velocity_table(speed):
+    """The generator's direction table for ``speed`` (the fraction of the free range a digit travels per frame): int32 (4096, 2) on
+    the host, ``[a] = (rint(speed * 65536 * cos(2 pi a / 4096)), rint(speed * 65536 * sin(2 pi a / 4096)))`` in f64."""
+    speed = float(speed)
+    if not 0.0 < speed <= 1.0:
+        raise ValueError(f"velocity_table: speed={speed} unsupported (0 < speed <= 1)")
+    from . import _lib as L
+    angle = 2.0 * np.pi * np.arange(L.CLIPGEN_DIRECTIONS, dtype=np.float64) / 4096.0
+    return np.stack([np.rint(speed * 65536.0 * np.cos(angle)), np.rint(speed * 65536.0 * np.sin(angle))], axis=1).astype(np.int32)
+
+
+def _velocity_on(device, speed):
+    key = (float(speed), str(device))
+    hit = _VELOCITY_TABLES.get(key)
+    if hit is None:
+        hit = _VELOCITY_TABLES[key] = torch.from_numpy(velocity_table(speed)).to(device)
+    return hit
+
+
+def _clipgen_args(bank, n_clips, seed, first_clip, frames, canvas, digits, speed, what):
+    """Every check of the generator's Python calls (nothing is launched, the library is not loaded): returns
+    (n_clips, seed, first_clip, T, S, K, speed, D, G).  ``bank`` is anything with a dtype and a shape."""
+    from . import _lib as L
+    n_clips, seed, first_clip, T, S, K, speed = int(n_clips), int(seed), int(first_clip), int(frames), int(canvas), int(digits), float(speed)
+    if getattr(bank, "dtype", None) not in (torch.uint8, np.dtype(np.uint8)) or len(bank.shape) != 3 or bank.shape[1] != bank.shape[2]:
+        raise ValueError(f"{what}: bank must be a uint8 array of shape [D, G, G], got {getattr(bank, 'dtype', type(bank).__name__)} "
+                         f"{tuple(getattr(bank, 'shape', ()))}")
+    D, G = int(bank.shape[0]), int(bank.shape[1])
+    if S % 16 or not 16 <= S <= 64:
+        raise ValueError(f"{what}: canvas={S} unsupported (a multiple of 16 in 16..64)")
+    if not 1 <= G <= L.CLIPGEN_MAX_G:
+        raise ValueError(f"{what}: bank glyph side G={G} unsupported (1..{L.CLIPGEN_MAX_G})")
+    if S - G < 1:
+        raise ValueError(f"{what}: canvas={S} leaves a {G} x {G} glyph no room to move (canvas - G >= 1)")
+    if not 1 <= T <= L.CLIPGEN_MAX_T:
+        raise ValueError(f"{what}: frames={T} unsupported (1..{L.CLIPGEN_MAX_T})")
+    if not 1 <= K <= L.CLIPGEN_MAX_K:
+        raise ValueError(f"{what}: digits={K} unsupported (1..{L.CLIPGEN_MAX_K})")
+    if not 1 <= D <= L.CLIPGEN_MAX_D:
+        raise ValueError(f"{what}: bank of D={D} glyphs unsupported (1..2^24)")
+    if not 0.0 < speed <= 1.0:
+        raise ValueError(f"{what}: speed={speed} unsupported (0 < speed <= 1)")
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError(f"{what}: seed={seed} unsupported (0..2^64 - 1)")
+    if n_clips < 0:
+        raise ValueError(f"{what}: n_clips={n_clips} is negative")
+    if first_clip < 0 or first_clip + n_clips > 2 ** 63 - 1:
+        raise ValueError(f"{what}: first_clip={first_clip} with n_clips={n_clips} unsupported (clip indices in 0..2^63 - 1)")
+    return n_clips, seed, first_clip, T, S, K, speed, D, G
+
+
+def generate_batch(bank, n_clips, seed, first_clip, centres, data_mean, data_std, want=(True, True, False), frames=20, canvas=64, digits=2,
+                   speed=0.1):
+    """Moving MNIST clips ``first_clip .. first_clip + n_clips - 1`` of ``seed`` straight into the quantiser's outputs, one launch
+    (mmvae_generate_clips; the integer rule is in include/mmvae.h): ``digits`` glyphs of ``bank`` (uint8 device tensor [D, G, G]) bounce
+    inside a ``canvas`` x ``canvas`` frame for ``frames`` frames, overlaps composited with max.  A clip depends on (seed, its index,
+    the bank, the parameters) only.  ``want``: which of (labels int64, image f32, bytes uint8) to produce; returns the three tensors
+    (None where not wanted), each (N, T, S, S) on the bank's device.  labels / image equal
+    ``quantise_frames(generate_clips(...), centres, data_mean, data_std)`` bit for bit; ``centres`` is read for them only."""
+    n, seed, first, T, S, K, speed, D, G = _clipgen_args(bank, n_clips, seed, first_clip, frames, canvas, digits, speed, "generate_batch")
+    want = tuple(bool(w) for w in want)
+    if len(want) != 3 or not any(want):
+        raise ValueError("generate_batch: want is three flags (labels, image, bytes), at least one of them set")
+    bank = _u8_on_gpu(bank, "generate_batch").contiguous()
+    shape, dev = (n, T, S, S), bank.device
+    labels = torch.empty(shape, dtype=torch.int64, device=dev) if want[0] else None
+    image = torch.empty(shape, dtype=torch.float32, device=dev) if want[1] else None
+    out = torch.empty(shape, dtype=torch.uint8, device=dev) if want[2] else None
+    if n == 0:                                   # nothing to launch (and empty tensors have no address to hand over)
+        return labels, image, out
+    c = None
+    if want[0] or want[1]:
+        c = torch.as_tensor(centres, dtype=torch.float32, device=dev).reshape(-1).contiguous()
+    call("mmvae_generate_clips", dev, ptr(bank), D, G, ptr(_velocity_on(dev, speed)), seed, first, n, T, S, K, ptr(c),
+         0 if c is None else c.numel(), float(data_mean), float(data_std), ptr(labels), ptr(image), ptr(out))
+    return labels, image, out
+
+
+def generate_clips(bank, n_clips, seed, first_clip=0, frames=20, canvas=64, digits=2, speed=0.1):
+    """The bytes of ``generate_batch``: uint8 (N, T, S, S) on the bank's device -- what ``MovingMNISTClips.clips`` holds, so
+    ``fit_quantiser``, ``resize_frames``, ``nearest_frames`` and the panels take it as is."""
+    return generate_batch(bank, n_clips, seed, first_clip, None, 0.0, 1.0, (False, False, True), frames, canvas, digits, speed)[2]
+
+
+class GeneratedClips:
+    """``MovingMNISTClips`` without a dataset file: every batch is generated on the device by ``generate_batch`` (one launch from the
+    glyph bank to the int64 labels), and no clip is ever seen twice.  Same iterator contract: yields int64 k-means labels of shape
+    (B, T*S*S), has ``__len__``, a ``train_data`` whose ``len`` is ``clips_per_epoch``, and ``fit_quantiser`` -- so ``train()`` consumes
+    it unchanged.
+
+    bank: uint8 [D, G, G] glyphs (``load_idx_images`` of MNIST's train-images file; a host array or tensor is copied to ``device``).
+    Batch ``i`` of the ``e``-th iteration over the loader covers the clip indices from ``first_clip + e * clips_per_epoch + i * B``
+    (the last batch of an epoch may be ragged).  ``image_size`` other than the canvas generates the bytes and resizes them through
+    ``resize_quantise_frames``' launch (two launches); ``fit_quantiser`` still fits on the native bytes, like ``MovingMNISTClips``."""
+
+    def __init__(self, bank, centres, batch_size, clips_per_epoch, device, seed=0, first_clip=0, image_size=None, frames=20, digits=2,
+                 speed=0.1, canvas=64):
+        self.batch_size, self.clips_per_epoch = int(batch_size), int(clips_per_epoch)
+        if self.batch_size < 1:
+            raise ValueError(f"GeneratedClips: batch_size={self.batch_size} unsupported (>= 1)")
+        if self.clips_per_epoch < 1:
+            raise ValueError(f"GeneratedClips: clips_per_epoch={self.clips_per_epoch} unsupported (>= 1)")
+        _, self.seed, self.first_clip, self.frames, self.canvas, self.digits, self.speed, _, _ = _clipgen_args(
+            bank, self.clips_per_epoch, seed, first_clip, frames, canvas, digits, speed, "GeneratedClips")
+        self.image_size = None if image_size is None else _size_pair(image_size)
+        if self.image_size is not None and self.image_size[0] != self.image_size[1]:
+            raise ValueError("image_size is one int S (the model's input_image_size)")
+        self.device = torch.device(device)
+        self.bank = torch.as_tensor(bank).to(self.device).contiguous()
+        self.train_data = range(self.clips_per_epoch)             # len(dataset.train_data) is read by main.py:506
+        self.centres = None if centres is None else torch.as_tensor(centres, dtype=torch.float32).reshape(-1)
+        self._epoch = 0
+
+    def __len__(self):
+        return (self.clips_per_epoch + self.batch_size - 1) // self.batch_size
+
+    def _generate(self, first, n, centres, want):
+        return generate_batch(self.bank, n, self.seed, first, centres, 0.0, 1.0, want, self.frames, self.canvas, self.digits, self.speed)
+
+    def fit_quantiser(self, n_clusters, clips=4096):
+        """Fits the quantiser on the ``clips`` clips from ``first_clip`` on (generated 1024 at a time into one histogram), installs its
+        centres and returns the ``QuantiserFit``."""
+        clips = int(clips)
+        if clips < 1:
+            raise ValueError(f"fit_quantiser: clips={clips} unsupported (>= 1)")
+        counts = torch.zeros(256, dtype=torch.int64, device=self.device)
+        for lo in range(0, clips, 1024):
+            counts += pixel_histogram(self._generate(self.first_clip + lo, min(1024, clips - lo), None, (False, False, True))[2])
+        fit = _fit_counts(counts.cpu().numpy(), n_clusters)                  # the one device -> host copy
+        self.centres = torch.as_tensor(fit.centres, dtype=torch.float32).reshape(-1)
+        return fit
+
+    def __iter__(self):
+        if self.centres is None:
+            raise RuntimeError("GeneratedClips has no k-means centres: pass `centres` or call .fit_quantiser(n_clusters) first")
+        epoch, self._epoch = self._epoch, self._epoch + 1
+        return self._batches(self.first_clip + epoch * self.clips_per_epoch)
+
+    def _batches(self, first):
+        resize = self.image_size is not None and self.image_size != (self.canvas, self.canvas)
+        for lo in range(0, self.clips_per_epoch, self.batch_size):
+            n = min(self.batch_size, self.clips_per_epoch - lo)
+            if resize:
+                frames = self._generate(first + lo, n, None, (False, False, True))[2]
+                labels = _resize_launch(frames, self.image_size, self.centres, 0.0, 1.0, None, (True, False, False))[0]
+            else:
+                labels = self._generate(first + lo, n, self.centres, (True, False, False))[0]
+            yield labels.view(labels.shape[0], -1)
+
+
+def load_idx_images(path):
+    """The IDX3 ubyte file of MNIST's images (what torchvision leaves under ``raw/``: train-images-idx3-ubyte, plain or ``.gz``) as a
+    uint8 array (D, rows, cols).  Checks the magic number (0x00000803: unsigned bytes, three dimensions) and that the file holds exactly
+    the bytes its header announces.  Standard library and numpy only; downloads nothing."""
+    import gzip
+    path = os.fspath(path)
+    with open(path, "rb") as fh:
+        raw = fh.read()
+    if raw[:2] == b"\x1f\x8b":
+        raw = gzip.decompress(raw)
+    if len(raw) < 16:
+        raise ValueError(f"{path}: {len(raw)} bytes, shorter than an IDX3 header")
+    magic, n, rows, cols = (int(v) for v in np.frombuffer(raw, dtype=">u4", count=4))
+    if magic != 0x00000803:
+        raise ValueError(f"{path}: magic number 0x{magic:08x}, an IDX3 ubyte file starts with 0x00000803")
+    if len(raw) != 16 + n * rows * cols:
+        raise ValueError(f"{path}: header announces {n} x {rows} x {cols} bytes, the file holds {len(raw) - 16}")
+    return np.frombuffer(raw, dtype=np.uint8, offset=16).reshape(n, rows, cols).copy()
+
+
+def save_moving_mnist_files(folder, bank, n_train=10000, n_test=1000, seed=0, frames=20, canvas=64, digits=2, speed=0.1, device="cuda"):
+    """Writes ``folder``/movingmnisttrain.npz and movingmnisttest.npz, the two files the reference reads (movingmnistdataset.py:11-14):
+    ``arr_0`` uint8 in the file layout (N, C, W, H), i.e. the generated (N, T, S, S) clips with the last two axes swapped, so that
+    ``clips_from_npz_array`` / ``MovingMNISTClips(folder, ...)`` give the generated clips back exactly.  Train clips are the indices
+    [0, n_train) of ``seed``, test clips [n_train, n_train + n_test): the files can be made again from (bank, seed).  ``bank``: uint8
+    [D, G, G] on the host or the device.  Returns the two paths."""
+    n_train, n_test = int(n_train), int(n_test)
+    if n_test < 0:
+        raise ValueError(f"save_moving_mnist_files: n_test={n_test} is negative")
+    _clipgen_args(bank, n_train, seed, 0, frames, canvas, digits, speed, "save_moving_mnist_files")
+    _clipgen_args(bank, n_test, seed, n_train, frames, canvas, digits, speed, "save_moving_mnist_files")
+    dev_bank = torch.as_tensor(bank)
+    if not dev_bank.is_cuda:
+        dev_bank = dev_bank.to(device)
+    os.makedirs(folder, exist_ok=True)
+    paths = []
+    for name, first, n in (("movingmnisttrain.npz", 0, n_train), ("movingmnisttest.npz", n_train, n_test)):
+        arr = np.empty((n, int(frames), int(canvas), int(canvas)), dtype=np.uint8)
+        for lo in range(0, n, 1024):                                 # 1024 clips = 84 MB on the device at the canonical shape
+            m = min(1024, n - lo)
+            clips = generate_clips(dev_bank, m, seed, first + lo, frames, canvas, digits, speed)
+            arr[lo:lo + m] = clips.transpose(2, 3).cpu().numpy()
+        paths.append(os.path.join(folder, name))
+        np.savez(paths[-1], arr)
+    return tuple(paths)
