@@ -8,6 +8,8 @@ import ctypes
 import os
 from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (MMVAE_LIB_PATH: developer A/B runs of two builds on one box; the product always loads the in-tree library)
 LIB_PATH = os.environ.get("MMVAE_LIB_PATH") or os.path.join(_HERE, "libmmvae_hip.so")
@@ -190,11 +192,15 @@ def check(rc: int, what: str) -> int:
     return rc
 
 
+def cur_stream():
+    """The current HIP stream's handle, as the C ABI takes it."""
+    return torch.cuda.current_stream().cuda_stream
+
+
 def call(name: str, device, *args) -> int:
     """One launch off the train step: ``lib().<name>(*args, stream)`` on ``device``'s current stream, return code checked."""
-    import torch
     with torch.cuda.device(device):
-        return check(getattr(lib(), name)(*args, torch.cuda.current_stream().cuda_stream), name)
+        return check(getattr(lib(), name)(*args, cur_stream()), name)
 
 
 def ptr(t):

@@ -33,42 +33,31 @@ import torch
 from .data import (KMEANS_FILE_NOTE, GeneratedClips, MovingMNISTClips, QuantiserFit, choose_transformer, clips_from_npz_array,  # noqa: F401
                    fit_quantiser, generate_batch, generate_clips, load_idx_images, load_kmeans_file, nearest_frames, pixel_histogram,
                    quantise_frames, resize_frames, resize_quantise_frames, save_kmeans_file, save_moving_mnist_files, velocity_table)
+from .model import VAE
 from .monitor import TensorHistograms, make_histogram_callback, tensor_histograms  # noqa: F401
 from .panels import (column, gray_lut, latent_slide, make_plot_callback, neighbour_sheet, plot_neighbours, plot_pixelcnn, plot_pixelvae,  # noqa: F401
                      plot_vae, render_sheet, sample_from_reconstruction, scatter_panel, scatter_plot, scatter_tone, write_png_gray)
 
 
-def _is_categorical(model) -> bool:
-    # main.py:381 -- cross entropy when a PixelCNN exists or the decoder emits
-    # more channels than the input has.
-    return model.pixelcnn is not None or model.decoder_out_channels > model.in_channels
-
-
 def prepare_batch(model, batch, device, args, data_mean, data_std):
-    """main.py:374-388: returns (image, target)."""
+    """main.py:374-388: returns (image, target).  Categorical (main.py:381) by the HIP model's rule, whatever model this is."""
     if getattr(args, "dataset", "MovingMNIST") == "MNIST":
         batch = batch[0]
     size = model.input_image_size
     hook = getattr(model, "prepare_batch", None)
     if hook is not None:
         # HIP model: one fused kernel, labels -> normalised frames (+ targets)
-        return hook(batch, device, data_mean, data_std, _is_categorical(model))
+        return hook(batch, device, data_mean, data_std, VAE.is_categorical(model))
     frames = batch.to(device)
     image = (frames.float().view(-1, 1, size, size) - data_mean) / data_std
-    if _is_categorical(model):
-        target = frames.view(-1, size, size).to(device).long()
-    else:
-        target = image
+    target = frames.view(-1, size, size).to(device).long() if VAE.is_categorical(model) else image
     return image, target
 
 
 def train(model, data_loader, optimizer, device, args, epoch=0, data_mean=0, data_std=1, plot_every=200,
           directory="output/") -> Tuple[List[float], List[float], List[float], List[float]]:
     """One epoch.  Returns per-step lists (loss, nll, kl, mmd) like main.py:429."""
-    losses: List[float] = []
-    nlls: List[float] = []
-    kls: List[float] = []
-    mmds: List[float] = []
+    losses, nlls, kls, mmds = [], [], [], []
     t0 = time.time()
     model.train(True)
     plot_callback = getattr(args, "plot_callback", None)
@@ -144,7 +133,7 @@ def evaluate(model, data_loader, device, args, data_mean=0, data_std=1, iw_sampl
     if not hasattr(model, "per_image_terms"):
         raise TypeError("evaluate() drives the HIP VAE of this package (it needs model.per_image_terms)")
     latent = not model.only_pixelcnn
-    categorical = _is_categorical(model)
+    categorical = VAE.is_categorical(model)
     weight = getattr(args, "data_ratio_of_labels", None) if (weighted and categorical) else None
     was_training = bool(model.training)
     sums = None                                    # f64 device: nll, kl, iw
@@ -263,7 +252,6 @@ def select_model(args):
     """Model factory with the reference's name grammar and keyword mapping (main.py:41-147):
     ``pixelcnn_<layers>`` | ``<normal|categorical>_<vae|pixelvae>_<kl>_kl_<mmd>_mmd``.  Returns ``(model, model_params)`` with the reference's
     dict keys."""
-    from .model import VAE
     parts = args.model.split("_")
     if len(parts) == 2:                                                         # main.py:57-66
         if parts[0] != "pixelcnn":

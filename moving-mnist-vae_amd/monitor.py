@@ -34,7 +34,7 @@ def segment_table(model):
     if not tab:
         raise MmvaeError("the model has no parameters")
     seg = np.array([[off, n] for (_, _, off, n, _) in tab], dtype=np.int64).reshape(-1, 2)
-    return [e[0] for e in tab], seg
+    return [e.name for e in tab], seg
 
 
 def chunk_list(segments, chunk=CHUNK):

@@ -247,7 +247,7 @@ def test_gaussian_loss_gradient_folded_into_the_decoder_backward(oracle):
                 rec = rec * 1.0                       # a different tensor: the loss cannot fold its gradient
             loss = m.loss(image, mu, lv, enc, rec, dev, args)[0]
             loss.backward()
-            assert m._pending_tail is None
+            assert m._step.tail is None
             grads[mode] = {k: p.grad.detach().clone() for k, p in m.named_parameters()}
         for k, ref in grads["plain"].items():
             scale = ref.abs().max().item() + 1e-30

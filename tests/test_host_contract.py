@@ -145,11 +145,11 @@ def test_prepare_batch_stages_the_input_once(pkg, oracle):
     m = M.VAE(1, 32, 1, 2, 32, False, False, compute_dtype="bf16").to(dev).train()
     m.injected_eps = torch.randn(6, 32, 1, 1, device=dev)
     image, target = m.prepare_batch(labels, dev, oracle.DATA_MEAN, oracle.DATA_STD, False)
-    assert target is image and m._staged is not None
+    assert target is image and m._step.staged is not None
     ref = ((labels.float() - oracle.DATA_MEAN) / oracle.DATA_STD).view(6, 1, 64, 64)
     assert (image.cpu() - ref).abs().max().item() <= 1e-6
     out_staged = [t.detach().clone() for t in m(image)]
-    assert m._staged is None                                  # consumed
+    assert m._step.staged is None                             # consumed
     out_plain = [t.detach().clone() for t in m(image.clone())]       # a different tensor: converted by the forward itself
     for a, b in zip(out_staged, out_plain):
         assert torch.equal(a, b)

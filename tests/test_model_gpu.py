@@ -375,15 +375,15 @@ def test_deferred_side_join_decoder_only_backward():
     w = torch.randn(N, 1, 64, 64, device=dev)
 
     def grads(defer):
-        old = M._DEFER_JOIN
-        M._DEFER_JOIN = defer
+        old = m.defer_join
+        m.defer_join = defer
         try:
             m.zero_grad()
             enc.grad = None
             (m._decode(enc) * w).sum().backward()
             out = [p.grad.detach().clone() for p in m._dec_params] + [enc.grad.detach().clone()]
         finally:
-            M._DEFER_JOIN = old
+            m.defer_join = old
         return out
 
     ref = grads(False)
@@ -445,9 +445,9 @@ def test_loss_scalars_off_the_critical_stream_and_no_reference_cycle():
         image, target = pkg.main.prepare_batch(m1, batches[0], dev, args, 0.05, 0.22)
         mu, lv, enc, rec = m1(image)
         loss, nll, kl, mmd = m1.loss(target, mu, lv, enc, rec, dev, args, deferred=True)
-        assert m1.__dict__.get("_pending_loss") is not None
+        assert m1._step.loss_pending
         v = float(nll)
-        assert m1.__dict__.get("_pending_loss") is None and v == v and v > 0
+        assert not m1._step.loss_pending and v == v and v > 0
         del loss, nll, kl, mmd, mu, lv, enc, rec, image, target
         # (3) no cycle
         refs = [weakref.ref(m1), weakref.ref(m2)]

@@ -252,4 +252,4 @@ def test_pixelcnn_only_model_trains_through_train(pkg, oracle):
     # uint8 labels take the same path
     img8, tgt8 = m.prepare_batch(batches[0].to(torch.uint8), dev, oracle.DATA_MEAN, oracle.DATA_STD, True)
     img64, _ = m.prepare_batch(batches[0], dev, oracle.DATA_MEAN, oracle.DATA_STD, True)
-    assert torch.equal(img8, img64) and tgt8.dtype == torch.int64 and m._staged is None
+    assert torch.equal(img8, img64) and tgt8.dtype == torch.int64 and m._step.staged is None
