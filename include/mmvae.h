@@ -581,14 +581,27 @@ MMVAE_API int mmvae_upblock_bwd_fused(const float* d_raw, const float* tail_weig
  *   dy1 = A1 (d_a1 [bn1(y1) > 0]) + B1 y1 + C1;  g_in += dy1 (x) W1 (in place);  dw_conv1 (16,16,1,1) += dy1^T (x) pro(xin).
  * rows = N * H rows of 32 pixels.  scratch: MMVAE_WGRAD_SCRATCH_BYTES. */
 /* The same block's FORWARD tail: r_raw = decoder.conv2(relu(bn2(conv2(relu(bn1(y1)))) + upsample.1(upsample.0(x_in)))) (model.py:70-85,193) with both
- * ConvTranspose2d branch outputs recomputed row by row from their 32x32x16 inputs instead of read back (they are still written by
- * mmvae_conv2d_fwd for the statistics and the backward pass).  bf16 NHWC inputs, f32 weights in PyTorch layout (w2, wu: [16][16][4][4]; tail
+ * ConvTranspose2d branch outputs recomputed row by row from their 32x32x16 inputs instead of read back (this call does not write them: see
+ * mmvae_upblock_tail_fwd_store).  bf16 NHWC inputs, f32 weights in PyTorch layout (w2, wu: [16][16][4][4]; tail
  * weight [1][16][3][3] + bias), s / b pairs = forward scale / shift of the BatchNorms (sx / bx may be NULL: x_in is an activation);
  * r_raw f32 [N][64][64]; stats (nullable) receives <return value> partial rows [2] = (sum, sum of squares) of r_raw; scratch >= 16 KB. */
 MMVAE_API int mmvae_upblock_tail_fwd(const void* y1, const float* s1, const float* b1, const float* w2, const void* x_in, const float* sx,
                                      const float* bx, const float* wu, const float* s2, const float* b2, const float* ss, const float* bs,
                                      const float* tail_weight, const float* tail_bias, float* r_raw, float* stats, int N, void* scratch,
                                      void* stream);
+/* The same launch, also STORING the two branch outputs the backward pass reads: y2 = conv2(relu(bn1(y1))), ys = upsample.0(x_in), both
+ * [N][64][64][16] bf16 and bit-identical to what mmvae_conv2d_fwd writes for the same inputs (the same f32 accumulators, the same rounding).
+ * r_raw and stats are those of mmvae_upblock_tail_fwd bit for bit.  y2 and ys are both required here. */
+MMVAE_API int mmvae_upblock_tail_fwd_store(const void* y1, const float* s1, const float* b1, const float* w2, const void* x_in, const float* sx,
+                                           const float* bx, const float* wu, const float* s2, const float* b2, const float* ss, const float* bs,
+                                           const float* tail_weight, const float* tail_bias, float* r_raw, float* stats, void* y2, void* ys,
+                                           int N, void* scratch, void* stream);
+/* The batch statistics of ConvTranspose2d(16 -> 16, k4 s2 p1) on x [N][32][32][16] WITHOUT its output (what the training step runs in front of
+ * mmvae_upblock_tail_fwd_store): stats receives <return value> partial rows [2][16], bit-identical to those of mmvae_conv2d_fwd on the
+ * same inputs; pro_scale / pro_shift (both or neither) as there, with ReLU.  dtype: bf16 only; e4m3_out != 0 (the fp8 storage mode has
+ * no such form) and other dtypes are refused.  weight (16,16,4,4) f32; scratch >= 8 KB for the packed weights. */
+MMVAE_API int mmvae_convT4_stats(int dtype, const void* x, const float* weight, const float* pro_scale, const float* pro_shift, float* stats,
+                                 int N, int e4m3_out, void* scratch, void* stream);
 /* A block's residual join fused with the NEXT block's conv1 (reference model.py:86-88 of block i, :72 of block i + 1; conv_joinfwd.hip; bf16):
  *   out = relu(s2 y2 + b2 + ss ys + bs)  [npix][C]  (C = 16 or 32; written: the upsample branch and the backward pass read it),
  *   y1 = conv1(out), w_conv1 (16, C, 1, 1) f32, no bias, [npix][16];  stats (nullable): <return value> partial rows [2][16] = (sum, sum of

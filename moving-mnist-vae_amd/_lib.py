@@ -112,6 +112,8 @@ PROTOTYPES = {
     "mmvae_join_conv1x1_fwd": (c_int, [P, P, P, P, P, P, P, c_int, P, P, P, c_int64, P, P]),
     "mmvae_conv1x1_bwd_fused": (c_int, [P] * 13 + [c_int64, P, P]),
     "mmvae_upblock_tail_fwd": (c_int, [P] * 16 + [c_int, P, P]),
+    "mmvae_upblock_tail_fwd_store": (c_int, [P] * 18 + [c_int, P, P]),
+    "mmvae_convT4_stats": (c_int, [c_int, P, P, P, P, P, c_int, c_int, P, P]),
     "mmvae_pixelcnn_create": (c_int, [POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int]),
     "mmvae_pixelcnn_destroy": (None, [P]),
     "mmvae_pixelcnn_num_params": (c_int64, [P]),

@@ -655,6 +655,27 @@ int mmvae_upblock_tail_fwd(const void* y1, const float* s1, const float* b1, con
   rc = op_pack_up(DT_BF16, g, wu, sc + 8192, stream_of(st)); if (rc < 0) return rc;
   return launch_up5_tail_fwd(y1, s1, b1, sc, xin, sx, bx, sc + 8192, s2, b2, ss, bs, tw, bias, r_raw, stats, N, stream_of(st));
 }
+int mmvae_upblock_tail_fwd_store(const void* y1, const float* s1, const float* b1, const float* w2, const void* xin, const float* sx, const float* bx,
+                                 const float* wu, const float* s2, const float* b2, const float* ss, const float* bs, const float* tw,
+                                 const float* bias, float* r_raw, float* stats, void* y2, void* ys, int N, void* scratch, void* st) {
+  if (!scratch || !y1 || !s1 || !b1 || !w2 || !xin || !wu || !s2 || !b2 || !ss || !bs || !tw || !r_raw || !y2 || !ys || N < 1 ||
+      ((sx != nullptr) != (bx != nullptr))) {
+    set_error("upblock_tail_fwd_store: bad argument"); return MMVAE_ERR_ARG;
+  }
+  char* sc = static_cast<char*>(scratch);
+  const ConvGeom g = geom_for(1, 16, 16, 4, 2, 1);
+  int rc = op_pack_up(DT_BF16, g, w2, sc, stream_of(st)); if (rc < 0) return rc;
+  rc = op_pack_up(DT_BF16, g, wu, sc + 8192, stream_of(st)); if (rc < 0) return rc;
+  return launch_up5_tail_fwd(y1, s1, b1, sc, xin, sx, bx, sc + 8192, s2, b2, ss, bs, tw, bias, r_raw, stats, N, stream_of(st), y2, ys);
+}
+int mmvae_convT4_stats(int dt, const void* x, const float* w, const float* ps, const float* pb, float* stats, int N, int e4m3_out, void* scratch,
+                       void* st) {
+  if (!scratch || !x || !w || !stats || N < 1 || ((ps != nullptr) != (pb != nullptr))) { set_error("convT4_stats: bad argument"); return MMVAE_ERR_ARG; }
+  if (dt != DT_BF16) { set_error("convT4_stats: bf16 only"); return MMVAE_ERR_UNSUPPORTED; }
+  if (e4m3_out) { set_error("convT4_stats: the e4m3 storage mode has no statistics-only form"); return MMVAE_ERR_UNSUPPORTED; }
+  int rc = op_pack_up(dt, geom_for(1, 16, 16, 4, 2, 1), w, scratch, stream_of(st)); if (rc < 0) return rc;
+  return launch_convT4_stream(dt, x, scratch, nullptr, ps, pb, 1, stats, N, 32, stream_of(st));
+}
 int mmvae_conv1x1_bwd_fused(const void* da1, const void* y1, const float* s1, const float* b1, const float* A1, const float* B1, const float* C1,
                             const void* xin, const float* sx, const float* bx, const float* w1, float* dw1, void* gin, int64_t rows, void* scratch,
                             void* st) {

@@ -404,6 +404,8 @@ __global__ __launch_bounds__(256, 2) void tail_fwd_stream_kernel(TailFwdStreamAr
 // channels are two K = 32 MFMA steps per 16-pixel tile (A = the packed per-phase weights, 8 fragments resident; B = 16-byte reads of
 // ring pixels), the results of both parities are interleaved into a wave-private LDS row and leave as whole 16-byte-per-lane stores;
 // BatchNorm sums from the f32 results.
+// NOY (y == nullptr, the last up-block when up5_tail_fwd_kernel stores y2 / ys itself): the statistics-only form -- the same units, MFMA
+// sequence and sums (the partial rows are bit-identical to the storing launch's), no output row in LDS and no global store.
 struct ConvT4StreamArgs {
   const void* x; const void* w; void* y;
   const float* pro_scale; const float* pro_shift; int pro_relu;
@@ -412,12 +414,13 @@ struct ConvT4StreamArgs {
 };
 
 // F8O (fp8 mode, the 32x32 -> 64x64 layers): the output leaves as e4m3 bytes, 16 per pixel (the statistics are still those of the f32 results)
-template <int WIN, bool PRO, bool F8O = false>
+template <int WIN, bool PRO, bool F8O = false, bool NOY = false>
 __global__ __launch_bounds__(256, 3) void convT4_stream_kernel(ConvT4StreamArgs a) {
+  static_assert(!NOY || !F8O, "statistics-only: the bf16 forms");
   constexpr int CB = 32, WL = WIN + 2, ROWB = WL * CB, NSLOT = 4, NPRIME = 2;
   constexpr int CBO = F8O ? 16 : 32;                                        // bytes per output pixel
   constexpr int OROWB = 2 * WIN * CBO;                                      // one output row
-  constexpr int WAVE_LDS = NSLOT * ROWB + OROWB;
+  constexpr int WAVE_LDS = NSLOT * ROWB + (NOY ? 0 : OROWB);
   constexpr int XV = (WIN * CB + 1023) / 1024;                              // input-row vectors per lane (WIN = 32: 1; 16: 1, half the lanes)
   constexpr int NPT = WIN / 16;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -476,7 +479,7 @@ __global__ __launch_bounds__(256, 3) void convT4_stream_kernel(ConvT4StreamArgs 
       }
       *reinterpret_cast<Vec16*>(ring + ((row + 4 * NSLOT) % NSLOT) * ROWB + CB + lane * 16) = v;
     }
-    (void)n; (void)XV;
+    (void)n; (void)XV; (void)orow;
   };
   int u = u_first, q = 0;
   if (u < u_end) issue(u, 0);
@@ -510,7 +513,8 @@ __global__ __launch_bounds__(256, 3) void convT4_stream_kernel(ConvT4StreamArgs 
           for (int pt = 0; pt < NPT; ++pt) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) { st1[j] += acc[pt][j]; st2[j] += acc[pt][j] * acc[pt][j]; }
-            if constexpr (F8O) {
+            if constexpr (NOY) {
+            } else if constexpr (F8O) {
               *reinterpret_cast<uint32_t*>(orow + (2 * (16 * pt + r) + pw) * CBO + gq * 4) = pack4_fp8(acc[pt][0], acc[pt][1], acc[pt][2], acc[pt][3]);
             } else {
               uint2 o;
@@ -520,11 +524,14 @@ __global__ __launch_bounds__(256, 3) void convT4_stream_kernel(ConvT4StreamArgs 
           }
         }
         // the finished output row 2*iq + ph leaves as 16 bytes per lane (compiler fence: stored as 4- / 8-byte vectors, read back as 16-byte ones)
-        asm volatile("" ::: "memory");
-        char* dst = reinterpret_cast<char*>(a.y) + (((long)n * (2 * a.Hi) + 2 * iq + ph) * (2 * WIN)) * CBO;
+        if constexpr (!NOY) {
+          asm volatile("" ::: "memory");
+          char* dst = reinterpret_cast<char*>(a.y) + (((long)n * (2 * a.Hi) + 2 * iq + ph) * (2 * WIN)) * CBO;
 #pragma unroll
-        for (int k = 0; k < OROWB / 1024; ++k) *reinterpret_cast<Vec16*>(dst + (lane + 64 * k) * 16) = *reinterpret_cast<const Vec16*>(orow + (lane + 64 * k) * 16);
+          for (int k = 0; k < OROWB / 1024; ++k) *reinterpret_cast<Vec16*>(dst + (lane + 64 * k) * 16) = *reinterpret_cast<const Vec16*>(orow + (lane + 64 * k) * 16);
+        }
       }
+      (void)n;
     }
     __builtin_amdgcn_sched_barrier(0);
     u = un; q = qn;
@@ -545,16 +552,22 @@ __global__ __launch_bounds__(256, 3) void convT4_stream_kernel(ConvT4StreamArgs 
 // Here a wave keeps rings of the two ConvTranspose2d INPUT rows (32x32x16: 0.34 GB together) and recomputes both branch outputs for the
 // two output rows of an input row exactly like convT4_stream_kernel does (same MFMA sequence; the f32 accumulators are NOT rounded to bf16 as the
 // stored tensors are), joins them in the D-fragment mapping (lane = 4 channels of one output pixel) into the ring of joined rows (bf16) the tail conv reads.
-// y2 / ys are still written by convT4_stream_kernel (statistics; the backward pass reads them): this kernel only stops READING them.
+// STORE (y2 / ys non-null: the training step): this kernel also WRITES the two branch outputs the backward pass reads -- the f32 accumulators
+// rounded with the pack2_bf16 of convT4_stream_kernel, so the tensors are bit-identical to that kernel's; convT4_stream_kernel then runs
+// in its statistics-only form before this one (BatchNorm needs the batch statistics of y2 / ys before the join) and stores nothing.  A unit
+// stores the output rows of the input rows it owns (q0 <= iq < q0 + HS; the two halo rows are recomputed for the tail conv and belong to
+// the neighbouring units) as 16-byte-per-lane row stores straight from registers (v_permlane16_swap pairs the two column parities up; a
+// 2 KB staging row per wave in LDS, as convT4_stream_kernel has, made this LDS-bound kernel 400 us in the step instead of 362: DESIGN lesson 64).
 struct Up5TailFwdArgs {
   const void* y1; const float* p1s; const float* p1b; const void* w2;      // conv2 branch: input (pre-bn1), bn1 scale / shift, packed up weights
   const void* xin; const float* pxs; const float* pxb; const void* wu;     // upsample branch: block input (+ optional BatchNorm+ReLU), packed up weights
   const float* s2; const float* b2; const float* ss; const float* bs;      // join coefficients (forward scale / shift of bn2 and of the shortcut's BatchNorm)
   const float* w; const float* bias; float* r_raw; float* stats;
+  void* y2; void* ys;                                                      // STORE: the branch outputs [N][64][64][16] bf16
   int N, HS, nunits;
 };
 
-template <bool PRO_X>
+template <bool PRO_X, bool STORE = false>
 __global__ __launch_bounds__(256, 2) void up5_tail_fwd_kernel(Up5TailFwdArgs a) {
   constexpr int WIN = 32, Hi = 32, W = 64, H = 64, CB = 32;
   constexpr int IWL = WIN + 2, IROWB = IWL * CB, NSLOT = 4;                // input rings: 4 rows of 34 pixels
@@ -664,6 +677,7 @@ __global__ __launch_bounds__(256, 2) void up5_tail_fwd_kernel(Up5TailFwdArgs a) 
       const int n = u / nstrips, q0 = (u - n * nstrips) * a.HS;
       const int iq = q0 - 1 + q - NPRIME;                                   // input row of this step: q0 - 1 .. q0 + HS
       const bool inside = iq >= 0 && iq < Hi;                               // (wave-uniform) rows outside the image: the tail conv's zero padding
+      const bool own = STORE && iq >= q0 && iq < q0 + a.HS;                 // (wave-uniform) the halo rows' outputs are the neighbours' to store
       // ---- the two joined rows 2 iq, 2 iq + 1
 #pragma unroll
       for (int ph = 0; ph < 2; ++ph) {
@@ -672,6 +686,8 @@ __global__ __launch_bounds__(256, 2) void up5_tail_fwd_kernel(Up5TailFwdArgs a) 
           for (int i = lane; i < (W * CB) / 16; i += 64) *reinterpret_cast<Vec16*>(jrow + CB + i * 16) = Vec16{{0, 0, 0, 0}};
           continue;
         }
+        uint2 k2[2][2], ks[2][2];                                           // (STORE) both branches' rounded results [pw][pt], until both parities are there
+        (void)k2; (void)ks; (void)own;
 #pragma unroll
         for (int pw = 0; pw < 2; ++pw) {
           f32x4 acc2[2], accS[2];
@@ -695,6 +711,29 @@ __global__ __launch_bounds__(256, 2) void up5_tail_fwd_kernel(Up5TailFwdArgs a) 
 #pragma unroll
             for (int j = 0; j < 4; ++j) o[j] = fmaxf(acc2[pt][j] * js2[j] + jb[j] + accS[pt][j] * jss[j], 0.f);
             *reinterpret_cast<uint2*>(jrow + (1 + 2 * (16 * pt + r) + pw) * CB + gq * 8) = make_uint2(pack2_bf16(o[0], o[1]), pack2_bf16(o[2], o[3]));
+            if constexpr (STORE) {
+              k2[pw][pt] = make_uint2(pack2_bf16(acc2[pt][0], acc2[pt][1]), pack2_bf16(acc2[pt][2], acc2[pt][3]));
+              ks[pw][pt] = make_uint2(pack2_bf16(accS[pt][0], accS[pt][1]), pack2_bf16(accS[pt][2], accS[pt][3]));
+            }
+          }
+        }
+        if constexpr (STORE) {
+          if (own) {
+            // output row 2 iq + ph of both branches.  A lane holds 8 bytes (channels 4gq ..) of pixel 2p of the pw = 0 results and of pixel
+            // 2p + 1 of the pw = 1 results; v_permlane16_swap (rows of 16 lanes: gq <-> gq ^ 1) hands the even gq the neighbour's half of pixel
+            // 2p and the odd gq the neighbour's half of pixel 2p + 1, so a lane ends with 16 contiguous bytes (channels 8 (gq >> 1) ..) and the
+            // wave stores 1 KB contiguous per 16-pixel tile -- no staging row, no LDS traffic beside the LDS-bound tail conv
+            char* const o2 = reinterpret_cast<char*>(a.y2) + (((long)n * H + 2 * iq + ph) * W) * CB + (gq & 1) * CB + (gq >> 1) * 16;
+            char* const oS = reinterpret_cast<char*>(a.ys) + (o2 - reinterpret_cast<char*>(a.y2));
+#pragma unroll
+            for (int pt = 0; pt < 2; ++pt) {
+              const auto x2 = __builtin_amdgcn_permlane16_swap(k2[0][pt].x, k2[1][pt].x, false, false);
+              const auto y2 = __builtin_amdgcn_permlane16_swap(k2[0][pt].y, k2[1][pt].y, false, false);
+              const auto xS = __builtin_amdgcn_permlane16_swap(ks[0][pt].x, ks[1][pt].x, false, false);
+              const auto yS = __builtin_amdgcn_permlane16_swap(ks[0][pt].y, ks[1][pt].y, false, false);
+              *reinterpret_cast<Vec16*>(o2 + 2 * (16 * pt + r) * CB) = Vec16{{x2[0], y2[0], x2[1], y2[1]}};
+              *reinterpret_cast<Vec16*>(oS + 2 * (16 * pt + r) * CB) = Vec16{{xS[0], yS[0], xS[1], yS[1]}};
+            }
           }
         }
       }
@@ -766,10 +805,12 @@ bool up5_tail_fwd_ok(int dt, int OC, int C, int Cin, int Hin, int Hout) {
 // returns the number of partial rows [rows][2] (> 0) or an error
 int launch_up5_tail_fwd(const void* y1, const float* p1s, const float* p1b, const void* w2_up, const void* xin, const float* pxs, const float* pxb,
                         const void* wu_up, const float* s2, const float* b2, const float* ss, const float* bs, const float* w, const float* bias,
-                        float* r_raw, float* stats, int N, hipStream_t s) {
+                        float* r_raw, float* stats, int N, hipStream_t s, void* y2, void* ys) {
+  if ((y2 != nullptr) != (ys != nullptr)) { set_error("up5_tail_fwd: y2 and ys go together"); return MMVAE_ERR_ARG; }
+  const bool store = y2 != nullptr;
   Up5TailFwdArgs a; memset(&a, 0, sizeof(a));
   a.y1 = y1; a.p1s = p1s; a.p1b = p1b; a.w2 = w2_up; a.xin = xin; a.pxs = pxs; a.pxb = pxb; a.wu = wu_up;
-  a.s2 = s2; a.b2 = b2; a.ss = ss; a.bs = bs; a.w = w; a.bias = bias; a.r_raw = r_raw; a.stats = stats;
+  a.s2 = s2; a.b2 = b2; a.ss = ss; a.bs = bs; a.w = w; a.bias = bias; a.r_raw = r_raw; a.stats = stats; a.y2 = y2; a.ys = ys;
   a.N = N; a.HS = 16; a.nunits = N * (32 / a.HS);
   int gx = 512;                                              // two blocks per CU (LDS), one resident round; rows of `stats` <= N
   while (gx > 1 && (long)gx * 4 > a.nunits) gx -= gx > 8 ? 8 : 1;
@@ -778,12 +819,18 @@ int launch_up5_tail_fwd(const void* y1, const float* p1s, const float* p1b, cons
   if (!attr_set) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&up5_tail_fwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&up5_tail_fwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&up5_tail_fwd_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&up5_tail_fwd_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) { set_error("up5_tail_fwd: hipFuncSetAttribute: %s", hipGetErrorString(e)); return MMVAE_ERR_HIP; }
     attr_set = true;
   }
-  if (pxs) hipLaunchKernelGGL(up5_tail_fwd_kernel<true>, dim3(gx), dim3(256), lds, s, a);
+  if (store) {
+    if (pxs) hipLaunchKernelGGL((up5_tail_fwd_kernel<true, true>), dim3(gx), dim3(256), lds, s, a);
+    else hipLaunchKernelGGL((up5_tail_fwd_kernel<false, true>), dim3(gx), dim3(256), lds, s, a);
+  } else if (pxs) hipLaunchKernelGGL(up5_tail_fwd_kernel<true>, dim3(gx), dim3(256), lds, s, a);
   else hipLaunchKernelGGL(up5_tail_fwd_kernel<false>, dim3(gx), dim3(256), lds, s, a);
-  note_launch_bytes((double)N * (2.0 * 32 * 32 * 16 * 2 + 64 * 64 * 4.0));
+  // the two ConvTranspose2d inputs + r_raw (+ y2 and ys, bf16, when this kernel stores them)
+  note_launch_bytes((double)N * (2.0 * 32 * 32 * 16 * 2 + 64 * 64 * 4.0 + (store ? 2.0 * 64 * 64 * 16 * 2 : 0.0)));
   const int rc = check_launch("up5_tail_fwd");
   return rc ? rc : gx;
 }
@@ -803,12 +850,18 @@ int launch_convT4_stream(int dt, const void* x, const void* w_up, void* y, const
   int gx = Hin == 32 ? 1024 : 768;
   while (gx > 8 && (long)gx * 4 > a.nunits) gx -= 8;
   const bool pro = pro_scale != nullptr;
-  const size_t lds = 1024 + 4 * (size_t)(4 * (Hin + 2) * 32 + 2 * Hin * 32);
+  const bool noy = y == nullptr;                             // statistics only: same units and grid, no output row in LDS
+  const size_t lds = 1024 + 4 * (size_t)(4 * (Hin + 2) * 32 + (noy ? 0 : 2 * Hin * 32));
   if (f8out && Hin != 32) { set_error("convT4_stream: e4m3 output only for the 32x32 -> 64x64 layers"); return MMVAE_ERR_UNSUPPORTED; }
-  if (f8out) { if (pro) hipLaunchKernelGGL((convT4_stream_kernel<32, true, true>), dim3(gx), dim3(256), lds, s, a); else hipLaunchKernelGGL((convT4_stream_kernel<32, false, true>), dim3(gx), dim3(256), lds, s, a); }
+  if (noy && f8out) { set_error("convT4_stream: the statistics-only form (y == NULL) has no e4m3 variant"); return MMVAE_ERR_UNSUPPORTED; }
+  if (noy && !stats) { set_error("convT4_stream: y == NULL needs stats"); return MMVAE_ERR_ARG; }
+  if (noy && Hin == 32) { if (pro) hipLaunchKernelGGL((convT4_stream_kernel<32, true, false, true>), dim3(gx), dim3(256), lds, s, a); else hipLaunchKernelGGL((convT4_stream_kernel<32, false, false, true>), dim3(gx), dim3(256), lds, s, a); }
+  else if (noy) { if (pro) hipLaunchKernelGGL((convT4_stream_kernel<16, true, false, true>), dim3(gx), dim3(256), lds, s, a); else hipLaunchKernelGGL((convT4_stream_kernel<16, false, false, true>), dim3(gx), dim3(256), lds, s, a); }
+  else if (f8out) { if (pro) hipLaunchKernelGGL((convT4_stream_kernel<32, true, true>), dim3(gx), dim3(256), lds, s, a); else hipLaunchKernelGGL((convT4_stream_kernel<32, false, true>), dim3(gx), dim3(256), lds, s, a); }
   else if (Hin == 32) { if (pro) hipLaunchKernelGGL((convT4_stream_kernel<32, true>), dim3(gx), dim3(256), lds, s, a); else hipLaunchKernelGGL((convT4_stream_kernel<32, false>), dim3(gx), dim3(256), lds, s, a); }
   else { if (pro) hipLaunchKernelGGL((convT4_stream_kernel<16, true>), dim3(gx), dim3(256), lds, s, a); else hipLaunchKernelGGL((convT4_stream_kernel<16, false>), dim3(gx), dim3(256), lds, s, a); }
-  note_launch_bytes((double)N * 16 * (2.0 + (f8out ? 4.0 : 8.0)) * Hin * Hin);   // x + y = (1 + 4) Hin^2 pixels of 16 channels (bf16; y e4m3 with f8out)
+  // x + y = (1 + 4) Hin^2 pixels of 16 channels (bf16; y e4m3 with f8out; statistics only: x alone)
+  note_launch_bytes((double)N * 16 * (2.0 + (noy ? 0.0 : f8out ? 4.0 : 8.0)) * Hin * Hin);
   const int rc = check_launch("convT4_stream");
   return rc ? rc : gx;
 }

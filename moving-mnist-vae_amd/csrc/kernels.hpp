@@ -228,15 +228,17 @@ int launch_conv3_stream(int dt, int stride, const void* x, const void* w, const 
 bool convT4_stream_ok(int dt, int Cin, int Cout, int k, int s, int p, int Hin, int Win);
 int launch_convT4_stream(int dt, const void* x, const void* w_up, void* y, const float* pro_scale, const float* pro_shift, int pro_relu, float* stats,
                          int N, int Hin, hipStream_t s, int f8out = 0);    // f8out: y leaves as e4m3 bytes (32x32 inputs only)
+                                                                           // y == nullptr (not with f8out): the statistics alone, same partial rows
 // last up-block join + one-plane tail conv as a per-wave MFMA stream (conv_fstream.hip; bf16, 64x64): returns stats rows or an error
 bool tail_fwd_stream_ok(int dt, int OC, int H, int W);
 int launch_tail_fwd_stream(int dt, const void* y2, const float* s2, const float* b2, const void* ys, const float* ss, const float* bs, const float* w,
                            const float* bias, float* r_raw, float* stats, int N, int H, int W, hipStream_t s, int f8in = 0);
-// the same with the two branch outputs recomputed from the ConvTranspose2d inputs instead of read (conv_fstream.hip; bf16, 32x32 -> 64x64, 16 channels)
+// the same with the two branch outputs recomputed from the ConvTranspose2d inputs instead of read (conv_fstream.hip; bf16, 32x32 -> 64x64, 16 channels);
+// y2 / ys (both or neither): the kernel also stores the branch outputs [N][64][64][16] bf16, bit-identical to launch_convT4_stream's
 bool up5_tail_fwd_ok(int dt, int OC, int C, int Cin, int Hin, int Hout);
 int launch_up5_tail_fwd(const void* y1, const float* p1s, const float* p1b, const void* w2_up, const void* xin, const float* pxs, const float* pxb,
                         const void* wu_up, const float* s2, const float* b2, const float* ss, const float* bs, const float* w, const float* bias,
-                        float* r_raw, float* stats, int N, hipStream_t s);
+                        float* r_raw, float* stats, int N, hipStream_t s, void* y2 = nullptr, void* ys = nullptr);
 // stem forward as a per-wave stream (bf16; stem_bwd.hip): returns stats rows (> 0) or an error
 bool stem_fwd_stream_ok(int dt, int S);
 int launch_stem_fwd_stream(int dt, const void* x, const float* w, void* y, float* stats, int N, int S, hipStream_t s);

@@ -845,17 +845,29 @@ int Net::decoder_fwd(int N, const float* encv, const float* params, float* bnbuf
     xin = base + P.act0d; xs = xb = nullptr;
   }
   int c1_done = 0;                 // rows of bn1 statistics the previous block's join kernel left for this block's conv1 (0: conv1 not done)
+  // The last block on the up5_tail_fwd route: that kernel recomputes both ConvTranspose2d outputs anyway and STORES them (y2 / ys, for the
+  // backward pass) beside its LDS-bound work, so the two ConvTranspose2d launches in front of it only take the batch statistics (y == nullptr:
+  // no 1.34 GB of stores in front of the join).  In eval mode the BatchNorms are folded and nothing reads y2 / ys: no launches, no stores.
+  bool up5_route = false;
+  if (nd > 0 && tail_fwd_fused()) {
+    const Block& B = dec.back();
+    up5_route = !store8 && !B.identity && !B.c2.fp8 && !B.cs.fp8 && tail_fwd_stream_ok(dt(), cfg.out_ch, Sd, Sd) &&
+                up5_tail_fwd_ok(dt(), cfg.out_ch, B.C, B.Cin, B.Hin, B.Hout) && convT4_stream_ok(dt(), B.c2.D0, B.c2.D1, B.c2.k, B.c2.s, B.c2.p, B.Hin, B.Win) &&
+                convT4_stream_ok(dt(), B.cs.D0, B.cs.D1, B.cs.k, B.cs.s, B.cs.p, B.Hin, B.Win);
+  }
   for (int i = 0; i < nd; ++i) {
     Block& B = dec[i];
     const double cnt = (double)N * B.Hout * B.Wout;
     const BnRows r1 = ps.rows(B.b1), r2 = ps.rows(B.b2);
     const Shortcut sc = ps.shortcut(B, xin);
+    const bool stats_only = up5_route && i == nd - 1;      // (then both launches below are convT4_stream launches: up5_route checked it)
     // upsample (shortcut) branch on the side stream, concurrently with conv1 -> bn1 -> conv2 -> bn2
     if (!B.identity) {
       MM_TRY(side_fork(s));
       hipStream_t ss = wgrad_stream(s);
-      if (!B.cs.fp8 && convT4_stream_ok(dt(), B.cs.D0, B.cs.D1, B.cs.k, B.cs.s, B.cs.p, B.Hin, B.Win))
-        np = launch_convT4_stream(dt(), xin, ps.packed(B.cs.packU), base + B.ys, xs, xb, 1, stats ? stats + kPartialFloats : nullptr,
+      if (stats_only && !stats) np = 1;
+      else if (!B.cs.fp8 && convT4_stream_ok(dt(), B.cs.D0, B.cs.D1, B.cs.k, B.cs.s, B.cs.p, B.Hin, B.Win))
+        np = launch_convT4_stream(dt(), xin, ps.packed(B.cs.packU), stats_only ? nullptr : base + B.ys, xs, xb, 1, stats ? stats + kPartialFloats : nullptr,
                                   N, B.Hin, ss, (store8 && i == nd - 1) ? 1 : 0);
       else
         np = run_up(ps, B.cs, xin, B.Hin, B.Win, base + B.ys, B.Hout, B.Wout, xs, xb, 1, stats ? stats + kPartialFloats : nullptr, 0, ss);
@@ -870,8 +882,9 @@ int Net::decoder_fwd(int N, const float* encv, const float* params, float* bnbuf
     if (B.identity)    // 3x3 Conv2d, shape preserving
       np = run_down(ps, B.c2, base + B.y1, B.Hin, B.Win, base + B.y2, B.Hout, B.Wout, r1.scale, r1.shift, 1, stats, 0, dt(), s);
     else
-      if (!B.c2.fp8 && convT4_stream_ok(dt(), B.c2.D0, B.c2.D1, B.c2.k, B.c2.s, B.c2.p, B.Hin, B.Win))   // per-wave stream (conv_fstream.hip)
-        np = launch_convT4_stream(dt(), base + B.y1, ps.packed(B.c2.packU), base + B.y2, r1.scale, r1.shift, 1, stats, N, B.Hin, s,
+      if (stats_only && !stats) np = 1;
+      else if (!B.c2.fp8 && convT4_stream_ok(dt(), B.c2.D0, B.c2.D1, B.c2.k, B.c2.s, B.c2.p, B.Hin, B.Win))   // per-wave stream (conv_fstream.hip)
+        np = launch_convT4_stream(dt(), base + B.y1, ps.packed(B.c2.packU), stats_only ? nullptr : base + B.y2, r1.scale, r1.shift, 1, stats, N, B.Hin, s,
                                   (store8 && i == nd - 1) ? 1 : 0);
       else
         np = run_up(ps, B.c2, base + B.y1, B.Hin, B.Win, base + B.y2, B.Hout, B.Wout, r1.scale, r1.shift, 1, stats, 0, s);
@@ -900,11 +913,12 @@ int Net::decoder_fwd(int N, const float* encv, const float* params, float* bnbuf
     const Block& B = dec.back();     // (the join left to this kernel: xin is still the block's input)
     const BnRows r1 = ps.rows(B.b1), r2 = ps.rows(B.b2);
     const Shortcut sc = ps.shortcut(B, xin);
-    if (!store8 && !B.identity && !B.c2.fp8 && !B.cs.fp8 && tail_fwd_stream_ok(dt(), cfg.out_ch, Sd, Sd) &&
-        up5_tail_fwd_ok(dt(), cfg.out_ch, B.C, B.Cin, B.Hin, B.Hout) && convT4_stream_ok(dt(), B.c2.D0, B.c2.D1, B.c2.k, B.c2.s, B.c2.p, B.Hin, B.Win))
-      // the join + tail conv with both branch outputs recomputed from the ConvTranspose2d inputs (0.34 GB) instead of read back (1.34 GB)
+    if (up5_route)
+      // the join + tail conv with both branch outputs recomputed from the ConvTranspose2d inputs (0.34 GB) instead of read back (1.34 GB),
+      // and (training) stored from here for the backward pass
       np = launch_up5_tail_fwd(base + B.y1, r1.scale, r1.shift, ps.packed(B.c2.packU), xin, xs, xb, ps.packed(B.cs.packU), r2.scale, r2.shift,
-                               sc.scale, sc.shift, params + tail.off, params + tail_bias, r_raw, stats, N, s);
+                               sc.scale, sc.shift, params + tail.off, params + tail_bias, r_raw, stats, N, s,
+                               stats ? base + B.y2 : nullptr, stats ? base + B.ys : nullptr);
     else if (tail_fwd_stream_ok(dt(), cfg.out_ch, Sd, Sd))
       np = launch_tail_fwd_stream(dt(), base + B.y2, r2.scale, r2.shift, sc.y, sc.scale, sc.shift, params + tail.off, params + tail_bias,
                                   r_raw, stats, N, Sd, Sd, s, store8 ? 1 : 0);
