@@ -134,6 +134,12 @@ MMVAE_API void* mmvae_net_side_stream(mmvae_net* net);
  * by the loaders of the two fused ConvTranspose2d backward passes -- no apply pass, no dy tensors.  0: reduce -> apply -> consumers, the form
  * every other block uses.  Same arithmetic per element; the parity tests compare the two. */
 MMVAE_API int mmvae_net_set_join_grad(mmvae_net* net, int enable);
+/* Which kernel route every block takes at batch size N, as text: one line per block (`encoder.layer1.0: fwd_c1_cs_stream=1 ...`,
+ * `decoder.uplayer5.0: ...`) and a last line `net: ...` for the boundary layers, 0 / 1 per field (tail_fwd: GATHER, JOIN, STREAM or UP5); the
+ * fields are DESIGN.md section 5's.  The routes are settled with the plan of N, before anything is enqueued: where the forward's and the
+ * backward's routes do not fit each other this call and every network entry point return MMVAE_ERR_UNSUPPORTED and mmvae_last_error names the
+ * rule.  Writes at most cap bytes (NUL-terminated) and returns the bytes needed, terminator included.  Host only: needs no device. */
+MMVAE_API int mmvae_net_describe_routes(mmvae_net* net, int N, char* buf, int cap);
 
 /* SyncBN: BatchNorm statistics over the global batch of a data-parallel job.  `fn` must SUM the `n` f32 values at
  * device pointer `buf` over all ranks in place, ordered on `stream` (the caller's stream or the net's side stream), and return 0;

@@ -132,6 +132,15 @@ int mmvae_net_set_join_grad(mmvae_net* n, int enable) {
   return MMVAE_OK;
 }
 
+int mmvae_net_describe_routes(mmvae_net* n, int N, char* buf, int cap) {
+  if (!n || N <= 0 || cap < 0 || (!buf && cap > 0)) { set_error("net_describe_routes: bad argument"); return MMVAE_ERR_ARG; }
+  std::string text;
+  const int rc = n->net->describe_routes(N, text);
+  if (rc < 0) return rc;
+  if (cap > 0) { std::strncpy(buf, text.c_str(), cap - 1); buf[cap - 1] = 0; }
+  return (int)text.size() + 1;
+}
+
 void* mmvae_net_side_stream(mmvae_net* n) { return n ? reinterpret_cast<void*>(n->net->side()) : nullptr; }
 
 int mmvae_net_set_sync_bn(mmvae_net* n, mmvae_allreduce_fn fn, void* user, int world) {

@@ -228,12 +228,130 @@ const Plan& Net::plan(int N) {
   P.stem_R = take(1024 * 8);
   P.stem_gram = take(1024L * stem_bwd_part_floats() * 4);
   P.bytes = (size_t)cur;
+  settle_routes(N, P.route);
   plan_ = P;
   return plan_;
 }
 
+static inline ConvGeom geom(const ConvW& w) { return ConvGeom{w.D0, w.D1, w.k, w.s, w.p}; }
+// Which kernel takes each launch of a train step at batch size N: the only place that asks the kernels' shape predicates (the constructor's store8
+// guess aside).  One field per decision; the rules at the end are what forward and backward must agree on about what the forward stored.
+void Net::settle_routes(int N, NetRoute& R) {
+  const int nd = (int)dec.size();
+  R = NetRoute(); R.store8 = store8;
+  R.stem_fwd_stream = cfg.in_ch == 1 && stem_fwd_stream_ok(dt(), cfg.S);
+  // the stem's backward in one pass (stem_bwd.hip); where the shape does not fit: reduce -> apply -> im2col -> wgrad
+  // (measured: im2col + 1x1 weight gradient 0.39 ms, a planar-G patch-tile path 0.42 ms)
+  R.stem_bwd_fused = cfg.in_ch == 1 && stem_bwd_fusable(cfg.S);
+  for (size_t i = 0; i < enc.size(); ++i) {
+    Block& B = enc[i];
+    BlockRoute& r = B.r = BlockRoute();
+    const ConvW &g = B.c1, &gs = B.cs;
+    const bool plain = !B.identity && !g.fp8 && !gs.fp8;
+    // encoder.layer1 (32 -> 32 channels, bf16): conv1 AND the 1x1 shortcut from ONE read of the block input, conv2 likewise a per-wave
+    // stream (conv_fstream.hip); both BatchNorms finalise on the caller's stream
+    r.fwd_c1_cs_stream = plain && gs.k == 1 && gs.s == 2 && conv3_stream_ok(dt(), B.Cin, B.C, g.k, g.s, g.p, B.Hin, B.Win);
+    r.fwd_c2_stream = !B.c2.fp8 && conv3_stream_ok(dt(), B.C, B.C, B.c2.k, B.c2.s, B.c2.p, B.Hout, B.Wout);
+    // conv1 (3x3 s2) + 1x1 s2 shortcut weight gradients in one stream pass: encoder.layer1's shape (bf16, 32 -> 32 channels, 32x32 -> 16x16)
+    r.bwd_pair_wgrad = plain && dt() == DT_BF16 && g.k == 3 && g.s == 2 && g.p == 1 && gs.k == 1 && gs.s == 2 && gs.p == 0 && g.D0 == 32 &&
+                       g.D1 == 32 && gs.D0 == 32 && gs.D1 == 32 && B.Hout == 16 && B.Hin == 32;
+    // encoder.layer1 (the block the step ends on): conv2's weight gradient is a stream pass, whose reduce can wait (encoder_bwd says for what)
+    r.bwd_c2_late_reduce = i == 0 && !B.c2.fp8 && op_wgrad_is_stream(dt(), geom(B.c2), N, B.Hout, B.Wout, B.Hout, B.Wout, false, true);
+    // encoder.layer1.conv2's data gradient + bn1's backward sums in one stream pass (bf16, 32 -> 32 channels, 16x16 maps, one block per stage)
+    r.bwd_c2_dgrad_stream = i == 0 && !B.identity && r.fwd_c2_stream;
+  }
+  // The stem's backward recomputes its incoming gradient (encoder.layer1's conv1 3x3 s2 + 1x1 s2 shortcut data gradients) instead of reading it:
+  // bf16, 64x64 images, the reference's first stage (32 -> 32 channels, strided block with a 1x1 shortcut), row-major packed weights
+  const Block& E = enc[0];
+  R.stem_dg_fused = R.stem_bwd_fused && stem_bwd_dg_ok(dt(), cfg.S) && E.r.bwd_pair_wgrad && E.c1.wscale == 1.f && E.cs.wscale == 1.f && !E.c1.fragU &&
+                    !E.cs.fragU && H1 == 32;
+  // The tail conv's input gradient is not materialised where the shape allows: the last up-block's join backward recomputes it from d_raw
+  // (launch_tail_join_bwd_*) -- as one pass over the whole block (conv_joinbwd.hip: dy2 / dys are produced row by row inside the kernel that consumes
+  // them -- both ConvTranspose2d weight gradients, both data gradients, bn1's backward sums -- and never stored) or as reduce -> apply
+  Block& L = dec.back();
+  R.tail_bwd_fused = L.C == 16 && tail_join_fusable(dt(), cfg.out_ch, N, Sd, Sd);
+  const bool last_js = R.tail_bwd_fused && !L.identity && !L.c2.fp8 && !L.cs.fp8 && !L.c1.fp8 && L.Cin == 16 && join_bwd_stream_ok(dt(), cfg.out_ch, L.C, L.Hin, L.Hout);
+  for (int i = 0; i < nd; ++i) {
+    Block& B = dec[i];
+    BlockRoute& r = B.r = BlockRoute();
+    r.bwd_join_stream = last_js && i == nd - 1;
+    // the two ConvTranspose2d forwards as per-wave streams (conv_fstream.hip)
+    r.fwd_cs_stream = !B.identity && !B.cs.fp8 && convT4_stream_ok(dt(), B.cs.D0, B.cs.D1, B.cs.k, B.cs.s, B.cs.p, B.Hin, B.Win);
+    r.fwd_c2_stream = !B.identity && !B.c2.fp8 && convT4_stream_ok(dt(), B.c2.D0, B.c2.D1, B.c2.k, B.c2.s, B.c2.p, B.Hin, B.Win);
+    // the join, fused with the next block's 1x1 conv1 and bn1's statistics where that block's conv1 is 16-wide (uplayer3 -> 4, uplayer4 -> 5):
+    // the joined row is the conv's operand while it is in LDS -- one launch and one pass over `out` fewer than join -> conv
+    if (i + 1 < nd && !B.identity && !dec[i + 1].identity) {
+      const ConvW& n1 = dec[i + 1].c1;
+      r.fwd_join_conv1 = !n1.fp8 && n1.k == 1 && n1.s == 1 && n1.D1 == B.C && !n1.fragD && n1.wscale == 1.f &&
+                         join_conv1_fwd_ok(dt(), B.C, n1.D0, (long)N * B.Hout * B.Wout);
+    }
+    // Where the shape allows (uplayer4 / uplayer5: 16 output channels, 16x16 -> 32x32 or 32x32 -> 64x64, bf16) dgrad and wgrad of a ConvT
+    // are ONE pass over its dy tensor on the caller's stream (wgrad_stream_kernel with DG): dy2 / dys (671 MB each at N = 5120 in
+    // uplayer5) are read once instead of twice.  (Not asked where join_bwd_stream takes the whole block.)
+    const bool own = !B.identity && !r.bwd_join_stream;
+    r.bwd_fuse_c2 = own && !B.c2.fp8 && op_bwd_fusable(dt(), geom(B.c2), N, B.Hin, B.Win, B.Hout, B.Wout);
+    r.bwd_fuse_cs = own && !B.cs.fp8 && op_bwd_fusable(dt(), geom(B.cs), N, B.Hin, B.Win, B.Hout, B.Wout) && B.C == 16;
+    // Join-gradient form of a block's backward (blocks on 16-wide maps, uplayer4): the block above hands down its input gradient already masked
+    // by this block's join ReLU (conv1_bwd_stream_kernel, MASK: join_bwd_stream's block), the BatchNorm-backward reduce runs unmasked, and dy2 / dys
+    // are evaluated by the loaders of the two fused passes -- the bn_bwd_apply launch (840 MB at N = 5120) and both dy tensors disappear.
+    r.bwd_join_grad = last_js && i == nd - 2 && dt() == DT_BF16 && join_grad_ && own && B.C == 16 && !B.c2.fp8 && !B.cs.fp8 && !B.c1.fp8 &&
+                      !(i == 0 && cfg.blocks <= 1) && op_bwd_fusable_jg(dt(), geom(B.c2), N, B.Hin, B.Win, B.Hout, B.Wout, true, false, true) &&
+                      op_bwd_fusable_jg(dt(), geom(B.cs), N, B.Hin, B.Win, B.Hout, B.Wout, false, true, false);
+  }
+  // Last up-block forward as one kernel (join + tail conv, the joined activation is never stored); the backward then needs the recomputing wgrad
+  // (tail_wg_in_reduce: inside the join-backward reduce pass) and the recomputing join backward.  Shapes it does not take keep join -> conv.
+  // (N does not enter the geometry checks beyond the tile count limit, which the plan's maximum batch already satisfies)
+  const bool fused = L.C == 16 && tail_fwd_fusable(dt(), cfg.out_ch, 1, Sd, Sd) && tail_join_fusable(dt(), cfg.out_ch, 1, Sd, Sd);
+  const bool stream = tail_fwd_stream_ok(dt(), cfg.out_ch, Sd, Sd);
+  // The up5_tail_fwd route: that kernel recomputes both ConvTranspose2d outputs anyway and STORES them (y2 / ys, for the backward pass) beside its
+  // LDS-bound work, so the two ConvTranspose2d launches in front of it only take the batch statistics (fwd_stats_only: y == nullptr, no 1.34 GB of
+  // stores in front of the join).  In eval mode the BatchNorms are folded and nothing reads y2 / ys: no launches, no stores.
+  L.r.fwd_stats_only = fused && !R.store8 && stream && up5_tail_fwd_ok(dt(), cfg.out_ch, L.C, L.Cin, L.Hin, L.Hout) && L.r.fwd_c2_stream && L.r.fwd_cs_stream;
+  R.tail_fwd = !fused ? TAIL_GATHER : L.r.fwd_stats_only ? TAIL_UP5 : stream ? TAIL_STREAM : TAIL_JOIN;
+  R.tail_wg_in_reduce = fused && R.tail_bwd_fused;
+  // ---- what the forward stored is what the backward reads (the first broken rule is reported)
+  if (R.store8 && R.tail_fwd == TAIL_GATHER) R.refused = "fp8 storage of the last up-block needs the fused tail kernels";
+  else if (R.store8 && R.tail_fwd != TAIL_STREAM) R.refused = "fp8 storage of the last up-block needs tail_fwd_stream";
+  else if (R.store8 && !R.tail_wg_in_reduce) R.refused = "fp8 storage of the last up-block needs the fused tail backward";
+  else if (R.tail_fwd != TAIL_GATHER && !R.tail_wg_in_reduce) R.refused = "decoder_bwd: the fused tail forward (no stored join) needs the fused tail backward";
+  else if (R.store8 && !last_js) R.refused = "fp8 storage of the last up-block needs join_bwd_stream";
+  for (const Block& B : dec)
+    if (!R.refused && B.r.bwd_join_grad && !(B.r.bwd_fuse_c2 && B.r.bwd_fuse_cs)) R.refused = "decoder_bwd: the join-gradient form needs both fused passes";
+}
+
+int Net::describe_routes(int N, std::string& out) {
+  const NetRoute& R = plan(N).route;
+  if (R.refused) { set_error("%s", R.refused); return MMVAE_ERR_UNSUPPORTED; }
+  const int nb = cfg.blocks < 1 ? 1 : cfg.blocks;
+  auto line = [&](const std::string& name, std::initializer_list<std::pair<const char*, int>> fields) {
+    out += name + ":";
+    for (const auto& f : fields) out += std::string(" ") + f.first + "=" + std::to_string(f.second);
+    out += "\n";
+  };
+  out.clear();
+  for (size_t i = 0; i < enc.size(); ++i) {
+    const BlockRoute& r = enc[i].r;
+    line("encoder.layer" + std::to_string(i / nb + 1) + "." + std::to_string(i % nb),
+         {{"fwd_c1_cs_stream", r.fwd_c1_cs_stream}, {"fwd_c2_stream", r.fwd_c2_stream}, {"bwd_pair_wgrad", r.bwd_pair_wgrad},
+          {"bwd_c2_late_reduce", r.bwd_c2_late_reduce}, {"bwd_c2_dgrad_stream", r.bwd_c2_dgrad_stream}});
+  }
+  for (size_t i = 0; i < dec.size(); ++i) {
+    const BlockRoute& r = dec[i].r;
+    line("decoder.uplayer" + std::to_string(i / nb + 1) + "." + std::to_string(i % nb),
+         {{"fwd_cs_stream", r.fwd_cs_stream}, {"fwd_c2_stream", r.fwd_c2_stream}, {"fwd_stats_only", r.fwd_stats_only},
+          {"fwd_join_conv1", r.fwd_join_conv1}, {"bwd_join_grad", r.bwd_join_grad}, {"bwd_join_stream", r.bwd_join_stream},
+          {"bwd_fuse_c2", r.bwd_fuse_c2}, {"bwd_fuse_cs", r.bwd_fuse_cs}});
+  }
+  static const char* const kTail[] = {"GATHER", "JOIN", "STREAM", "UP5"};
+  out += std::string("net: stem_fwd_stream=") + std::to_string(R.stem_fwd_stream) + " stem_bwd_fused=" + std::to_string(R.stem_bwd_fused) +
+         " stem_dg_fused=" + std::to_string(R.stem_dg_fused) + " tail_fwd=" + kTail[R.tail_fwd] + " tail_bwd_fused=" + std::to_string(R.tail_bwd_fused) +
+         " tail_wg_in_reduce=" + std::to_string(R.tail_wg_in_reduce) + " store8=" + std::to_string(R.store8) + "\n";
+  return MMVAE_OK;
+}
+
 int Net::begin_pass(Pass& ps, int N, void* ws, size_t ws_bytes, const float* params, float* grads, float* bnbuf, long long* nbt, bool training) {
   const Plan& P = plan(N);
+  if (P.route.refused) { set_error("%s", P.route.refused); return MMVAE_ERR_UNSUPPORTED; }
   if (ws_bytes < P.bytes) { set_error("workspace too small: %zu < %zu", ws_bytes, P.bytes); return MMVAE_ERR_WORKSPACE; }
   ps.P = &P; ps.base = static_cast<char*>(ws); ps.params = params; ps.grads = grads; ps.bnbuf = bnbuf; ps.nbt = nbt; ps.N = N;
   ps.training = training; ps.esz = esz();
@@ -249,8 +367,6 @@ int Net::fill_consts(const Pass& ps, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------------ conv helpers
-static inline ConvGeom geom(const ConvW& w) { return ConvGeom{w.D0, w.D1, w.k, w.s, w.p}; }
-
 // The pack that feeds a conv's FORWARD direction (down for Conv2d, up for ConvTranspose2d) is e4m3 bytes on an fp8 layer; every pack of an
 // fp8 layer carries its weight scale.  Fragment-major or plain: settled per layer in settle_layout().
 int Net::pack_down(const Pass& ps, const ConvW& w, hipStream_t s) {
@@ -304,12 +420,6 @@ int Net::side_join(hipStream_t s) {
   return MMVAE_OK;
 }
 
-// the stem's backward in one pass (stem_bwd.hip); where the shape does not fit: reduce -> apply -> im2col -> wgrad
-// (measured: im2col + 1x1 weight gradient 0.39 ms, a planar-G patch-tile path 0.42 ms)
-bool Net::stem_bwd_fused() const {
-  return cfg.in_ch == 1 && stem_bwd_fusable(cfg.S);
-}
-
 int Net::side_mark(int slot) {
   if (side_state_ != 1) return MMVAE_OK;
   bool ok = hipEventRecord(blk_ev_[slot & 15], side_) == hipSuccess;
@@ -337,34 +447,6 @@ int Net::reduce_wgrad_parts(const Pass& ps, const ConvW& w, const float* parts, 
   u.Ca_valid = w.D0; u.Cb_valid = w.D1; u.sA = w.D1 * ntaps; u.sB = ntaps; u.scale = w.wscale;
   for (int t = 0; t < ntaps; ++t) u.tap_off[t] = t;
   return launch_wgrad_reduce(u, s);
-}
-
-// conv1 (3x3 s2) + 1x1 s2 shortcut weight gradients in one stream pass: encoder.layer1's shape (bf16, 32 -> 32 channels, 32x32 -> 16x16)
-static bool wgrad_pair_ok(int dt, const ConvGeom& g, const ConvGeom& gs, int Hout, int Hin) {
-  return dt == DT_BF16 && g.k == 3 && g.s == 2 && g.p == 1 && gs.k == 1 && gs.s == 2 && gs.p == 0 && g.D0 == 32 && g.D1 == 32 && gs.D0 == 32 &&
-         gs.D1 == 32 && Hout == 16 && Hin == 32;
-}
-
-// encoder.layer1.conv2's data gradient + bn1's backward sums in one stream pass (bf16, 32 -> 32 channels, 16x16 maps, one block per stage)
-bool Net::l1_dgrad_stream() const {
-  if (enc.empty()) return false;
-  const Block& B = enc[0];
-  return !B.identity && !B.c2.fp8 && conv3_stream_ok(dt(), B.C, B.C, B.c2.k, B.c2.s, B.c2.p, B.Hout, B.Wout);
-}
-
-// The stem's backward recomputes its incoming gradient (encoder.layer1's conv1 3x3 s2 + 1x1 s2 shortcut data gradients) instead of reading it:
-// bf16, 64x64 images, the reference's first stage (32 -> 32 channels, strided block with a 1x1 shortcut), row-major packed weights
-bool Net::stem_dg_fused() const {
-  if (enc.empty() || !stem_bwd_fused() || !stem_bwd_dg_ok(dt(), cfg.S)) return false;
-  const Block& B = enc[0];
-  return !B.identity && B.Cin == 32 && B.C == 32 && B.c1.k == 3 && B.c1.s == 2 && B.c1.p == 1 && B.cs.k == 1 && B.cs.s == 2 && B.cs.p == 0 &&
-         !B.c1.fp8 && !B.cs.fp8 && B.c1.wscale == 1.f && B.cs.wscale == 1.f && !B.c1.fragU && !B.cs.fragU && H1 == 32 && B.Hout == 16;
-}
-
-bool Net::tail_fwd_fused() const {
-  // N does not enter the geometry checks beyond the tile count limit, which the plan's maximum batch already satisfies
-  return !dec.empty() && dec.back().C == 16 && tail_fwd_fusable(dt(), cfg.out_ch, 1, Sd, Sd) &&
-         tail_join_fusable(dt(), cfg.out_ch, 1, Sd, Sd);
 }
 
 // SyncBN: sum the partial rows locally, let the host's collective sum the row over the ranks (stream-ordered), and hand the
@@ -458,6 +540,28 @@ int Net::bn_backward_coefs_join(const Pass& ps, const Bn& b2, const Bn& bs, int 
   g2.dgamma = g2.dbeta = gs.dgamma = gs.dbeta = nullptr;
   return launch_bn_bwd_finalize2(g2, gs, s);
 }
+int Net::bn_relu_backward(const Pass& ps, const Bn& bn, const void* g, const void* y, void* dy, long npix, hipStream_t s, int nparts_ready) {
+  const BnRows r = ps.rows(bn);
+  const int np = nparts_ready > 0 ? nparts_ready : launch_bn_bwd_reduce(dt(), g, nullptr, r.scale, r.shift, y, nullptr, npix, bn.C, ps.part, s);
+  MM_TRY(np);
+  MM_TRY(bn_backward_coefs(ps, bn, np, 1, 0, (double)npix, s));
+  return launch_bn_bwd_apply(dt(), g, nullptr, r.scale, r.shift, y, r.A, r.B, r.C, dy, nullptr, nullptr, nullptr, nullptr, nullptr, npix, bn.C, s);
+}
+int Net::join_backward(const Pass& ps, const Block& B, const Shortcut& sc, const void* g, bool g_masked, void* dy2, void* dys, hipStream_t s,
+                       int nparts_ready) {
+  const BnRows r2 = ps.rows(B.b2);
+  const void* y2 = ps.base + B.y2;
+  const long npix = (long)ps.N * B.Hout * B.Wout;
+  const bool m = !g_masked;        // the reduce applies the join's ReLU mask itself
+  const int np = nparts_ready > 0 ? nparts_ready : launch_bn_bwd_reduce(dt(), g, nullptr, m ? r2.scale : nullptr, m ? r2.shift : nullptr, y2, sc.y, npix, B.C,
+                                                                        ps.part, s, m ? sc.scale : nullptr, m ? sc.shift : nullptr);
+  MM_TRY(np);
+  if (B.identity) MM_TRY(bn_backward_coefs(ps, B.b2, np, 2, 0, (double)npix, s));
+  else MM_TRY(bn_backward_coefs_join(ps, B.b2, B.bs, np, (double)npix, s));
+  if (!dy2) return MMVAE_OK;
+  return launch_bn_bwd_apply(dt(), g, nullptr, r2.scale, r2.shift, y2, r2.A, r2.B, r2.C, dy2, sc.y, sc.A, sc.B, sc.C, dys, npix, B.C, s, sc.scale,
+                             sc.shift);
+}
 
 // ------------------------------------------------------------------------------------------------ weight re-packs per entry point
 // (recorded by launch_pack() while a batch is open; see pack_batch_begin/flush)
@@ -498,7 +602,7 @@ int Net::packs_enc_bwd(const Pass& ps, hipStream_t s) {
     MM_TRY(pack_up(ps, B.c1, s));
     if (!B.identity) MM_TRY(pack_up(ps, B.cs, s));
   }
-  if (l1_dgrad_stream()) {
+  if (enc[0].r.bwd_c2_dgrad_stream) {
     // dx[n,h,w,ci] = sum_{kh,kw,co} dy[n, h+1-kh, w+1-kw, co] W[co][ci][kh][kw]: a forward 3x3 conv over dy with weights [ci][tap' = 8 - tap][co]
     const ConvW& w = enc[0].c2;
     PackArgs pf; std::memset(&pf, 0, sizeof(pf));
@@ -565,7 +669,7 @@ int Net::encoder_fwd(int N, const float* x, const float* params, float* bnbuf, l
   if (!training) MM_TRY(fold_bn_eval(ps, 0, s));
   if (!staged) MM_TRY(launch_convert(DT_F32, dt(), x, base + P.x_t, (long)N * cfg.in_ch * S * S, s));
   int np;
-  if (cfg.in_ch == 1 && stem_fwd_stream_ok(dt(), S)) {
+  if (P.route.stem_fwd_stream) {
     np = launch_stem_fwd_stream(dt(), base + P.x_t, params + stem.off, base + P.y0, stats, N, S, s);
   } else {
     // stem Conv2d(in_channels -> 32, k5 s2 p2) (model.py:94): the planar image (in_channels <= 4 planes) is staged as a zero-padded
@@ -590,13 +694,8 @@ int Net::encoder_fwd(int N, const float* x, const float* params, float* bnbuf, l
     const double cnt = (double)N * B.Hout * B.Wout;
     const BnRows r1 = ps.rows(B.b1), r2 = ps.rows(B.b2);
     const Shortcut sc = ps.shortcut(B, xin);
-    // shortcut branch (conv + its BatchNorm) on the side stream, concurrently with conv1 -> bn1 -> conv2 -> bn2
-    // encoder.layer1 (32 -> 32 channels, bf16): conv1 AND the 1x1 shortcut from ONE read of the block input, conv2 likewise a per-wave
-    // stream (conv_fstream.hip); both BatchNorms finalise on the caller's stream
-    const bool stream1 = !B.identity && !B.c1.fp8 && !B.cs.fp8 && B.cs.k == 1 && B.cs.s == 2 &&
-                         conv3_stream_ok(dt(), B.Cin, B.C, B.c1.k, B.c1.s, B.c1.p, B.Hin, B.Win);
-    const bool stream2 = !B.c2.fp8 && conv3_stream_ok(dt(), B.C, B.C, B.c2.k, B.c2.s, B.c2.p, B.Hout, B.Wout);
-    const bool fork = !B.identity && !stream1;
+    // shortcut branch (conv + its BatchNorm) on the side stream, concurrently with conv1 -> bn1 -> conv2 -> bn2 -- unless one kernel takes conv1 with it
+    const bool stream1 = B.r.fwd_c1_cs_stream, stream2 = B.r.fwd_c2_stream, fork = !B.identity && !stream1;
     if (stream1) {
       np = launch_conv3_stream(dt(), 2, xin, ps.packed(B.c1.packD), ps.packed(B.cs.packD), base + B.y1,
                                base + B.ys, xs, xb, 1, stats, stats ? stats + kPartialFloats : nullptr, N, B.Hout, s);
@@ -623,8 +722,7 @@ int Net::encoder_fwd(int N, const float* x, const float* params, float* bnbuf, l
     MM_TRY(np);
     MM_TRY(bn_fwd(ps, B.b2, np, cnt, s, 0, B.c2.wscale));
     if (fork) MM_TRY(side_join(s));
-    MM_TRY(launch_join_fwd(dt(), base + B.y2, r2.scale, r2.shift, sc.y, sc.scale, sc.shift, base + B.out,
-                           (long)N * B.Hout * B.Wout, B.C, s));
+    MM_TRY(launch_join_fwd(dt(), base + B.y2, r2.scale, r2.shift, sc.y, sc.scale, sc.shift, base + B.out, (long)N * B.Hout * B.Wout, B.C, s));
     xin = base + B.out; xs = xb = nullptr;
   }
   // global average pool + the two 1x1 heads (model.py:123-128) as ONE k=Hf,s=Hf conv whose taps share W/(Hf*Wf)
@@ -647,6 +745,7 @@ int Net::encoder_bwd(int N, const float* d_mu, const float* d_logvar, const floa
   const Plan& P = *ps.P;
   char* const base = ps.base;
   float* const part = ps.part;
+  const NetRoute& R = P.route;
   const BnRows r0 = ps.rows(bn0);
   const int Ch = cfg.need_logvar ? 2 * cfg.z : cfg.z;
   const int nt = Hf * Wf;
@@ -664,14 +763,14 @@ int Net::encoder_bwd(int N, const float* d_mu, const float* d_logvar, const floa
     MM_TRY(side_fork(s));
     MM_TRY(launch_wgrad(dt(), a, wgrad_stream(s)));
     // the stem's input-only work (patch gram matrix / im2col) early, off the tail of the critical path
-    if (stem_bwd_fused() && !(gram_ready_ && gram_fwd_N_ == N && gram_fwd_ws_ == ws)) {
+    if (R.stem_bwd_fused && !(gram_ready_ && gram_fwd_N_ == N && gram_fwd_ws_ == ws)) {
       MM_TRY(launch_stem_gram(dt(), base + P.x_t, reinterpret_cast<float*>(base + P.stem_gram), 1024L * stem_bwd_part_floats(),
                               reinterpret_cast<double*>(base + P.stem_R), N, cfg.S, H1, W1, wgrad_stream(s)));
       // the stem's finalize at the very end waits for THIS, not for the whole side stream (whose last weight gradients may still run)
       if (side_state_ == 1 && hipEventRecord(gram_ev_, side_) != hipSuccess) { set_error("side stream mark failed"); return MMVAE_ERR_HIP; }
     }
     gram_ready_ = false;            // (consumed: the next backward pass belongs to another forward pass)
-    if (!stem_bwd_fused() && cfg.in_ch == 1 && wgrad_stream(s) != s) MM_TRY(launch_stem_im2col(dt(), base + P.x_t, base + P.col, N, cfg.S, cfg.S, H1, W1, wgrad_stream(s)));
+    if (!R.stem_bwd_fused && cfg.in_ch == 1 && wgrad_stream(s) != s) MM_TRY(launch_stem_im2col(dt(), base + P.x_t, base + P.col, N, cfg.S, cfg.S, H1, W1, wgrad_stream(s)));
     GatherArgs g; std::memset(&g, 0, sizeof(g));
     g.x = base + P.dh; g.w = ps.packed(head_pack_dg); g.y = base + P.g[0];
     g.N = N; g.Hi = 1; g.Wi = 1; g.Cin = Ch; g.Ho = Hf; g.Wo = Wf; g.Cout = 256; g.SI = 1; g.SO = Hf;
@@ -685,11 +784,10 @@ int Net::encoder_bwd(int N, const float* d_mu, const float* d_logvar, const floa
   for (int i = ne - 1; i >= 0; --i) {
     Block& B = enc[i];
     const long npix = (long)N * B.Hout * B.Wout;
-    const double cnt = (double)npix;
     const void* xin = i == 0 ? base + P.y0 : base + enc[i - 1].out;
     const float* xs = i == 0 ? r0.scale : nullptr;
     const float* xb = i == 0 ? r0.shift : nullptr;
-    const BnRows r1 = ps.rows(B.b1), r2 = ps.rows(B.b2);
+    const BnRows r1 = ps.rows(B.b1);
     const Shortcut sc = ps.shortcut(B, xin);
     // dy1 / dy2 / dys alternate between two sets, so this block only has to wait for the weight gradients of the block
     // before the previous one (the side stream may lag one block behind)
@@ -703,12 +801,7 @@ int Net::encoder_bwd(int N, const float* d_mu, const float* d_logvar, const floa
     const long dyso = B.identity ? P.g[cur ^ 1] : (priv ? P.edys[i - (ne - 2)] : P.dys[ds]);
     if (i + 2 <= ne - 1) MM_TRY(side_wait_mark(i + 2, s));
     // join backward: g = d_out * [out > 0] feeds bn2 (y2) and the shortcut BN (ys)
-    int np = launch_bn_bwd_reduce(dt(), base + P.g[cur], nullptr, r2.scale, r2.shift, base + B.y2, sc.y, npix, B.C, part, s, sc.scale, sc.shift);
-    MM_TRY(np);
-    if (B.identity) MM_TRY(bn_backward_coefs(ps, B.b2, np, 2, 0, cnt, s));
-    else MM_TRY(bn_backward_coefs_join(ps, B.b2, B.bs, np, cnt, s));
-    MM_TRY(launch_bn_bwd_apply(dt(), base + P.g[cur], nullptr, r2.scale, r2.shift, base + B.y2, r2.A, r2.B, r2.C, base + dy2o, sc.y, sc.A, sc.B,
-                               sc.C, base + dyso, npix, B.C, s, sc.scale, sc.shift));
+    MM_TRY(join_backward(ps, B, sc, base + P.g[cur], false, base + dy2o, base + dyso, s));
     // conv2 (3x3 s1): wgrad with a1 = relu(bn1(y1)) recomputed in the load prologue; dgrad -> d_a1
     hipStream_t wsm = wgrad_stream(s);
     MM_TRY(side_fork(s));
@@ -718,26 +811,21 @@ int Net::encoder_bwd(int N, const float* d_mu, const float* d_logvar, const floa
     // AFTER the block's other weight gradient has been enqueued -- under the stem backward's load a 19 MB reduce takes 120 us instead of
     // 10, and it sat in front of the last big kernel of the side stream
     WgradReduceArgs late; late.nparts = 0;
-    if (i == 0 && wsm != s && !B.c2.fp8 && op_wgrad_is_stream(dt(), geom(B.c2), N, B.Hout, B.Wout, B.Hout, B.Wout, false, true))
+    if (B.r.bwd_c2_late_reduce && wsm != s)
       MM_TRY(op_run_wgrad(dt(), geom(B.c2), N, base + dy2o, B.Hout, B.Wout, nullptr, nullptr, 1, base + B.y1, B.Hout, B.Wout, r1.scale,
                           r1.shift, 1, grads + B.c2.off, wsm, reinterpret_cast<float*>(base + P.wscratch2), B.c2.wscale, &late));
     else
       MM_TRY(run_wgrad(ps, B.c2, base + dy2o, B.Hout, B.Wout, nullptr, nullptr, base + B.y1, B.Hout, B.Wout, r1.scale, r1.shift, wsm));
-    // (encoder.layer1: the shortcut's weight gradient rides on conv1's pass over the block input, below)
-    const bool pair = !B.identity && !B.c1.fp8 && !B.cs.fp8 && wgrad_pair_ok(dt(), geom(B.c1), geom(B.cs), B.Hout, B.Hin);
+    const bool pair = B.r.bwd_pair_wgrad;     // (encoder.layer1: the shortcut's weight gradient rides on conv1's pass over the block input, below)
     if (!B.identity && !pair) MM_TRY(run_wgrad(ps, B.cs, base + dyso, B.Hout, B.Wout, nullptr, nullptr, xin, B.Hin, B.Win, xs, xb, wsm));
-    if (i == 0 && l1_dgrad_stream()) {
+    int np1 = 0;                         // rows of bn1's backward sums when the data-gradient pass has left them in `part`
+    if (B.r.bwd_c2_dgrad_stream) {
       // encoder.layer1.conv2: the data gradient as a per-wave stream over dy2 (conv3_stream_kernel) with bn1's backward sums from the same pass
-      np = launch_conv3_stream_bwd(dt(), base + dy2o, ps.packed(l1c2_flip), base + P.da1, base + B.y1, r1.scale, r1.shift, part, N, B.Hout, s);
-    } else {
+      np1 = launch_conv3_stream_bwd(dt(), base + dy2o, ps.packed(l1c2_flip), base + P.da1, base + B.y1, r1.scale, r1.shift, part, N, B.Hout, s);
+      MM_TRY(np1);
+    } else
       MM_TRY(run_up(ps, B.c2, base + dy2o, B.Hout, B.Wout, base + P.da1, B.Hout, B.Wout, nullptr, nullptr, 0, nullptr, 0, s));
-      // bn1 + relu backward
-      np = launch_bn_bwd_reduce(dt(), base + P.da1, nullptr, r1.scale, r1.shift, base + B.y1, nullptr, npix, B.C, part, s);
-    }
-    MM_TRY(np);
-    MM_TRY(bn_backward_coefs(ps, B.b1, np, 1, 0, cnt, s));
-    MM_TRY(launch_bn_bwd_apply(dt(), base + P.da1, nullptr, r1.scale, r1.shift, base + B.y1, r1.A, r1.B, r1.C, base + dy1o, nullptr, nullptr,
-                               nullptr, nullptr, nullptr, npix, B.C, s));
+    MM_TRY(bn_relu_backward(ps, B.b1, base + P.da1, base + B.y1, base + dy1o, npix, s, np1));      // bn1 + relu backward
     // conv1 (3x3) and the 1x1 s2 shortcut: weight gradients, then d_xin = dgrad(conv1) + dgrad(shortcut)
     MM_TRY(side_fork(s));
     int taken = 0;
@@ -750,7 +838,7 @@ int Net::encoder_bwd(int N, const float* d_mu, const float* d_logvar, const floa
     if (!taken) MM_TRY(run_wgrad(ps, B.c1, base + dy1o, B.Hout, B.Wout, nullptr, nullptr, xin, B.Hin, B.Win, xs, xb, wsm));
     if (late.nparts > 0) MM_TRY(launch_wgrad_reduce(late, wsm));
     MM_TRY(side_mark(i));
-    if (i == 0 && stem_dg_fused()) {
+    if (i == 0 && R.stem_dg_fused) {
       // the gradient of the stem's output is never a tensor: stem_bwd_kernel<DG> recomputes it row by row from dy1 / dys (below)
       stem_dy1 = dy1o; stem_dys = dyso;
     } else if (B.identity)     // d_xin already holds the shortcut's share: the main path's data gradient is added to it
@@ -761,12 +849,12 @@ int Net::encoder_bwd(int N, const float* d_mu, const float* d_logvar, const floa
     cur ^= 1;
   }
   // ---- stem: bn0 + relu backward and the 5x5 weight gradient
-  if (stem_bwd_fused()) {
+  if (R.stem_bwd_fused) {
     // one pass over g and y0 (stem_bwd.hip): BatchNorm sums and the three pixel reductions dW is an affine function of; no dy
     // tensor, no im2col, nothing waits on a grid-wide reduction except the 32-block finalize
     const long npix = (long)N * H1 * W1;
     const Block& B0 = enc[0];
-    const int np = stem_dg_fused()
+    const int np = R.stem_dg_fused
         ? launch_stem_bwd_dg(base + stem_dy1, base + stem_dys, ps.packed(B0.c1.packU), ps.packed(B0.cs.packU), base + P.y0, base + P.x_t,
                              r0.scale, r0.shift, part, kPartialFloats, N, cfg.S, H1, W1, s)
         : launch_stem_bwd(dt(), base + P.g[cur], base + P.y0, base + P.x_t, r0.scale, r0.shift, part, kPartialFloats, N, cfg.S, H1, W1, s);
@@ -784,35 +872,26 @@ int Net::encoder_bwd(int N, const float* d_mu, const float* d_logvar, const floa
   }
   // ---- stem: bn0 + relu backward, then the 5x5 weight gradient
   MM_TRY(side_wait_mark(1, s));    // the stem uses dy set 1 (block index -1): block 1's weight gradients read it last
-  const int ds = 1;
-  {
-    const long npix = (long)N * H1 * W1;
-    int np = launch_bn_bwd_reduce(dt(), base + P.g[cur], nullptr, r0.scale, r0.shift, base + P.y0, nullptr, npix, 32, part, s);
-    MM_TRY(np);
-    MM_TRY(bn_backward_coefs(ps, bn0, np, 1, 0, (double)npix, s));
-    MM_TRY(launch_bn_bwd_apply(dt(), base + P.g[cur], nullptr, r0.scale, r0.shift, base + P.y0, r0.A, r0.B, r0.C, base + P.dy1[ds], nullptr,
-                               nullptr, nullptr, nullptr, nullptr, npix, 32, s));
-    MM_TRY(side_fork(s));
-    hipStream_t wsm = wgrad_stream(s);
-    WgradArgs a; std::memset(&a, 0, sizeof(a));
-    a.P = base + P.dy1[ds]; a.dW = grads + stem.off; a.scratch = ps.wscratch;
-    a.N = N; a.Hp = H1; a.Wp = W1; a.Ca = 32; a.scale = 1.f;
-    if (cfg.in_ch > 1) {
-      // in_channels > 1 (main.py:555): G = the image as NHWC with 16 zero-padded channels, the generic 25-tap weight gradient
-      MM_TRY(launch_planar_to_nhwc16(dt(), static_cast<const void*>(base + P.x_t), dt(), base + P.col, N, cfg.in_ch, cfg.S * cfg.S, wsm));
-      a.G = base + P.col; a.Hg = cfg.S; a.Wg = cfg.S; a.Cb = 16; a.Cb_valid = cfg.in_ch;
-      a.stride = 2; a.pad = 2; a.ksz = 5; a.sA = 25 * cfg.in_ch; a.sB = 25; a.ntaps = 25;
-      for (int t = 0; t < 25; ++t) a.tap_off[t] = t;
-    } else {
-      // im2col of the 1-channel image (25 taps padded to 32 columns) + the MFMA weight-gradient kernel as a 1x1 conv
-      if (wsm == s) MM_TRY(launch_stem_im2col(dt(), base + P.x_t, base + P.col, N, cfg.S, cfg.S, H1, W1, wsm));   // else: done early
-      a.G = base + P.col; a.Hg = H1; a.Wg = W1; a.Cb = 32; a.Cb_valid = 25;
-      a.stride = 1; a.pad = 0; a.ksz = 1; a.sA = 25; a.sB = 1; a.ntaps = 1;
-    }
-    MM_TRY(launch_wgrad(dt(), a, wsm));
-    MM_TRY(side_join(s));
+  MM_TRY(bn_relu_backward(ps, bn0, base + P.g[cur], base + P.y0, base + P.dy1[1], (long)N * H1 * W1, s));
+  MM_TRY(side_fork(s));
+  hipStream_t wsm = wgrad_stream(s);
+  WgradArgs a; std::memset(&a, 0, sizeof(a));
+  a.P = base + P.dy1[1]; a.dW = grads + stem.off; a.scratch = ps.wscratch;
+  a.N = N; a.Hp = H1; a.Wp = W1; a.Ca = 32; a.scale = 1.f;
+  if (cfg.in_ch > 1) {
+    // in_channels > 1 (main.py:555): G = the image as NHWC with 16 zero-padded channels, the generic 25-tap weight gradient
+    MM_TRY(launch_planar_to_nhwc16(dt(), static_cast<const void*>(base + P.x_t), dt(), base + P.col, N, cfg.in_ch, cfg.S * cfg.S, wsm));
+    a.G = base + P.col; a.Hg = cfg.S; a.Wg = cfg.S; a.Cb = 16; a.Cb_valid = cfg.in_ch;
+    a.stride = 2; a.pad = 2; a.ksz = 5; a.sA = 25 * cfg.in_ch; a.sB = 25; a.ntaps = 25;
+    for (int t = 0; t < 25; ++t) a.tap_off[t] = t;
+  } else {
+    // im2col of the 1-channel image (25 taps padded to 32 columns) + the MFMA weight-gradient kernel as a 1x1 conv
+    if (wsm == s) MM_TRY(launch_stem_im2col(dt(), base + P.x_t, base + P.col, N, cfg.S, cfg.S, H1, W1, wsm));   // else: done early
+    a.G = base + P.col; a.Hg = H1; a.Wg = W1; a.Cb = 32; a.Cb_valid = 25;
+    a.stride = 1; a.pad = 0; a.ksz = 1; a.sA = 25; a.sB = 1; a.ntaps = 1;
   }
-  return MMVAE_OK;
+  MM_TRY(launch_wgrad(dt(), a, wsm));
+  return side_join(s);
 }
 
 // ------------------------------------------------------------------------------------------------ decoder
@@ -824,6 +903,7 @@ int Net::decoder_fwd(int N, const float* encv, const float* params, float* bnbuf
   char* const base = ps.base;
   float* const part = ps.part;
   float* stats = training ? part : nullptr;
+  const NetRoute& R = P.route;
   pack_batch_begin();
   MM_TRY(packs_dec_fwd(ps, s));
   MM_TRY(pack_batch_flush(dt(), s));
@@ -845,32 +925,24 @@ int Net::decoder_fwd(int N, const float* encv, const float* params, float* bnbuf
     xin = base + P.act0d; xs = xb = nullptr;
   }
   int c1_done = 0;                 // rows of bn1 statistics the previous block's join kernel left for this block's conv1 (0: conv1 not done)
-  // The last block on the up5_tail_fwd route: that kernel recomputes both ConvTranspose2d outputs anyway and STORES them (y2 / ys, for the
-  // backward pass) beside its LDS-bound work, so the two ConvTranspose2d launches in front of it only take the batch statistics (y == nullptr:
-  // no 1.34 GB of stores in front of the join).  In eval mode the BatchNorms are folded and nothing reads y2 / ys: no launches, no stores.
-  bool up5_route = false;
-  if (nd > 0 && tail_fwd_fused()) {
-    const Block& B = dec.back();
-    up5_route = !store8 && !B.identity && !B.c2.fp8 && !B.cs.fp8 && tail_fwd_stream_ok(dt(), cfg.out_ch, Sd, Sd) &&
-                up5_tail_fwd_ok(dt(), cfg.out_ch, B.C, B.Cin, B.Hin, B.Hout) && convT4_stream_ok(dt(), B.c2.D0, B.c2.D1, B.c2.k, B.c2.s, B.c2.p, B.Hin, B.Win) &&
-                convT4_stream_ok(dt(), B.cs.D0, B.cs.D1, B.cs.k, B.cs.s, B.cs.p, B.Hin, B.Win);
-  }
   for (int i = 0; i < nd; ++i) {
     Block& B = dec[i];
     const double cnt = (double)N * B.Hout * B.Wout;
     const BnRows r1 = ps.rows(B.b1), r2 = ps.rows(B.b2);
     const Shortcut sc = ps.shortcut(B, xin);
-    const bool stats_only = up5_route && i == nd - 1;      // (then both launches below are convT4_stream launches: up5_route checked it)
+    // a ConvTranspose2d forward: the per-wave stream (conv_fstream.hip) where routed -- on the up5 route statistics only, nothing in eval mode -- else the up conv
+    auto convT = [&](const ConvW& w, bool stream, const void* x, long y, const float* pro_s, const float* pro_b, float* st, hipStream_t q) {
+      const bool stats_only = B.r.fwd_stats_only;
+      if (stats_only && !st) return 1;
+      if (stream) return launch_convT4_stream(dt(), x, ps.packed(w.packU), stats_only ? nullptr : base + y, pro_s, pro_b, 1, st, N, B.Hin, q,
+                                              (R.store8 && i == nd - 1) ? 1 : 0);
+      return run_up(ps, w, x, B.Hin, B.Win, base + y, B.Hout, B.Wout, pro_s, pro_b, 1, st, 0, q);
+    };
     // upsample (shortcut) branch on the side stream, concurrently with conv1 -> bn1 -> conv2 -> bn2
     if (!B.identity) {
       MM_TRY(side_fork(s));
       hipStream_t ss = wgrad_stream(s);
-      if (stats_only && !stats) np = 1;
-      else if (!B.cs.fp8 && convT4_stream_ok(dt(), B.cs.D0, B.cs.D1, B.cs.k, B.cs.s, B.cs.p, B.Hin, B.Win))
-        np = launch_convT4_stream(dt(), xin, ps.packed(B.cs.packU), stats_only ? nullptr : base + B.ys, xs, xb, 1, stats ? stats + kPartialFloats : nullptr,
-                                  N, B.Hin, ss, (store8 && i == nd - 1) ? 1 : 0);
-      else
-        np = run_up(ps, B.cs, xin, B.Hin, B.Win, base + B.ys, B.Hout, B.Wout, xs, xb, 1, stats ? stats + kPartialFloats : nullptr, 0, ss);
+      np = convT(B.cs, B.r.fwd_cs_stream, xin, B.ys, xs, xb, stats ? stats + kPartialFloats : nullptr, ss);
       MM_TRY(np);
       MM_TRY(bn_fwd(ps, B.bs, np, cnt, ss, kPartialFloats, B.cs.wscale));
     }
@@ -882,47 +954,34 @@ int Net::decoder_fwd(int N, const float* encv, const float* params, float* bnbuf
     if (B.identity)    // 3x3 Conv2d, shape preserving
       np = run_down(ps, B.c2, base + B.y1, B.Hin, B.Win, base + B.y2, B.Hout, B.Wout, r1.scale, r1.shift, 1, stats, 0, dt(), s);
     else
-      if (stats_only && !stats) np = 1;
-      else if (!B.c2.fp8 && convT4_stream_ok(dt(), B.c2.D0, B.c2.D1, B.c2.k, B.c2.s, B.c2.p, B.Hin, B.Win))   // per-wave stream (conv_fstream.hip)
-        np = launch_convT4_stream(dt(), base + B.y1, ps.packed(B.c2.packU), stats_only ? nullptr : base + B.y2, r1.scale, r1.shift, 1, stats, N, B.Hin, s,
-                                  (store8 && i == nd - 1) ? 1 : 0);
-      else
-        np = run_up(ps, B.c2, base + B.y1, B.Hin, B.Win, base + B.y2, B.Hout, B.Wout, r1.scale, r1.shift, 1, stats, 0, s);
+      np = convT(B.c2, B.r.fwd_c2_stream, base + B.y1, B.y2, r1.scale, r1.shift, stats, s);
     MM_TRY(np);
     MM_TRY(bn_fwd(ps, B.b2, np, cnt, s, 0, B.c2.wscale));
     if (!B.identity) MM_TRY(side_join(s));
-    if (i == nd - 1 && tail_fwd_fused()) break;     // the join of the last block happens inside the tail conv kernel
-    if (i == nd - 1 && store8) { set_error("fp8 storage of the last up-block needs the fused tail kernels"); return MMVAE_ERR_UNSUPPORTED; }
-    // the join, fused with the next block's 1x1 conv1 and bn1's statistics where that block's conv1 is 16-wide (uplayer3 -> 4, uplayer4 -> 5):
-    // the joined row is the conv's operand while it is in LDS -- one launch and one pass over `out` fewer than join -> conv
-    const bool fuse_c1 = i + 1 < nd && !B.identity && !dec[i + 1].identity && !dec[i + 1].c1.fp8 && dec[i + 1].c1.k == 1 && dec[i + 1].c1.s == 1 &&
-                         dec[i + 1].c1.D1 == B.C && !dec[i + 1].c1.fragD && dec[i + 1].c1.wscale == 1.f &&
-                         join_conv1_fwd_ok(dt(), B.C, dec[i + 1].c1.D0, (long)N * B.Hout * B.Wout);
-    if (fuse_c1) {
+    if (i == nd - 1 && R.tail_fwd != TAIL_GATHER) break;     // the join of the last block happens inside the tail conv kernel
+    if (B.r.fwd_join_conv1) {      // the join computes the next block's conv1 and bn1's statistics as well
       c1_done = launch_join_conv1_fwd(B.C, base + B.y2, r2.scale, r2.shift, sc.y, sc.scale, sc.shift, ps.packed(dec[i + 1].c1.packD),
                                       base + B.out, base + dec[i + 1].y1, stats, (long)N * B.Hout * B.Wout, s);
       MM_TRY(c1_done);
     } else
-    MM_TRY(launch_join_fwd(dt(), base + B.y2, r2.scale, r2.shift, sc.y, sc.scale, sc.shift, base + B.out,
-                           (long)N * B.Hout * B.Wout, B.C, s));
+    MM_TRY(launch_join_fwd(dt(), base + B.y2, r2.scale, r2.shift, sc.y, sc.scale, sc.shift, base + B.out, (long)N * B.Hout * B.Wout, B.C, s));
     xin = base + B.out; xs = xb = nullptr;
   }
   // tail conv (+bias) and the output BatchNorm (model.py:193)
   float* r_raw = reinterpret_cast<float*>(base + P.r_raw);
-  if (tail_fwd_fused()) {
+  if (R.tail_fwd != TAIL_GATHER) {
     const Block& B = dec.back();     // (the join left to this kernel: xin is still the block's input)
     const BnRows r1 = ps.rows(B.b1), r2 = ps.rows(B.b2);
     const Shortcut sc = ps.shortcut(B, xin);
-    if (up5_route)
+    if (R.tail_fwd == TAIL_UP5)
       // the join + tail conv with both branch outputs recomputed from the ConvTranspose2d inputs (0.34 GB) instead of read back (1.34 GB),
       // and (training) stored from here for the backward pass
       np = launch_up5_tail_fwd(base + B.y1, r1.scale, r1.shift, ps.packed(B.c2.packU), xin, xs, xb, ps.packed(B.cs.packU), r2.scale, r2.shift,
                                sc.scale, sc.shift, params + tail.off, params + tail_bias, r_raw, stats, N, s,
                                stats ? base + B.y2 : nullptr, stats ? base + B.ys : nullptr);
-    else if (tail_fwd_stream_ok(dt(), cfg.out_ch, Sd, Sd))
+    else if (R.tail_fwd == TAIL_STREAM)
       np = launch_tail_fwd_stream(dt(), base + B.y2, r2.scale, r2.shift, sc.y, sc.scale, sc.shift, params + tail.off, params + tail_bias,
-                                  r_raw, stats, N, Sd, Sd, s, store8 ? 1 : 0);
-    else if (store8) { set_error("fp8 storage of the last up-block needs tail_fwd_stream"); return MMVAE_ERR_UNSUPPORTED; }
+                                  r_raw, stats, N, Sd, Sd, s, R.store8 ? 1 : 0);
     else
       np = launch_tail_join_fwd(dt(), base + B.y2, r2.scale, r2.shift, sc.y, sc.scale, sc.shift, params + tail.off, params + tail_bias,
                                 r_raw, stats, N, Sd, Sd, s);
@@ -951,13 +1010,14 @@ int Net::decoder_bwd(int N, const float* d_recon, const float* params, float* gr
   float* r_raw = reinterpret_cast<float*>(base + P.r_raw);
   float* d_raw = reinterpret_cast<float*>(base + P.d_raw);
   const BnRows r0 = ps.rows(dbn0), ro = ps.rows(bn_out);
+  const NetRoute& R = P.route;
   const int HW = Sd * Sd;
   pack_batch_begin();
   MM_TRY(packs_dec_bwd(ps, d_enc != nullptr, s));
   MM_TRY(pack_batch_flush(dt(), s));
   // the encoder stem's patch gram matrix (input only; stem_bwd.hip): here the side stream is idle for ~1 ms beside HBM-bound kernels, at the
   // start of encoder_bwd it ran beside the latency-bound kernels around the latent code and held their small launches up (lesson 55)
-  if (stem_bwd_fused() && !gram_ready_ && gram_fwd_N_ == N && gram_fwd_ws_ == ws && wgrad_stream(s) != s) {
+  if (R.stem_bwd_fused && !gram_ready_ && gram_fwd_N_ == N && gram_fwd_ws_ == ws && wgrad_stream(s) != s) {
     MM_TRY(side_fork(s));
     MM_TRY(launch_stem_gram(dt(), base + P.x_t, reinterpret_cast<float*>(base + P.stem_gram), 1024L * stem_bwd_part_floats(),
                             reinterpret_cast<double*>(base + P.stem_R), N, cfg.S, H1, W1, wgrad_stream(s)));
@@ -978,12 +1038,7 @@ int Net::decoder_bwd(int N, const float* d_recon, const float* params, float* gr
                                    N, cfg.out_ch, HW, s));
   else
     MM_TRY(launch_bn_bwd_apply_nchw(d_recon, r_raw, ro.A, ro.B, ro.C, d_raw, N, cfg.out_ch, HW, s));
-  const bool tail_fused = !dec.empty() && dec.back().C == 16 && tail_join_fusable(dt(), cfg.out_ch, N, Sd, Sd);
-  // forward did not store the joined activation: the weight gradient recomputes it inside the join-backward reduce pass (below)
-  const bool tail_wg_in_reduce = tail_fwd_fused() && tail_fused;
-  if (store8 && !tail_wg_in_reduce) { set_error("fp8 storage of the last up-block needs the fused tail backward"); return MMVAE_ERR_UNSUPPORTED; }
-  if (!tail_wg_in_reduce) {
-    if (tail_fwd_fused()) { set_error("decoder_bwd: the fused tail forward (no stored join) needs the fused tail backward"); return MMVAE_ERR_UNSUPPORTED; }
+  if (!R.tail_wg_in_reduce) {      // (else the forward did not store the joined activation: the join-backward reduce pass below recomputes it)
     // dW[oc][ci][kh][kw]: P = d_raw (planar f32, out_ch planes staged as 16 zero-padded channels), G = the last up-block's output
     WgradArgs a; std::memset(&a, 0, sizeof(a));
     a.P = d_raw; a.P_planar = 1; a.P_planes = cfg.out_ch; a.G = base + dec.back().out; a.dW = grads + tail.off; a.scratch = ps.wscratch;
@@ -994,9 +1049,7 @@ int Net::decoder_bwd(int N, const float* d_recon, const float* params, float* gr
     MM_TRY(launch_wgrad(dt(), a, wgrad_stream(s)));
   }
   int cur = 0;
-  // The tail conv's input gradient is not materialised where the shape allows: the last up-block's join backward recomputes it from d_raw
-  // (launch_tail_join_bwd_*).  Otherwise the separate dgrad kernel:
-  if (!tail_fused) {
+  if (!R.tail_bwd_fused) {          // (else the last up-block's join backward recomputes the tail conv's input gradient from d_raw)
     // dx[n,h,w,ci] = sum dy[n,oc,h+1-kh,w+1-kw] * w[oc][ci][kh][kw]: planar f32 source padded to 8 channels in LDS
     GatherArgs a; std::memset(&a, 0, sizeof(a));
     a.x = d_raw; a.w = ps.packed(tail_pack_d); a.y = base + P.g[cur]; a.x_planar = 1; a.x_planes = cfg.out_ch;
@@ -1006,22 +1059,10 @@ int Net::decoder_bwd(int N, const float* d_recon, const float* params, float* gr
     MM_TRY(launch_gather_gemm(dt(), dt(), a, s));
   }
   const int nd = (int)dec.size();
-  // Join-gradient form of a block's backward (blocks on 16-wide maps, uplayer4): the block above hands down its input gradient already masked
-  // by this block's join ReLU (conv1_bwd_stream_kernel, MASK), the BatchNorm-backward reduce runs unmasked, and dy2 / dys are evaluated by the
-  // loaders of the two fused ConvTranspose2d backward passes -- the bn_bwd_apply launch (840 MB at N = 5120) and both dy tensors disappear.
-  auto jg_block = [&](int j) {
-    if (j < 0 || j >= nd || dt() != DT_BF16 || !join_grad_) return false;
-    const Block& Bj = dec[j];
-    if (Bj.identity || Bj.C != 16 || Bj.c2.fp8 || Bj.cs.fp8 || Bj.c1.fp8 || (j == 0 && cfg.blocks <= 1)) return false;
-    return op_bwd_fusable_jg(dt(), geom(Bj.c2), N, Bj.Hin, Bj.Win, Bj.Hout, Bj.Wout, true, false, true) &&
-           op_bwd_fusable_jg(dt(), geom(Bj.cs), N, Bj.Hin, Bj.Win, Bj.Hout, Bj.Wout, false, true, false);
-  };
-  bool g_masked = false;             // g[cur] is masked by the ReLU of the block about to run its backward
   for (int i = nd - 1; i >= 0; --i) {
     Block& B = dec[i];
-    const bool jg = g_masked;
-    g_masked = false;
-    const long npo = (long)N * B.Hout * B.Wout, npi = (long)N * B.Hin * B.Win;
+    const bool jg = B.r.bwd_join_grad;     // join-gradient form: g[cur] is already masked by this block's join ReLU (the block above did it)
+    const long npi = (long)N * B.Hin * B.Win;
     // (blocks > 1: block 0 has an identity shortcut and reads the stem's materialised activation)
     const void* xin = i == 0 ? (cfg.blocks > 1 ? base + P.act0d : base + P.y0d) : base + dec[i - 1].out;
     const float* xs = (i == 0 && cfg.blocks <= 1) ? r0.scale : nullptr;
@@ -1030,27 +1071,21 @@ int Net::decoder_bwd(int N, const float* d_recon, const float* params, float* gr
     const Shortcut sc = ps.shortcut(B, xin);
     const int ds = i & 1;          // dy set of this block (see encoder_bwd)
     if (i + 2 <= nd - 1) MM_TRY(side_wait_mark(i + 2, s));
-    const bool from_tail = tail_fused && i == nd - 1;
+    const bool from_tail = R.tail_bwd_fused && i == nd - 1;
     // an identity shortcut's gradient is the masked incoming gradient itself: it goes straight into the block-input gradient
     const long dyso = B.identity ? P.g[cur ^ 1] : P.dys[ds];
     if (from_tail) {
       np = launch_tail_join_bwd_reduce(dt(), d_raw, params + tail.off, cfg.out_ch, N, Sd, Sd, r2.scale, r2.shift, sc.scale, sc.shift, base + B.y2,
-                                       sc.y, part, s, tail_wg_in_reduce ? ps.wscratch : nullptr, store8 ? 1 : 0);
-      if (tail_wg_in_reduce && np > 0) {
+                                       sc.y, part, s, R.tail_wg_in_reduce ? ps.wscratch : nullptr, R.store8 ? 1 : 0);
+      MM_TRY(np);
+      if (R.tail_wg_in_reduce) {
         MM_TRY(side_fork(s));
         MM_TRY(launch_tail_wgrad_finalize(ps.wscratch, np, grads + tail.off, wgrad_stream(s)));
       }
-    } else if (jg)
-      np = launch_bn_bwd_reduce(dt(), base + P.g[cur], nullptr, nullptr, nullptr, base + B.y2, sc.y, npo, B.C, part, s, nullptr, nullptr);
-    else
-      np = launch_bn_bwd_reduce(dt(), base + P.g[cur], nullptr, r2.scale, r2.shift, base + B.y2, sc.y, npo, B.C, part, s, sc.scale, sc.shift);
-    MM_TRY(np);
-    if (B.identity) MM_TRY(bn_backward_coefs(ps, B.b2, np, 2, 0, (double)npo, s));
-    else MM_TRY(bn_backward_coefs_join(ps, B.b2, B.bs, np, (double)npo, s));
-    // The last up-block in one pass (conv_joinbwd.hip): dy2 / dys are produced row by row inside the kernel that consumes them -- both
-    // ConvTranspose2d weight gradients, both data gradients, bn1's backward sums -- and never stored; conv1 (1x1) follows once bn1's
-    // sums are final.
-    if (from_tail && !B.identity && !B.c2.fp8 && !B.cs.fp8 && !B.c1.fp8 && B.Cin == 16 && join_bwd_stream_ok(dt(), cfg.out_ch, B.C, B.Hin, B.Hout)) {
+      MM_TRY(join_backward(ps, B, sc, nullptr, false, nullptr, nullptr, s, np));       // (the sums are there: the coefficients only)
+    } else   // (join-gradient form: no apply pass, the two fused passes below evaluate dy2 / dys from g[cur], y2 / ys and the coefficients)
+      MM_TRY(join_backward(ps, B, sc, base + P.g[cur], jg, jg ? nullptr : base + P.dy2[ds], base + dyso, s));
+    if (B.r.bwd_join_stream) {   // the whole block in one pass (conv_joinbwd.hip); conv1 (1x1) follows once bn1's sums are final
       float* ws2 = reinterpret_cast<float*>(base + P.wscratch2);
       JoinBwdLaunch L;
       L.d_raw = d_raw; L.w_tail = params + tail.off; L.y2 = base + B.y2; L.ys = sc.y;
@@ -1061,7 +1096,7 @@ int Net::decoder_bwd(int N, const float* d_recon, const float* params, float* gr
       L.wd2 = ps.packed(B.c2.packD); L.da1 = base + P.da1; L.part2 = ws2; L.bn_part = part;
       L.xin = xin; L.pxs = xs; L.pxb = xb; L.wds = ps.packed(B.cs.packD); L.gin = base + P.g[cur ^ 1];
       L.parts = ws2 + 1024L * 4096;                        // (at most 1024 blocks, one [16][16][16] partial image per conv each)
-      L.N = N; L.f8in = store8 ? 1 : 0;
+      L.N = N; L.f8in = R.store8 ? 1 : 0;
       const int nb = launch_join_bwd_stream(L, s);
       MM_TRY(nb);
       MM_TRY(reduce_wgrad_parts(ps, B.c2, L.part2, nb, 16, s));
@@ -1072,8 +1107,7 @@ int Net::decoder_bwd(int N, const float* d_recon, const float* params, float* gr
       C1.A = r1.A; C1.B = r1.B; C1.C = r1.C;
       C1.xin = xin; C1.pxs = xs; C1.pxb = xb; C1.w1u = ps.packed(B.c1.packU);
       C1.gin = base + P.g[cur ^ 1]; C1.part = ws2; C1.nrows = (long)N * B.Hin;
-      C1.mask_out = jg_block(i - 1) ? 1 : 0;
-      g_masked = C1.mask_out != 0;
+      C1.mask_out = (i > 0 && dec[i - 1].r.bwd_join_grad) ? 1 : 0;
       const int nb1 = launch_conv1_bwd_stream(C1, s);
       MM_TRY(nb1);
       MM_TRY(reduce_wgrad_parts(ps, B.c1, ws2, nb1, 1, s));   // conv1: Conv2d weight (out = 16, in = Cin): partial images [out][in]
@@ -1081,35 +1115,23 @@ int Net::decoder_bwd(int N, const float* d_recon, const float* params, float* gr
       cur ^= 1;
       continue;
     }
-    if (store8 && i == nd - 1) { set_error("fp8 storage of the last up-block needs join_bwd_stream"); return MMVAE_ERR_UNSUPPORTED; }
-    if (jg) {
-      // (no apply pass: the two fused passes below evaluate dy2 / dys from g[cur], y2 / ys and the coefficients)
-    } else if (from_tail)
+    if (from_tail)
       MM_TRY(launch_tail_join_bwd_apply(dt(), d_raw, params + tail.off, cfg.out_ch, N, Sd, Sd, r2.scale, r2.shift, sc.scale, sc.shift, base + B.y2,
                                         r2.A, r2.B, r2.C, base + P.dy2[ds], sc.y, sc.A, sc.B, sc.C, base + P.dys[ds], s));
-    else
-      MM_TRY(launch_bn_bwd_apply(dt(), base + P.g[cur], nullptr, r2.scale, r2.shift, base + B.y2, r2.A, r2.B, r2.C, base + P.dy2[ds], sc.y, sc.A,
-                                 sc.B, sc.C, base + dyso, npo, B.C, s, sc.scale, sc.shift));
     hipStream_t wsm = wgrad_stream(s);
     MM_TRY(side_fork(s));
-    bool fuse_c2 = false, fuse_cs = false;
+    const bool fuse_c2 = B.r.bwd_fuse_c2, fuse_cs = B.r.bwd_fuse_cs;
     int np_b1 = 0;                       // rows of bn1's backward sums when the fused pass has left them in `part`
     if (B.identity) {
       // conv2 (3x3 Conv2d): wgrad(P = dy2, G = a1 with BN+ReLU prologue); dgrad -> d_a1
       MM_TRY(run_wgrad(ps, B.c2, base + P.dy2[ds], B.Hout, B.Wout, nullptr, nullptr, base + B.y1, B.Hin, B.Win, r1.scale, r1.shift, wsm));
       MM_TRY(run_up(ps, B.c2, base + P.dy2[ds], B.Hout, B.Wout, base + P.da1, B.Hin, B.Win, nullptr, nullptr, 0, nullptr, 0, s));
     } else {
-      // conv2 (ConvT k4 s2): wgrad(P = a1 small side with BN+ReLU prologue, G = dy2 large side); dgrad = strided conv -> d_a1
-      // Where the shape allows (uplayer4 / uplayer5: 16 output channels, 16x16 -> 32x32 or 32x32 -> 64x64, bf16) dgrad and wgrad of a ConvT
-      // are ONE pass over its dy tensor on the caller's stream (wgrad_stream_kernel with DG): dy2 / dys (671 MB each at N = 5120 in
-      // uplayer5) are read once instead of twice.
-      fuse_c2 = !B.c2.fp8 && op_bwd_fusable(dt(), geom(B.c2), N, B.Hin, B.Win, B.Hout, B.Wout);
-      fuse_cs = !B.cs.fp8 && op_bwd_fusable(dt(), geom(B.cs), N, B.Hin, B.Win, B.Hout, B.Wout) && B.C == 16;
+      // conv2 (ConvT k4 s2): wgrad(P = a1 small side with BN+ReLU prologue, G = dy2 large side); dgrad = strided conv -> d_a1; fused: ONE pass over dy
       float* wsc2 = reinterpret_cast<float*>(base + P.wscratch2);
       if (!fuse_c2)
         MM_TRY(run_wgrad(ps, B.c2, base + B.y1, B.Hin, B.Win, r1.scale, r1.shift, base + P.dy2[ds], B.Hout, B.Wout, nullptr, nullptr, wsm));
       if (!fuse_cs) MM_TRY(run_wgrad(ps, B.cs, xin, B.Hin, B.Win, xs, xb, base + P.dys[ds], B.Hout, B.Wout, nullptr, nullptr, wsm));
-      if (jg && !(fuse_c2 && fuse_cs)) { set_error("decoder_bwd: the join-gradient form needs both fused passes"); return MMVAE_ERR_UNSUPPORTED; }
       if (fuse_c2) {
         // ... and bn1's backward sums come out of the same pass (the data gradient is in registers, y1 is the pass's P operand)
         const JoinGrad j2{base + B.y2, r2.A, r2.B, r2.C};
@@ -1121,11 +1143,7 @@ int Net::decoder_bwd(int N, const float* d_recon, const float* params, float* gr
       } else
         MM_TRY(run_down(ps, B.c2, base + P.dy2[ds], B.Hout, B.Wout, base + P.da1, B.Hin, B.Win, nullptr, nullptr, 0, nullptr, 0, dt(), s));
     }
-    np = np_b1 > 0 ? np_b1 : launch_bn_bwd_reduce(dt(), base + P.da1, nullptr, r1.scale, r1.shift, base + B.y1, nullptr, npi, B.C, part, s);
-    MM_TRY(np);
-    MM_TRY(bn_backward_coefs(ps, B.b1, np, 1, 0, (double)npi, s));
-    MM_TRY(launch_bn_bwd_apply(dt(), base + P.da1, nullptr, r1.scale, r1.shift, base + B.y1, r1.A, r1.B, r1.C, base + P.dy1[ds], nullptr, nullptr,
-                               nullptr, nullptr, nullptr, npi, B.C, s));
+    MM_TRY(bn_relu_backward(ps, B.b1, base + P.da1, base + B.y1, base + P.dy1[ds], npi, s, np_b1));
     // conv1 (1x1): wgrad(P = dy1, G = xin); upsample (ConvT): wgrad(P = xin, G = dys)
     MM_TRY(side_fork(s));
     // (with the fused shortcut pass below the 1x1 conv's weight gradient comes out of that pass: dy1 and the block input are its rows)
@@ -1146,22 +1164,14 @@ int Net::decoder_bwd(int N, const float* d_recon, const float* params, float* gr
   }
   // ---- decoder stem
   if (dec.size() >= 2) MM_TRY(side_wait_mark(1, s));   // the stem uses dy set 1 (block index -1)
-  const int ds = 1;
-  {
-    const long npix = (long)N * 4;
-    np = launch_bn_bwd_reduce(dt(), base + P.g[cur], nullptr, r0.scale, r0.shift, base + P.y0d, nullptr, npix, 128, part, s);
-    MM_TRY(np);
-    MM_TRY(bn_backward_coefs(ps, dbn0, np, 1, 0, (double)npix, s));
-    MM_TRY(launch_bn_bwd_apply(dt(), base + P.g[cur], nullptr, r0.scale, r0.shift, base + P.y0d, r0.A, r0.B, r0.C, base + P.dy1[ds], nullptr,
-                               nullptr, nullptr, nullptr, nullptr, npix, 128, s));
-    MM_TRY(side_fork(s));
-    MM_TRY(run_wgrad(ps, dstem, base + P.enc_t, 1, 1, nullptr, nullptr, base + P.dy1[ds], 2, 2, nullptr, nullptr, wgrad_stream(s)));
-    if (d_enc) {
-      MM_TRY(run_down(ps, dstem, base + P.dy1[ds], 2, 2, base + P.dh, 1, 1, nullptr, nullptr, 0, nullptr, 0, dt(), s));
-      MM_TRY(launch_convert(dt(), DT_F32, base + P.dh, d_enc, (long)N * cfg.z, s));
-    }
-    if (!defer_join_) MM_TRY(side_join(s));
+  MM_TRY(bn_relu_backward(ps, dbn0, base + P.g[cur], base + P.y0d, base + P.dy1[1], (long)N * 4, s));
+  MM_TRY(side_fork(s));
+  MM_TRY(run_wgrad(ps, dstem, base + P.enc_t, 1, 1, nullptr, nullptr, base + P.dy1[1], 2, 2, nullptr, nullptr, wgrad_stream(s)));
+  if (d_enc) {
+    MM_TRY(run_down(ps, dstem, base + P.dy1[1], 2, 2, base + P.dh, 1, 1, nullptr, nullptr, 0, nullptr, 0, dt(), s));
+    MM_TRY(launch_convert(dt(), DT_F32, base + P.dh, d_enc, (long)N * cfg.z, s));
   }
+  if (!defer_join_) MM_TRY(side_join(s));
   return MMVAE_OK;
 }
 

@@ -4,6 +4,8 @@
 // the activation workspace are caller-provided device pointers.
 // Each entry point binds those pointers once into a Net::Pass; the helpers take the Pass and the call sites name only what varies
 // (layer, operands, stream).  BatchNorm scratch rows and packed weights are reached by name: Pass::rows(), Pass::shortcut(), Pass::packed().
+// Which kernel takes each launch is settled with the plan: Net::settle_routes(N) fills a BlockRoute per block and a NetRoute for the boundary layers and
+// checks that forward and backward fit each other; the entry points only read the fields (ANDed with what depends on the run: side stream, training, d_enc).
 #pragma once
 #include <string>
 #include <vector>
@@ -38,6 +40,21 @@ struct Bn {
 };
 struct BnRows { float *mean, *istd, *scale, *shift, *A, *B, *C; };   // device pointers to a Bn's scratch rows
 
+// The kernel routes of one block at the plan's batch size; Net::settle_routes says what each one is.
+struct BlockRoute {
+  bool fwd_c1_cs_stream = false, fwd_c2_stream = false, bwd_pair_wgrad = false, bwd_c2_late_reduce = false, bwd_c2_dgrad_stream = false;   // encoder
+  bool fwd_cs_stream = false, fwd_stats_only = false, fwd_join_conv1 = false;                                               // decoder (+ fwd_c2_stream)
+  bool bwd_join_grad = false, bwd_join_stream = false, bwd_fuse_c2 = false, bwd_fuse_cs = false;
+};
+// ... and of the boundary layers.  tail_fwd, the last up-block's join + tail conv: GATHER = join, then the generic conv; JOIN / STREAM / UP5 = one kernel
+// (tail_join_fwd / tail_fwd_stream / up5_tail_fwd) that never stores the joined activation.  refused: the rule of settle_routes the routes break, or null.
+enum TailFwd : int { TAIL_GATHER, TAIL_JOIN, TAIL_STREAM, TAIL_UP5 };
+struct NetRoute {
+  bool stem_fwd_stream = false, stem_bwd_fused = false, stem_dg_fused = false, tail_bwd_fused = false, tail_wg_in_reduce = false, store8 = false;
+  TailFwd tail_fwd = TAIL_GATHER;
+  const char* refused = nullptr;
+};
+
 struct Block {   // encoder BasicBlock or decoder DeconvBottleneck (both: main c1->c2, shortcut cs, join)
   ConvW c1, c2, cs; Bn b1, b2, bs;
   int Cin, C, Hin, Win, Hmid, Wmid, Hout, Wout;
@@ -45,6 +62,7 @@ struct Block {   // encoder BasicBlock or decoder DeconvBottleneck (both: main c
   // identity: a shape-preserving block of a deeper-than-reference net (blocks > 1): no shortcut conv / BatchNorm, the shortcut is
   // the block input itself (model.py:39-55 with downsample=None; decoder: conv2 is a 3x3 Conv2d instead of the ConvTranspose2d)
   bool identity = false;
+  BlockRoute r;
 };
 
 struct Plan {
@@ -65,6 +83,7 @@ struct Plan {
   long cvec;                                             // constants: 256 ones, 256 zeros (identity shortcuts as a unit BatchNorm)
   long act0d;                                            // blocks > 1: relu(bn(decoder stem)) materialised (an identity shortcut needs it)
   long enc_ws_end;
+  NetRoute route;
 };
 
 constexpr long kPartialFloats = 4096L * 3 * 256;   // floats of one reduction-partials region
@@ -94,6 +113,9 @@ class Net {
 
   size_t workspace_bytes(int N);
   const Plan& plan(int N);
+  // the settled routes of batch size N as text, one line per block and one for the boundary layers (`name: field=value ...`); the settling
+  // error when they are refused.  Host only: enqueues nothing.
+  int describe_routes(int N, std::string& out);
 
   // staged: the storage-type copy of x is already in the workspace (stage_labels wrote it together with x): no conversion pass
   int encoder_fwd(int N, const float* x, const float* params, float* bnbuf, long long* nbt, void* ws, size_t ws_bytes,
@@ -158,6 +180,7 @@ class Net {
   size_t esz() const { return dtype_size(cfg.dtype); }
   ConvW add_conv(const std::string& name, int D0, int D1, int k, int s, int p, bool pack, bool transposed = false);
   void settle_layout(ConvW& w) const;
+  void settle_routes(int N, NetRoute& R);       // called by plan(N): every block's BlockRoute, R, and the rules between them
   Bn add_bn(const std::string& prefix, int C);
   void add_entry(const std::string& name, std::initializer_list<int> shape, int kind, long off);
 
@@ -178,11 +201,6 @@ class Net {
                 const void* G, int Hl, int Wl, const float* proG_s, const float* proG_b, hipStream_t s);
   // sum of the partial images [D0][D1][ntaps] a fused backward pass left at `parts` -> w's weight gradient
   int reduce_wgrad_parts(const Pass& ps, const ConvW& w, const float* parts, int nparts, int ntaps, hipStream_t s);
-  // Last up-block forward as one kernel (join + tail conv, the joined activation is never stored); the backward then needs the
-  // recomputing wgrad and the recomputing join backward.  Shapes it does not take keep join -> conv.
-  bool tail_fwd_fused() const;
-  bool stem_bwd_fused() const;       // stem backward as one pass (stem_bwd.hip)
-  bool stem_dg_fused() const;        // ... with encoder.layer1's data gradient recomputed inside it (no stored gradient of the stem's output)
   // decoder_bwd leaves its weight gradients running on the side stream; encoder_bwd (or join()) orders them before the caller's stream
   bool defer_join_ = false;
   int (*ar_fn_)(float*, long long, void*, void*) = nullptr; void* ar_user_ = nullptr; int ar_world_ = 1;
@@ -193,7 +211,7 @@ class Net {
   // the join-gradient form of a 16-wide block's backward (decoder_bwd: masked gradient handed down, dy evaluated by the consumers' loaders);
   // off = the reduce -> apply -> consumers form every other block uses (kept reachable for the A/B parity test)
   bool join_grad_ = true;
-  void set_join_grad(bool v) { join_grad_ = v; }
+  void set_join_grad(bool v) { join_grad_ = v; plan_.N = -1; }      // (the routes are settled again)
   // SyncBN: fn sums a device f32 buffer over all ranks, ordered on the given stream; NULL = per-rank statistics
   typedef int (*AllReduceFn)(float* buf, long long n, void* stream, void* user);
   void set_sync_bn(AllReduceFn fn, void* user, int world) { ar_fn_ = fn; ar_user_ = user; ar_world_ = fn ? world : 1; comm_ = comm_side_ = nullptr; }
@@ -210,14 +228,19 @@ class Net {
   int bn_fwd(const Pass& ps, const Bn& bn, int nparts, double count, hipStream_t s, long part_off = 0, float in_scale = 1.f);
   // eval mode: all BatchNorms of the encoder (which = 0) / decoder (1) folded to (scale, shift) in one launch
   int fold_bn_eval(const Pass& ps, int which, hipStream_t s);
-  bool l1_dgrad_stream() const;
-  long l1c2_flip = 0;
-  bool eval_folded_ = false;
-  bool store8 = false;          // fp8 mode: the last up-block's branch outputs are stored as e4m3 bytes (see the constructor)
+  long l1c2_flip = 0; bool eval_folded_ = false;
+  bool store8 = false;          // fp8 mode: the last up-block's branch outputs are stored as e4m3 bytes (the constructor's guess; settle_routes confirms it)
   int fill_consts(const Pass& ps, hipStream_t s);
   int bn_backward_coefs(const Pass& ps, const Bn& bn, int nparts, int ny, int which, double count, hipStream_t s, float* dbias_conv = nullptr);
   BnBwdFinalizeArgs bwd_finalize_args(const Pass& ps, const Bn& bn, const float* partials, int nparts, int ny, int which, double count) const;
   int bn_backward_coefs_join(const Pass& ps, const Bn& b2, const Bn& bs, int nparts, double count, hipStream_t s);
+  // BatchNorm + ReLU backward of g (the gradient behind relu(bn(y))) into dy: reduce -> coefficients -> apply; nparts_ready > 0: a fused pass
+  // has already left that many rows of sums in ps.part, no reduce launch
+  int bn_relu_backward(const Pass& ps, const Bn& bn, const void* g, const void* y, void* dy, long npix, hipStream_t s, int nparts_ready = 0);
+  // Head of a residual block's backward: g, the join's output gradient, feeds bn2 (y2) and the shortcut's BatchNorm (sc): reduce -> both coefficient sets ->
+  // apply into dy2 / dys.  g_masked: g already carries the join's ReLU mask (plain sums); nparts_ready as above; dy2 == nullptr: no apply launch.
+  int join_backward(const Pass& ps, const Block& B, const Shortcut& sc, const void* g, bool g_masked, void* dy2, void* dys, hipStream_t s,
+                    int nparts_ready = 0);
 };
 
 }  // namespace mmvae
