@@ -359,6 +359,27 @@ typedef struct mmvae_panel_col {
  * 1 <= S <= 64.  Every byte of out is written exactly once, none outside it; no atomics: the same bytes every run. */
 MMVAE_API int mmvae_panel_sheet(const mmvae_panel_col* cols, int ncols, int n, int S, uint8_t* out, void* stream);
 
+/* ------------------------------------------------------------------ per-frame quality: squared error and SSIM of two columns
+ * n pairs of S x S planes, 11 <= S <= 64 (else MMVAE_ERR_UNSUPPORTED), one launch.  a and b: one HOST descriptor each, copied into the
+ * launch; each side is reduced to bytes by the column rule above (the bytes mmvae_panel_sheet would write for it), or is bytes already:
+ *   MMVAE_FRAME_BYTES_U8 [n][S*S] uint8, taken as is; the other fields of the descriptor are ignored.  This kind is accepted here only:
+ *   mmvae_panel_sheet refuses it.
+ * Per plane pair p, with a and b the two byte planes as exact values:
+ *   out[p]     = sse  = sum over the S*S pixels of (a - b)^2, an integer <= 4096 * 65025, exact in f64;
+ *   out[n + p] = ssim = the mean over the (S - 10)^2 positions whose 11 x 11 window lies inside the plane of
+ *                  ((2 mu_a mu_b + C1) (2 s_ab + C2)) / ((mu_a^2 + mu_b^2 + C1) (s_a^2 + s_b^2 + C2)),
+ *     mu_a = E[a], mu_b = E[b], s_a^2 = E[a^2] - mu_a^2, s_b^2 = E[b^2] - mu_b^2, s_ab = E[a b] - mu_a mu_b, every E[.] the sum under
+ *     the window w = g g^T, g[k] = exp(-(k - 5)^2 / (2 * 1.5^2)) / sum_k (k = 0..10), C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2.
+ *   This is Wang et al. 2004 on 8-bit data; it is what skimage.metrics.structural_similarity(gaussian_weights=True,
+ *   use_sample_covariance=False, data_range=255) returns, whose border crop leaves the same positions.
+ * All arithmetic is f64 (window sums, map, mean; g is computed once on the host in double); mse = sse / S^2 and
+ * psnr = 10 log10(65025 / mse) are the caller's.  out: f64 [2][n]; nothing outside it is written.  No atomics, no allocation, no host
+ * read: capturable, and the same bits every run.
+ * MMVAE_ERR_ARG, nothing enqueued: NULL a, b, out or source, n < 1, an unknown kind, a class kind without lut (or _SAMPLE without
+ * uniforms) or with Q outside 1..16, IMAGE_F32 without hi > lo. */
+#define MMVAE_FRAME_BYTES_U8 5
+MMVAE_API int mmvae_frame_quality(const mmvae_panel_col* a, const mmvae_panel_col* b, int n, int S, double* out, void* stream);
+
 /* ------------------------------------------------------------------ latent diagnostics (scatter_plot, main.py:166-183)
  * Density panel of n 2-D points, the picture behind the reference's scatter plot of q(z|x) against p(z): point p is
  * (pts[p*stride + col_x], pts[p*stride + col_y]) (an (N, z, 1, 1) encoding in place: stride = z; the reference plots dimensions 0, 1).

@@ -77,6 +77,7 @@ PROTOTYPES = {
     "mmvae_generate_clips": (c_int, [P, c_int64, c_int, P, c_uint64, c_int64, c_int64, c_int, c_int, c_int, P, c_int, c_float, c_float, P, P, P, P]),
     "mmvae_logits_to_labels": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P]),
     "mmvae_panel_sheet": (c_int, [P, c_int, c_int, c_int, P, P]),
+    "mmvae_frame_quality": (c_int, [P, P, c_int, c_int, P, P]),
     "mmvae_scatter_panel": (c_int, [P, c_int64, c_int, c_int, c_int, P, c_int, c_int, P, P, c_int64, P]),
     "mmvae_latent_stats": (c_int, [P, P, P, c_int, c_int, c_int, P, P]),
     "mmvae_nearest_frames_scratch_bytes": (c_size_t, [c_int, c_int64, c_int, c_int]),
@@ -134,6 +135,7 @@ class MmvaeError(RuntimeError):
 PICK_ARGMAX, PICK_SAMPLE = 0, 1                                  # MMVAE_PICK_*
 PANEL_LABELS_U8, PANEL_LABELS_I64, PANEL_LOGITS_ARGMAX, PANEL_LOGITS_SAMPLE, PANEL_IMAGE_F32 = range(5)      # MMVAE_PANEL_*
 PANEL_MAX_COLS, PANEL_MAX_Q, PANEL_MAX_S = 8, 16, 64
+FRAME_BYTES_U8, FRAME_MIN_S, FRAME_MAX_S = 5, 11, 64             # MMVAE_FRAME_BYTES_U8; the sides mmvae_frame_quality accepts
 SCATTER_MAX_SIDE, SCATTER_MIN_RADIUS16, SCATTER_MAX_RADIUS16 = 512, 12, 128      # mmvae_scatter_panel's accepted ranges
 LATENT_STATS_ROWS, LATENT_STATS_MAX_D = 6, 512                                   # mmvae_latent_stats: rows of acc, widest latent
 NEAREST_MAX_M, NEAREST_MAX_K, NEAREST_MAX_D = 64, 8, 16384                       # mmvae_nearest_frames: queries, neighbours, bytes per plane

@@ -358,6 +358,9 @@ int mmvae_logits_to_labels(const float* logits, int N, int Q, int HW, int mode, 
 int mmvae_panel_sheet(const mmvae_panel_col* cols, int ncols, int n, int S, uint8_t* out, void* st) {
   return launch_panel_sheet(cols, ncols, n, S, out, stream_of(st));
 }
+int mmvae_frame_quality(const mmvae_panel_col* a, const mmvae_panel_col* b, int n, int S, double* out, void* st) {
+  return launch_frame_quality(a, b, n, S, out, stream_of(st));
+}
 // ---- latent diagnostics (arguments are checked in the launchers)
 int mmvae_scatter_panel(const float* pts, int64_t n, int stride, int col_x, int col_y, const float* xform, int side, int radius16,
                         const uint8_t* tone, uint8_t* out, int64_t out_row_stride, void* st) {

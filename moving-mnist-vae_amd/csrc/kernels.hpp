@@ -427,6 +427,9 @@ int launch_generate_clips(const unsigned char* bank, long D, int G, const int* v
 // [n * S][ncols * S] from ncols column descriptors (host array, passed to the kernel by value)
 int launch_logits_to_labels(const float* logits, int N, int Q, int HW, int mode, const float* uniforms, long long* labels, hipStream_t s);
 int launch_panel_sheet(const mmvae_panel_col* cols, int ncols, int n, int S, unsigned char* out, hipStream_t s);
+// per-frame quality (frame_quality.hip): out f64 [2][n] = squared error and SSIM (11 x 11 Gaussian window, valid positions) of n pairs of
+// S x S planes, each side one column descriptor reduced to bytes by the sheet's rule (or MMVAE_FRAME_BYTES_U8); 11 <= S <= 64
+int launch_frame_quality(const mmvae_panel_col* a, const mmvae_panel_col* b, int n, int S, double* out, hipStream_t s);
 // latent diagnostics (latent_diag.hip): the density panel of n 2-D points pts[p * stride + col_x / col_y] (xform: device {xlim, ylim, sx, sy};
 // byte = tone[min(#covering discs, 255)], out rows out_row_stride bytes apart), and acc[6][d] f64 per-dimension sums over N images of
 // mu, mu^2, the KL term, exp(logvar), enc, enc^2 (logvar / enc nullable: their rows are zero; accumulate: add to acc instead of writing).

@@ -2,15 +2,8 @@
 // class labels or the bytes of an 8-bit greyscale contact sheet out.  The host side (main.py: render_sheet, plot_*) only describes the
 // columns; no softmax / argmax / cat / indexing chain in ATen, no f32 tensor crosses to the host.
 //
-// Pick rule.  pick_label() is the one device function that turns the Q logits of a pixel into a label; both kernels call it.
-//   argmax: strict `>` scan from index 0 against a running maximum that starts at -inf: the lowest index among equal maxima, a NaN never
-//           wins, an all-NaN (or all -inf) pixel gives 0.
-//   sample: f32 softmax (maximum subtracted, expf, sum in channel order), p_k = e_k / sum, then label = #{k in [0, Q-2] : cdf_k <= u} with
-//           cdf accumulated in channel order -- the rule of model.draw_labels and of pixel_head_kernel (pixelcnn.hip).  That kernel keeps
-//           its own loop: it sums the exponentials by a lane butterfly, another order of additions than this serial sum, so folding the two
-//           together would change its bits.
-// One thread per pixel; logits are planar [N][Q][HW], so a thread's Q loads are HW apart and neighbouring lanes read neighbouring
-// addresses.  The logits stay in registers (the loops over 16 are fully unrolled and predicated on k < Q); no LDS.
+// Pick rule and byte rule.  panel_decode.hpp holds them (pick_label(), panel_byte()): the quality kernel (frame_quality.hip) reduces its
+// two sides to bytes through the same functions.  One thread per pixel.
 //
 // Sheet.  out is uint8 [n * S][ncols * S]; column c holds its n planes stacked vertically in bytes [:, c*S : (c+1)*S].  The grid is
 // (pixels of one column, column): the column descriptor, a kernel argument passed by value, is indexed by blockIdx.y only, so it is read
@@ -20,40 +13,14 @@
 // every lane stores its own byte.
 #include "common.hpp"
 #include "kernels.hpp"
+#include "panel_decode.hpp"
 
 namespace mmvae {
 
 namespace {
 
-constexpr int kMaxQ = 16;
+constexpr int kMaxQ = kPanelMaxQ;
 constexpr int kThreads = 256;
-
-__device__ __forceinline__ int pick_label(const float* __restrict__ p, long stride, int Q, bool sample, float u) {
-  float l[kMaxQ];
-#pragma unroll
-  for (int k = 0; k < kMaxQ; ++k) l[k] = k < Q ? p[k * stride] : -INFINITY;
-  float mx = -INFINITY;
-  int best = 0;
-#pragma unroll
-  for (int k = 0; k < kMaxQ; ++k)
-    if (k < Q && l[k] > mx) { mx = l[k]; best = k; }
-  if (!sample) return best;
-  float sum = 0.f;
-#pragma unroll
-  for (int k = 0; k < kMaxQ; ++k) {
-    l[k] = k < Q ? expf(l[k] - mx) : 0.f;
-    sum += l[k];
-  }
-  float cdf = 0.f;
-  int label = 0;
-#pragma unroll
-  for (int k = 0; k < kMaxQ - 1; ++k)
-    if (k < Q - 1) {                                                 // inverse CDF: label = #{k <= Q - 2 : cdf_k <= u}
-      cdf += l[k] / sum;
-      label += cdf <= u;
-    }
-  return label;
-}
 
 __global__ __launch_bounds__(kThreads) void logits_to_labels_kernel(const float* __restrict__ logits, long npix, int Q, int HW, int sample,
                                                                    const float* __restrict__ uniforms, long long* __restrict__ labels) {
@@ -64,10 +31,6 @@ __global__ __launch_bounds__(kThreads) void logits_to_labels_kernel(const float*
 }
 
 struct PanelCols { mmvae_panel_col c[MMVAE_PANEL_MAX_COLS]; };
-
-__device__ __forceinline__ unsigned lut_byte(const unsigned char* __restrict__ lut, long long label, int Q) {
-  return (unsigned long long)label < (unsigned long long)Q ? lut[label] : 0u;
-}
 
 __global__ __launch_bounds__(kThreads) void panel_sheet_kernel(PanelCols cols, int ncols, long n, int S, int Sp,
                                                               unsigned char* __restrict__ out) {
@@ -81,28 +44,7 @@ __global__ __launch_bounds__(kThreads) void panel_sheet_kernel(PanelCols cols, i
     const int HW = S * S;
     const long r = row / S;
     const int pix = (int)(row - r * S) * S + x;
-    const long at = r * HW + pix;                                    // index into a [n][S*S] tensor
-    switch (col.kind) {
-      case MMVAE_PANEL_LABELS_U8:
-        byte = lut_byte(col.lut, static_cast<const unsigned char*>(col.src)[at], col.Q);
-        break;
-      case MMVAE_PANEL_LABELS_I64:
-        byte = lut_byte(col.lut, static_cast<const long long*>(col.src)[at], col.Q);
-        break;
-      case MMVAE_PANEL_LOGITS_ARGMAX:
-        byte = col.lut[pick_label(static_cast<const float*>(col.src) + r * col.Q * HW + pix, HW, col.Q, false, 0.f)];
-        break;
-      case MMVAE_PANEL_LOGITS_SAMPLE:
-        byte = col.lut[pick_label(static_cast<const float*>(col.src) + r * col.Q * HW + pix, HW, col.Q, true, col.uniforms[at])];
-        break;
-      default: {                                                     // MMVAE_PANEL_IMAGE_F32; explicit roundings: no contraction
-        const float v = static_cast<const float*>(col.src)[at];
-        const float t = __fmul_rn(__fdiv_rn(__fsub_rn(v, col.lo), __fsub_rn(col.hi, col.lo)), 255.f);
-        float b = floorf(__fadd_rn(t, 0.5f));
-        b = b > 0.f ? b : 0.f;                                       // NaN -> 0
-        byte = (unsigned)(b < 255.f ? b : 255.f);
-      }
-    }
+    byte = panel_byte(col, r, pix, HW);
   }
   // the four lanes [q, q + 4) hold pixels x0 .. x0 + 3 of one sheet row (Sp and the block size are multiples of 4); every lane of the
   // wave takes part in the shuffles

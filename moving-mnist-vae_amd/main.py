@@ -3,7 +3,8 @@
 Mirrors the loop body of the reference ``main.py:362-429`` (normalise ->
 forward -> loss -> bookkeeping -> zero_grad / backward / step) so that a user
 of the reference can swap ``from main import train`` for this one.  Around the
-loop: held-out evaluation (``evaluate``, ``latent_stats``), the model-name
+loop: held-out evaluation (``evaluate``, ``latent_stats``; the per-frame MSE /
+PSNR / SSIM behind ``evaluate(quality=True)`` live in ``quality.py``), the model-name
 grammar (``select_model``), the reference's samplers (``generate*``) and its
 checkpoint format.  The plotting branch (``main.py:401-424``) hangs off
 ``args.plot_callback``: ``make_plot_callback`` in ``panels.py`` returns one, and
@@ -37,6 +38,7 @@ from .model import VAE
 from .monitor import TensorHistograms, make_histogram_callback, tensor_histograms  # noqa: F401
 from .panels import (column, gray_lut, latent_slide, make_plot_callback, neighbour_sheet, plot_neighbours, plot_pixelcnn, plot_pixelvae,  # noqa: F401
                      plot_vae, render_sheet, sample_from_reconstruction, scatter_panel, scatter_plot, scatter_tone, write_png_gray)
+from .quality import frame_quality, reconstruction_quality  # noqa: F401
 
 
 def prepare_batch(model, batch, device, args, data_mean, data_std):
@@ -110,7 +112,7 @@ def train(model, data_loader, optimizer, device, args, epoch=0, data_mean=0, dat
 
 
 def evaluate(model, data_loader, device, args, data_mean=0, data_std=1, iw_samples=0, weighted=False, generator=None,
-             return_per_image=False, latent_stats=False) -> dict:
+             return_per_image=False, latent_stats=False, quality=False, centres=None) -> dict:
     """Held-out evaluation of the HIP model (the reference builds a test loader, main.py:497, and never reads it): one eval-mode pass
     over ``data_loader`` under ``torch.no_grad()``; the model's train / eval mode is restored afterwards and no parameter or buffer
     changes.  Batches are prepared as in ``train``.  Per-image terms come from ``model.per_image_terms`` (and ``model.iw_bound``
@@ -129,16 +131,22 @@ def evaluate(model, data_loader, device, args, data_mean=0, data_std=1, iw_sampl
     ``z_var`` (of the sampled codes: the aggregate posterior's moments).  Without a logvar ``kl_per_dim`` and ``mean_posterior_var`` are
     None; a PixelCNN on its own has ``latent`` None.  Under this flag ``kl`` (and ``elbo``) are taken from the same accumulator, whose
     terms are formed in f64: ``sum(kl_per_dim) == kl`` up to f64 summation order, and ``kl`` moves by the f32 rounding of the
-    per-image kernel's terms (a few 1e-8 relative) against the value without the flag."""
+    per-image kernel's terms (a few 1e-8 relative) against the value without the flag.
+    ``quality=True`` adds ``quality``: {'mse', 'psnr', 'ssim'} of the reconstruction against the input as 8-bit pictures
+    (``reconstruction_quality`` on every batch, ``centres`` the k-means centres of its grey table): ``mse`` and ``ssim`` are means per
+    image, ``psnr = 10 log10(65025 / mean mse)``.  The sums join the f64 device sums above and come back in the same single copy;
+    ``per_image`` gains 'mse' and 'ssim'.  Needs 11 <= input_image_size <= 64.  Without the flag nothing changes, keys or bits."""
     if not hasattr(model, "per_image_terms"):
         raise TypeError("evaluate() drives the HIP VAE of this package (it needs model.per_image_terms)")
     latent = not model.only_pixelcnn
     categorical = VAE.is_categorical(model)
     weight = getattr(args, "data_ratio_of_labels", None) if (weighted and categorical) else None
     was_training = bool(model.training)
-    sums = None                                    # f64 device: nll, kl, iw
+    sums = None                                    # f64 device: nll, kl, iw (, mse, ssim with `quality`)
     want_latent, acc = bool(latent_stats) and latent, None      # acc: f64 device [6][z], see latent_stats()
     kept = {"nll": [], "kl": [], "iw_bound": []}
+    if quality:
+        kept.update(mse=[], ssim=[])
     n_images = 0
     model.eval()
     try:
@@ -161,12 +169,16 @@ def evaluate(model, data_loader, device, args, data_mean=0, data_std=1, iw_sampl
                     acc, have_lv = _latent_stats_into(model, mu, logvar, encoding, acc), logvar is not None
                 iw = model.iw_bound(image, target, iw_samples, generator=generator, weight=weight) if iw_samples else None
                 if sums is None:
-                    sums = torch.zeros(3, dtype=torch.float64, device=nll.device)
+                    sums = torch.zeros(5 if quality else 3, dtype=torch.float64, device=nll.device)
                 sums[0] += nll.sum()
                 if kl is not None:
                     sums[1] += kl.sum()
                 if iw is not None:
                     sums[2] += iw.sum()
+                if quality:
+                    q = reconstruction_quality(model, image, reconstruction, data_mean, data_std, centres)
+                    sums[3] += q["mse"].sum()
+                    sums[4] += q["ssim"].sum()
                 n_images += N
                 if return_per_image:
                     kept["nll"].append(nll)
@@ -174,11 +186,14 @@ def evaluate(model, data_loader, device, args, data_mean=0, data_std=1, iw_sampl
                         kept["kl"].append(kl)
                     if iw is not None:
                         kept["iw_bound"].append(iw)
+                    if quality:
+                        kept["mse"].append(q["mse"])
+                        kept["ssim"].append(q["ssim"])
     finally:
         model.train(was_training)
     if n_images == 0:
         raise ValueError("evaluate(): the data loader yielded no batch")
-    s_nll, s_kl, s_iw = (v / n_images for v in sums.tolist())                           # the one device -> host copy
+    s_nll, s_kl, s_iw, *s_quality = (v / n_images for v in sums.tolist())               # the one device -> host copy
     latent_out = None
     if want_latent:
         a = acc.cpu().numpy()                                                           # ... and the accumulator's
@@ -192,6 +207,9 @@ def evaluate(model, data_loader, device, args, data_mean=0, data_std=1, iw_sampl
     dims = model.in_channels * model.input_image_size ** 2
     out = {"n_images": n_images, "nll": s_nll, "kl": s_kl if latent else None, "elbo": -(s_nll + s_kl) if latent else None,
            "iw_bound": s_iw if iw_samples else None, "bits_per_dim": s_nll / (dims * float(np.log(2.0))) if categorical else None}
+    if quality:
+        s_mse, s_ssim = s_quality
+        out["quality"] = {"mse": s_mse, "psnr": float("inf") if s_mse == 0.0 else 10.0 * float(np.log10(65025.0 / s_mse)), "ssim": s_ssim}
     if return_per_image:
         out["per_image"] = {k: (torch.cat(v) if v else None) for k, v in kept.items()}
     if latent_stats:
