@@ -554,21 +554,22 @@ int mmvae_batchnorm_fwd(int dt, const void* y, int64_t npix, int C, const float*
   f.nbt = reinterpret_cast<long long*>(nbt); f.mean = save_mean; f.istd = save_istd; f.scale = coef; f.shift = coef + C; f.momentum = momentum; f.eps = eps;
   int rc = launch_bn_finalize(f, stream_of(st));
   if (rc < 0) return rc;
-  return launch_affine_act(dt, y, coef, coef + C, relu, out, npix, C, stream_of(st));
+  return launch_affine_act(dt, BnSide{y, {coef, coef + C}}, relu, out, npix, C, stream_of(st));
 }
 int mmvae_batchnorm_bwd(int dt, const void* dout, const void* y, const void* out, int64_t npix, int C, const float* gamma, const float* save_mean,
                         const float* save_istd, void* dy, float* dgamma, float* dbeta, void* scratch, void* st) {
   if (!scratch || C < 1 || C > 512 || npix < 1) { set_error("batchnorm_bwd: bad arguments (C <= 512, scratch required)"); return MMVAE_ERR_ARG; }
   float* part = static_cast<float*>(scratch);
   float* coef = part + 1024L * 3 * 512;              // A, B, C
-  const int np = launch_bn_bwd_reduce(dt, dout, out, nullptr, nullptr, y, nullptr, npix, C, part, stream_of(st));
+  const BnSide side{y, {}, {coef, coef + C, coef + 2 * C}};
+  const int np = launch_bn_bwd_reduce(dt, dout, out, side, BnSide{}, part, npix, C, stream_of(st));
   if (np < 0) return np;
   BnBwdFinalizeArgs f; std::memset(&f, 0, sizeof(f));
   f.partials = part; f.nparts = np; f.C = C; f.which = 0; f.ny = 1; f.count = (double)npix; f.gamma = gamma; f.mean = save_mean; f.istd = save_istd;
   f.dgamma = dgamma; f.dbeta = dbeta; f.coefA = coef; f.coefB = coef + C; f.coefC = coef + 2 * C;
   int rc = launch_bn_bwd_finalize(f, stream_of(st));
   if (rc < 0) return rc;
-  return launch_bn_bwd_apply(dt, dout, out, nullptr, nullptr, y, coef, coef + C, coef + 2 * C, dy, nullptr, nullptr, nullptr, nullptr, nullptr, npix, C, stream_of(st));
+  return launch_bn_bwd_apply(dt, dout, out, side, BnSide{}, dy, nullptr, npix, C, stream_of(st));
 }
 static_assert(MMVAE_STEM_SCRATCH_BYTES >= 32 * 25 * 16, "stem scratch: 32 columns x 25 taps x one 16-byte vector of padded input channels");
 int mmvae_stem_fwd(int dt, const void* x, const float* w, void* y, int N, int Sz, float* stats, void* scratch, void* st) {
@@ -610,21 +611,21 @@ int mmvae_stem_bwd(int dt, const void* g, const void* y0, const void* x, const f
 }
 int mmvae_tail_join_fwd(int dt, const void* y2, const float* s2, const float* b2, const void* ys, const float* ss, const float* bs,
                         const float* w, const float* bias, float* r_raw, float* stats, int N, int H, int W, void* st) {
-  return launch_tail_join_fwd(dt, y2, s2, b2, ys, ss, bs, w, bias, r_raw, stats, N, H, W, stream_of(st));
+  return launch_tail_join_fwd(dt, BnSide{y2, {s2, b2}}, BnSide{ys, {ss, bs}}, w, bias, r_raw, stats, N, H, W, stream_of(st));
 }
 int mmvae_tail_join_fwd_stream(int dt, const void* y2, const float* s2, const float* b2, const void* ys, const float* ss, const float* bs,
                                const float* w, const float* bias, float* r_raw, float* stats, int N, int H, int W, void* st) {
-  return launch_tail_fwd_stream(dt, y2, s2, b2, ys, ss, bs, w, bias, r_raw, stats, N, H, W, stream_of(st));
+  return launch_tail_fwd_stream(dt, BnSide{y2, {s2, b2}}, BnSide{ys, {ss, bs}}, w, bias, r_raw, stats, N, H, W, stream_of(st));
 }
 int mmvae_tail_join_bwd_reduce(int dt, const float* d_raw, const float* w, int oc, const void* y2, const float* s2, const float* b2,
                                const void* ys, const float* ss, const float* bs, float* partials, float* wpartials, int N, int H, int W,
                                void* st) {
-  return launch_tail_join_bwd_reduce(dt, d_raw, w, oc, N, H, W, s2, b2, ss, bs, y2, ys, partials, stream_of(st), wpartials);
+  return launch_tail_join_bwd_reduce(dt, d_raw, w, BnSide{y2, {s2, b2}}, BnSide{ys, {ss, bs}}, partials, oc, N, H, W, stream_of(st), wpartials);
 }
 int mmvae_tail_join_bwd_apply(int dt, const float* d_raw, const float* w, int oc, const void* y2, const float* s2, const float* b2,
                               const void* ys, const float* ss, const float* bs, const float* A2, const float* B2, const float* C2,
                               const float* As, const float* Bs, const float* Cs, void* dy2, void* dys, int N, int H, int W, void* st) {
-  return launch_tail_join_bwd_apply(dt, d_raw, w, oc, N, H, W, s2, b2, ss, bs, y2, A2, B2, C2, dy2, ys, As, Bs, Cs, dys, stream_of(st));
+  return launch_tail_join_bwd_apply(dt, d_raw, w, BnSide{y2, {s2, b2}, {A2, B2, C2}}, BnSide{ys, {ss, bs}, {As, Bs, Cs}}, dy2, dys, oc, N, H, W, stream_of(st));
 }
 int mmvae_upblock_bwd_fused(const float* d_raw, const float* tw, const void* y2, const float* s2, const float* b2, const void* ys, const float* ss,
                             const float* bs, const float* A2, const float* B2, const float* C2, const float* As, const float* Bs, const float* Cs,
@@ -639,10 +640,9 @@ int mmvae_upblock_bwd_fused(const float* d_raw, const float* tw, const void* y2,
   rc = op_pack_down(DT_BF16, g, wu, sc + 8192, stream_of(st)); if (rc < 0) return rc;
   float* parts = reinterpret_cast<float*>(sc + 16384);
   JoinBwdLaunch L;
-  L.d_raw = d_raw; L.w_tail = tw; L.y2 = y2; L.ys = ys; L.ms2 = s2; L.mb2 = b2; L.mss = ss; L.mbs = bs;
-  L.A2 = A2; L.B2 = B2; L.C2 = C2; L.As = As; L.Bs = Bs; L.Cs = Cs;
-  L.y1 = y1; L.p1s = s1; L.p1b = b1; L.wd2 = sc; L.da1 = da1; L.part2 = parts; L.bn_part = parts + 2L * 1024 * 4096;
-  L.xin = xin; L.pxs = sx; L.pxb = bx; L.wds = sc + 8192; L.gin = gin; L.parts = parts + 1024L * 4096;
+  L.d_raw = d_raw; L.w_tail = tw; L.y2 = BnSide{y2, {s2, b2}, {A2, B2, C2}}; L.ys = BnSide{ys, {ss, bs}, {As, Bs, Cs}};
+  L.y1 = BnSide{y1, {s1, b1}}; L.wd2 = sc; L.da1 = da1; L.part2 = parts; L.bn_part = parts + 2L * 1024 * 4096;
+  L.xin = BnSide{xin, {sx, bx}}; L.wds = sc + 8192; L.gin = gin; L.parts = parts + 1024L * 4096;
   L.N = N;
   const int nb = launch_join_bwd_stream(L, stream_of(st));
   if (nb < 0) return nb;
@@ -665,7 +665,7 @@ int mmvae_upblock_tail_fwd(const void* y1, const float* s1, const float* b1, con
   const ConvGeom g = geom_for(1, 16, 16, 4, 2, 1);
   int rc = op_pack_up(DT_BF16, g, w2, sc, stream_of(st)); if (rc < 0) return rc;
   rc = op_pack_up(DT_BF16, g, wu, sc + 8192, stream_of(st)); if (rc < 0) return rc;
-  return launch_up5_tail_fwd(y1, s1, b1, sc, xin, sx, bx, sc + 8192, s2, b2, ss, bs, tw, bias, r_raw, stats, N, stream_of(st));
+  return launch_up5_tail_fwd(BnSide{y1, {s1, b1}}, sc, BnSide{xin, {sx, bx}}, sc + 8192, Affine{s2, b2}, Affine{ss, bs}, tw, bias, r_raw, stats, N, stream_of(st));
 }
 int mmvae_upblock_tail_fwd_store(const void* y1, const float* s1, const float* b1, const float* w2, const void* xin, const float* sx, const float* bx,
                                  const float* wu, const float* s2, const float* b2, const float* ss, const float* bs, const float* tw,
@@ -678,7 +678,7 @@ int mmvae_upblock_tail_fwd_store(const void* y1, const float* s1, const float* b
   const ConvGeom g = geom_for(1, 16, 16, 4, 2, 1);
   int rc = op_pack_up(DT_BF16, g, w2, sc, stream_of(st)); if (rc < 0) return rc;
   rc = op_pack_up(DT_BF16, g, wu, sc + 8192, stream_of(st)); if (rc < 0) return rc;
-  return launch_up5_tail_fwd(y1, s1, b1, sc, xin, sx, bx, sc + 8192, s2, b2, ss, bs, tw, bias, r_raw, stats, N, stream_of(st), y2, ys);
+  return launch_up5_tail_fwd(BnSide{y1, {s1, b1}}, sc, BnSide{xin, {sx, bx}}, sc + 8192, Affine{s2, b2}, Affine{ss, bs}, tw, bias, r_raw, stats, N, stream_of(st), y2, ys);
 }
 int mmvae_convT4_stats(int dt, const void* x, const float* w, const float* ps, const float* pb, float* stats, int N, int e4m3_out, void* scratch,
                        void* st) {
@@ -698,7 +698,7 @@ int mmvae_conv1x1_bwd_fused(const void* da1, const void* y1, const float* s1, co
   const ConvGeom g = geom_for(0, 16, 16, 1, 1, 0);
   int rc = op_pack_up(DT_BF16, g, w1, sc, stream_of(st)); if (rc < 0) return rc;
   Conv1BwdLaunch C;
-  C.da1 = da1; C.y1 = y1; C.ms = s1; C.mb = b1; C.A = A1; C.B = B1; C.C = C1; C.xin = xin; C.pxs = sx; C.pxb = bx; C.w1u = sc; C.gin = gin;
+  C.da1 = da1; C.y1 = BnSide{y1, {s1, b1}, {A1, B1, C1}}; C.xin = BnSide{xin, {sx, bx}}; C.w1u = sc; C.gin = gin;
   C.part = reinterpret_cast<float*>(sc + 4096); C.nrows = (long)rows;
   const int nb = launch_conv1_bwd_stream(C, stream_of(st));
   if (nb < 0) return nb;
@@ -712,7 +712,7 @@ int mmvae_join_conv1x1_fwd(const void* y2, const float* s2, const float* b2, con
   if (!join_conv1_fwd_ok(DT_BF16, C, 16, (long)npix)) { set_error("join_conv1x1_fwd: C=%d npix=%ld unsupported (16 / 32 channels, whole 32-pixel steps)", C, (long)npix); return MMVAE_ERR_UNSUPPORTED; }
   const ConvGeom g = geom_for(0, C, 16, 1, 1, 0);
   const int rc = op_pack_down(DT_BF16, g, w1, scratch, stream_of(st)); if (rc < 0) return rc;
-  return launch_join_conv1_fwd(C, y2, s2, b2, ys, ss, bs, scratch, out, y1, stats, (long)npix, stream_of(st));
+  return launch_join_conv1_fwd(BnSide{y2, {s2, b2}}, BnSide{ys, {ss, bs}}, scratch, out, y1, stats, C, (long)npix, stream_of(st));
 }
 int mmvae_convert(int di, int dout, const void* in, void* out, int64_t n, void* st) { return launch_convert(di, dout, in, out, (long)n, stream_of(st)); }
 

@@ -245,7 +245,7 @@ int launch_conv3_stream_bwd(int dt, const void* dy, const void* w_flipped, void*
 
 // ---------------------------------------------------------------- last up-block join + tail conv (one output plane) as a stream
 // tail_fwd_stream_kernel: r_raw[n,0,h,w] = bias + sum_{kh,kw,c} x[n, h+kh-1, w+kw-1, c] * w[0][c][kh][kw] with the joined activation
-// x = relu(y2*s2+b2 + ys*ss+bs) recomputed on the way into a wave-private ring of rows (never stored).  tail_join_fwd_kernel (bn_elem.hip)
+// x = relu(y2*s2+b2 + ys*ss+bs) recomputed on the way into a wave-private ring of rows (never stored).  tail_join_fwd_kernel (tail_join.hip)
 // walks one image per block with per-tap dot products on the VALU and reads its 1.34 GB at 3.6 TB/s; here every wave streams strips of
 // rows, the next rows are in flight in registers, and the 16 x 9 reduction per pixel runs on the MFMA: two taps (2 x 16 channels) are one
 // K = 32 step, 6 steps per 16-pixel tile, the 15 unused output rows of the fragment cost nothing.  BatchNorm sums of the output
@@ -803,14 +803,14 @@ bool up5_tail_fwd_ok(int dt, int OC, int C, int Cin, int Hin, int Hout) {
   return dt == DT_BF16 && OC == 1 && C == 16 && Cin == 16 && Hin == 32 && Hout == 64;
 }
 // returns the number of partial rows [rows][2] (> 0) or an error
-int launch_up5_tail_fwd(const void* y1, const float* p1s, const float* p1b, const void* w2_up, const void* xin, const float* pxs, const float* pxb,
-                        const void* wu_up, const float* s2, const float* b2, const float* ss, const float* bs, const float* w, const float* bias,
-                        float* r_raw, float* stats, int N, hipStream_t s, void* y2, void* ys) {
+int launch_up5_tail_fwd(const BnSide& y1, const void* w2_up, const BnSide& xin, const void* wu_up, Affine bn2, Affine bns, const float* w,
+                        const float* bias, float* r_raw, float* stats, int N, hipStream_t s, void* y2, void* ys) {
   if ((y2 != nullptr) != (ys != nullptr)) { set_error("up5_tail_fwd: y2 and ys go together"); return MMVAE_ERR_ARG; }
   const bool store = y2 != nullptr;
+  const float* const pxs = xin.fwd.scale;
   Up5TailFwdArgs a; memset(&a, 0, sizeof(a));
-  a.y1 = y1; a.p1s = p1s; a.p1b = p1b; a.w2 = w2_up; a.xin = xin; a.pxs = pxs; a.pxb = pxb; a.wu = wu_up;
-  a.s2 = s2; a.b2 = b2; a.ss = ss; a.bs = bs; a.w = w; a.bias = bias; a.r_raw = r_raw; a.stats = stats; a.y2 = y2; a.ys = ys;
+  a.y1 = y1.y; a.p1s = y1.fwd.scale; a.p1b = y1.fwd.shift; a.w2 = w2_up; a.xin = xin.y; a.pxs = pxs; a.pxb = xin.fwd.shift; a.wu = wu_up;
+  a.s2 = bn2.scale; a.b2 = bn2.shift; a.ss = bns.scale; a.bs = bns.shift; a.w = w; a.bias = bias; a.r_raw = r_raw; a.stats = stats; a.y2 = y2; a.ys = ys;
   a.N = N; a.HS = 16; a.nunits = N * (32 / a.HS);
   int gx = 512;                                              // two blocks per CU (LDS), one resident round; rows of `stats` <= N
   while (gx > 1 && (long)gx * 4 > a.nunits) gx -= gx > 8 ? 8 : 1;
@@ -870,11 +870,12 @@ bool tail_fwd_stream_ok(int dt, int OC, int H, int W) {
   return dt == DT_BF16 && OC == 1 && W == 64 && H == 64;
 }
 // returns the number of partial rows [rows][2][1] (> 0) or an error
-int launch_tail_fwd_stream(int dt, const void* y2, const float* s2, const float* b2, const void* ys, const float* ss, const float* bs, const float* w,
-                           const float* bias, float* r_raw, float* stats, int N, int H, int W, hipStream_t s, int f8in) {
+int launch_tail_fwd_stream(int dt, const BnSide& y2, const BnSide& ys, const float* w, const float* bias, float* r_raw, float* stats, int N, int H,
+                           int W, hipStream_t s, int f8in) {
   if (!tail_fwd_stream_ok(dt, 1, H, W)) { set_error("tail_fwd_stream: bf16, one output plane, 64x64"); return MMVAE_ERR_UNSUPPORTED; }
   TailFwdStreamArgs a; memset(&a, 0, sizeof(a));
-  a.y2 = y2; a.ys = ys; a.s2 = s2; a.b2 = b2; a.ss = ss; a.bs = bs; a.w = w; a.bias = bias; a.r_raw = r_raw; a.stats = stats;
+  a.y2 = y2.y; a.ys = ys.y; a.s2 = y2.fwd.scale; a.b2 = y2.fwd.shift; a.ss = ys.fwd.scale; a.bs = ys.fwd.shift;
+  a.w = w; a.bias = bias; a.r_raw = r_raw; a.stats = stats;
   a.N = N; a.H = H; a.HS = 16; a.nunits = N * (H / a.HS);
   // blocks : 485 us at 256, 353 at 512, 333 at 768, 346 at 1024, 379 at 1280
   int gx = 768;                                              // rows of `stats` <= N: the entry point's contract is an [N][2] buffer

@@ -371,13 +371,14 @@ bool join_bwd_stream_ok(int dt, int OC, int C, int Hp, int Hg) {
 // Returns the number of blocks (= partial images per conv = rows of bn_part), <0 on error.
 int launch_join_bwd_stream(const JoinBwdLaunch& L, hipStream_t s) {
   JoinBwdArgs a; memset(&a, 0, sizeof(a));
-  a.d_raw = L.d_raw; a.w_tail = L.w_tail; a.y2 = L.y2; a.ys = L.ys;
-  a.ms2 = L.ms2; a.mb2 = L.mb2; a.mss = L.mss; a.mbs = L.mbs;
-  a.A2 = L.A2; a.B2 = L.B2; a.C2 = L.C2; a.As = L.As; a.Bs = L.Bs; a.Cs = L.Cs;
-  a.y1 = L.y1; a.p1s = L.p1s; a.p1b = L.p1b; a.wd2 = L.wd2; a.da1 = L.da1; a.part2 = L.part2; a.bn_part = L.bn_part;
-  a.xin = L.xin; a.pxs = L.pxs; a.pxb = L.pxb; a.wds = L.wds; a.gin = L.gin; a.parts = L.parts;
+  const bool pro_x = L.xin.fwd.scale != nullptr;
+  a.d_raw = L.d_raw; a.w_tail = L.w_tail; a.y2 = L.y2.y; a.ys = L.ys.y;
+  a.ms2 = L.y2.fwd.scale; a.mb2 = L.y2.fwd.shift; a.mss = L.ys.fwd.scale; a.mbs = L.ys.fwd.shift;
+  a.A2 = L.y2.bwd.A; a.B2 = L.y2.bwd.B; a.C2 = L.y2.bwd.C; a.As = L.ys.bwd.A; a.Bs = L.ys.bwd.B; a.Cs = L.ys.bwd.C;
+  a.y1 = L.y1.y; a.p1s = L.y1.fwd.scale; a.p1b = L.y1.fwd.shift; a.wd2 = L.wd2; a.da1 = L.da1; a.part2 = L.part2; a.bn_part = L.bn_part;
+  a.xin = L.xin.y; a.pxs = L.xin.fwd.scale; a.pxb = L.xin.fwd.shift; a.wds = L.wds; a.gin = L.gin; a.parts = L.parts;
   a.N = L.N; a.Hp = 32; a.Hg = 64; a.nunits = L.N;
-  if (!L.p1s || !L.p1b) { set_error("join_bwd_stream: conv2's input needs bn1's scale / shift"); return MMVAE_ERR_ARG; }
+  if (!a.p1s || !a.p1b) { set_error("join_bwd_stream: conv2's input needs bn1's scale / shift"); return MMVAE_ERR_ARG; }
   // measured (config 2, ms per step): two pairs per block x 512 blocks 7.17; 384 blocks 7.34; 768 blocks 7.24; one pair per block
   // (128 threads, 1024 blocks) 9.8 -- its register cap spills the accumulators
   // Phase ablation (isolated launch with its three helper launches, us): all 604; without the producer 451; without the weight-gradient
@@ -403,8 +404,8 @@ int launch_join_bwd_stream(const JoinBwdLaunch& L, hipStream_t s) {
     }                                                                                                                                \
     hipLaunchKernelGGL((join_bwd_stream_kernel<PX, PR, F8>), dim3(gx), dim3(128 * PR), lds, s, a);                                   \
   } while (0)
-  if (L.f8in) { if (L.pxs) MMVAE_JB(true, 2, true); else MMVAE_JB(false, 2, true); }
-  else { if (L.pxs) MMVAE_JB(true, 2, false); else MMVAE_JB(false, 2, false); }
+  if (L.f8in) { if (pro_x) MMVAE_JB(true, 2, true); else MMVAE_JB(false, 2, true); }
+  else { if (pro_x) MMVAE_JB(true, 2, false); else MMVAE_JB(false, 2, false); }
 #undef MMVAE_JB
   const int rc = check_launch("join_bwd_stream");
   return rc ? rc : gx;
@@ -517,12 +518,13 @@ __global__ __launch_bounds__(256, 4) void conv1_bwd_stream_kernel(Conv1BwdArgs a
 
 int launch_conv1_bwd_stream(const Conv1BwdLaunch& L, hipStream_t s) {
   Conv1BwdArgs a; memset(&a, 0, sizeof(a));
-  a.da1 = L.da1; a.y1 = L.y1; a.ms = L.ms; a.mb = L.mb; a.A = L.A; a.B = L.B; a.C = L.C; a.xin = L.xin; a.pxs = L.pxs; a.pxb = L.pxb;
+  a.da1 = L.da1; a.y1 = L.y1.y; a.ms = L.y1.fwd.scale; a.mb = L.y1.fwd.shift; a.A = L.y1.bwd.A; a.B = L.y1.bwd.B; a.C = L.y1.bwd.C;
+  a.xin = L.xin.y; a.pxs = L.xin.fwd.scale; a.pxb = L.xin.fwd.shift;
   a.w1u = L.w1u; a.gin = L.gin; a.part = L.part; a.nrows = L.nrows;
   int gx = 1024;
   while (gx > 8 && (long)gx * 4 > a.nrows) gx -= 8;
   note_launch_bytes((double)L.nrows * 1024.0 * 5);         // d_a1, y1, xin, g_in read; g_in written
-  if (L.pxs) {
+  if (a.pxs) {
     if (L.mask_out) hipLaunchKernelGGL((conv1_bwd_stream_kernel<true, true>), dim3(gx), dim3(256), 4 * 2048, s, a);
     else hipLaunchKernelGGL((conv1_bwd_stream_kernel<true, false>), dim3(gx), dim3(256), 4 * 2048, s, a);
   } else {

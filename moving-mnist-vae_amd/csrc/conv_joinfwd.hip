@@ -108,10 +108,11 @@ bool join_conv1_fwd_ok(int dt, int C, int Cout_next, long npix) {
 }
 
 // returns the number of blocks (= rows of `stats`, [2][16] each: sum, sum of squares of y1) or <0
-int launch_join_conv1_fwd(int C, const void* y2, const float* s2, const float* b2, const void* ys, const float* ss, const float* bs, const void* w1_down,
-                          void* out, void* y1, float* stats, long npix, hipStream_t s) {
+int launch_join_conv1_fwd(const BnSide& y2, const BnSide& ys, const void* w1_down, void* out, void* y1, float* stats, int C, long npix,
+                          hipStream_t s) {
   JoinConv1Args a; memset(&a, 0, sizeof(a));
-  a.y2 = y2; a.ys = ys; a.s2 = s2; a.b2 = b2; a.ss = ss; a.bs = bs; a.w1d = w1_down; a.out = out; a.y1 = y1; a.stats = stats; a.nsteps = npix / 32;
+  a.y2 = y2.y; a.ys = ys.y; a.s2 = y2.fwd.scale; a.b2 = y2.fwd.shift; a.ss = ys.fwd.scale; a.bs = ys.fwd.shift;
+  a.w1d = w1_down; a.out = out; a.y1 = y1; a.stats = stats; a.nsteps = npix / 32;
   int gx = 1024;
   while (gx > 8 && (long)gx * 4 > a.nsteps) gx -= 8;
   note_launch_bytes((double)npix * (3.0 * C + 16.0) * 2.0);        // y2, ys read; out, y1 written (bf16)

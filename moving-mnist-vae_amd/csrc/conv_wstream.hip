@@ -627,14 +627,14 @@ bool dgrad_wgrad_stream_shape(int dt, const WgradArgs& a) {
   const int kind = wstream_kind(dt, a);
   return (kind == 1 || kind == 2) && !a.proG_scale;
 }
-// jg (optional): G is the join's masked output gradient and dy = jg->A * G + jg->B * jg->y + jg->C is evaluated on load (JG above); the
+// jg (optional): G is the join's masked output gradient and dy = A * G + B * jg->y + C (jg->bwd) is evaluated on load (JG above); the
 // instantiated forms are the two a DeconvBottleneck on 16-wide maps needs: (Ca 16, prologue, BatchNorm sums) and (Ca 32, second source).
 bool dgrad_wgrad_stream_jg_shape(int dt, const WgradArgs& a, bool has_x2, bool bn_sums) {
   if (!dgrad_wgrad_stream_shape(dt, a) || wstream_kind(dt, a) != 2) return false;
   return (a.Ca == 16 && a.proP_scale && bn_sums && !has_x2) || (a.Ca == 32 && !a.proP_scale && has_x2 && !bn_sums);
 }
 int try_dgrad_wgrad_stream(int dt, const WgradArgs& a, const void* wd, void* dx, const void* x2, const void* w2, float* bn_part, hipStream_t s,
-                           float* dW2, float scale2, const JoinGrad* jg) {
+                           float* dW2, float scale2, const BnSide* jg) {
   if (!dgrad_wgrad_stream_shape(dt, a) || !wd || !dx || ((x2 != nullptr) != (w2 != nullptr))) return 0;
   if (jg && !dgrad_wgrad_stream_jg_shape(dt, a, x2 != nullptr, bn_part != nullptr)) { set_error("dgrad_wgrad_stream: no join-gradient form of this shape"); return MMVAE_ERR_UNSUPPORTED; }
   if (bn_part && (x2 || !a.proP_scale || a.Ca != 16)) { set_error("dgrad_wgrad_stream: BatchNorm sums need the prologue'd 16-channel P and no second source"); return MMVAE_ERR_ARG; }
@@ -643,7 +643,7 @@ int try_dgrad_wgrad_stream(int dt, const WgradArgs& a, const void* wd, void* dx,
   const int gx = wstream_fill(a, b, kind, x2 != nullptr);
   if (gx <= 0) return 0;
   b.wd = wd; b.dx = dx; b.x2 = x2; b.w2 = w2; b.bn_part = bn_part;
-  if (jg) { b.Jy = jg->y; b.jA = jg->A; b.jB = jg->B; b.jC = jg->C; }
+  if (jg) { b.Jy = jg->y; b.jA = jg->bwd.A; b.jB = jg->bwd.B; b.jC = jg->bwd.C; }
   note_launch_bytes((double)a.N * 2.0 * ((double)a.Hp * a.Wp * (2 * a.Ca + (x2 ? 16 : 0)) + (double)a.Hg * a.Wg * a.Cb * (jg ? 2 : 1)));   // P, dx, x2, G (+ Jy) (bf16)
   const bool pp = a.proP_scale != nullptr;
   int rc;

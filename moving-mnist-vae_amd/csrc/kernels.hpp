@@ -7,6 +7,13 @@ namespace mmvae {
 enum DType : int { DT_F32 = 0, DT_BF16 = 1 };
 inline size_t dtype_size(int dt) { return dt == DT_F32 ? 4 : 2; }
 
+// ---------------------------------------------------------------- a tensor seen through its BatchNorm
+// The launchers below take each such tensor as ONE argument: sides of a join first, then outputs, then the shape, then the stream.
+struct Affine { const float* scale = nullptr; const float* shift = nullptr; };                      // folded forward BatchNorm; both null: the tensor as it is
+struct BnCoef { const float* A = nullptr; const float* B = nullptr; const float* C = nullptr; };   // backward: dy = A*g + B*y + C (bn_bwd_finalize)
+// a pre-BatchNorm tensor with its rows: one side of a residual join, or a consumer's input under its BatchNorm + ReLU prologue (bwd unused)
+struct BnSide { const void* y = nullptr; Affine fwd; BnCoef bwd; };
+
 // ---------------------------------------------------------------- gather GEMM
 // y[n, hq*SO+ph, wq*SO+pw, co] (+)= bias[co] + sum_{t<ntaps} sum_{ci}
 //        pro(x[n, hq*SI+dh[t], wq*SI+dw[t], ci]) * w[co][t][ci]
@@ -75,23 +82,20 @@ int try_wgrad_stream_pair(int dt, const WgradArgs& a, const void* P2, float* dW2
 // weight gradient + data gradient (w.r.t. P) of a 16 -> 16 channel k4 s2 layer in one pass over G (conv_wstream.hip)
 bool dgrad_wgrad_stream_shape(int dt, const WgradArgs& a);
 // dW2 (optional, with x2): the 1x1 conv's own weight gradient [16][Ca] += scale2 * x2^T (x) pro(P), from the same pass
-// dy of a BatchNorm behind a residual join, evaluated by the consumer's loader: dy = A[c] * g + B[c] * y + C[c], g = the join's output gradient
-// already masked by its ReLU, y = the branch's pre-BatchNorm output (conv_wstream.hip, JG)
-struct JoinGrad { const void* y; const float* A; const float* B; const float* C; };
+// jg: dy of a BatchNorm behind a residual join, evaluated by the consumer's loader: dy = A[c] * g + B[c] * y + C[c] (jg->bwd), g = the join's
+// output gradient already masked by its ReLU, y = the branch's pre-BatchNorm output (conv_wstream.hip, JG)
 bool dgrad_wgrad_stream_jg_shape(int dt, const WgradArgs& a, bool has_x2, bool bn_sums);
 int try_dgrad_wgrad_stream(int dt, const WgradArgs& a, const void* wd, void* dx, const void* x2, const void* w2, float* bn_part, hipStream_t s,
-                           float* dW2 = nullptr, float scale2 = 1.f, const JoinGrad* jg = nullptr);
+                           float* dW2 = nullptr, float scale2 = 1.f, const BnSide* jg = nullptr);
 
 // ---- last up-block backward in one pass (conv_joinbwd.hip): the join's BatchNorm backward (incoming gradient recomputed from the
 // one-plane reconstruction gradient), both ConvTranspose2d weight gradients and data gradients, bn1's backward sums -- dy2 / dys are
-// never stored.  bf16, 16 channels, 32x32 -> 64x64, one output plane.  Coefficients: ms* / mb* forward scale / shift, A / B / C the
-// BatchNorm-backward coefficients of the two branch BatchNorms (bn_bwd_finalize).
+// never stored.  bf16, 16 channels, 32x32 -> 64x64, one output plane.
 struct JoinBwdLaunch {
-  const float* d_raw; const float* w_tail; const void* y2; const void* ys;
-  const float* ms2; const float* mb2; const float* mss; const float* mbs;
-  const float* A2; const float* B2; const float* C2; const float* As; const float* Bs; const float* Cs;
-  const void* y1; const float* p1s; const float* p1b; const void* wd2; void* da1; float* part2; float* bn_part;   // main path (conv2)
-  const void* xin; const float* pxs; const float* pxb; const void* wds; void* gin; float* parts;                  // shortcut (upsample)
+  const float* d_raw; const float* w_tail;
+  BnSide y2, ys;           // the two branch outputs at the join, under bn2 / the shortcut's BatchNorm
+  BnSide y1; const void* wd2; void* da1; float* part2; float* bn_part;   // main path (conv2): its input under bn1 + ReLU (fwd required)
+  BnSide xin; const void* wds; void* gin; float* parts;                  // shortcut (upsample): the block input under its prologue, if any
   int N;
   int f8in = 0;            // y2 / ys are e4m3 bytes (16 per pixel): fp8 mode's storage of these two tensors
 };
@@ -99,15 +103,15 @@ bool join_bwd_stream_ok(int dt, int OC, int C, int Hp, int Hg);
 int launch_join_bwd_stream(const JoinBwdLaunch& L, hipStream_t s);    // returns blocks = partial images per conv = rows of bn_part
 // ... and the block's 1x1 conv afterwards: dy1 from d_a1 (bn1 backward), g_in += dy1 (x) W1 in place, dW1 partial images [blocks][16][16]
 struct Conv1BwdLaunch {
-  const void* da1; const void* y1; const float* ms; const float* mb; const float* A; const float* B; const float* C;
-  const void* xin; const float* pxs; const float* pxb; const void* w1u; void* gin; float* part; long nrows;
-  int mask_out = 0;   // g_in leaves masked by the ReLU that produced xin (xin > 0): the block below evaluates its BatchNorm backward on load (JoinGrad)
+  const void* da1; BnSide y1;      // conv1's output under bn1: ReLU mask from fwd, dy1 from bwd
+  BnSide xin; const void* w1u; void* gin; float* part; long nrows;
+  int mask_out = 0;   // g_in leaves masked by the ReLU that produced xin (xin > 0): the block below evaluates its BatchNorm backward on load (jg)
 };
 int launch_conv1_bwd_stream(const Conv1BwdLaunch& L, hipStream_t s);  // returns blocks
 // conv_joinfwd.hip: a block's residual join fused with the next block's 1x1 conv1 (16 outputs) and bn1's statistics; C = joined channels (16 / 32)
 bool join_conv1_fwd_ok(int dt, int C, int Cout_next, long npix);
-int launch_join_conv1_fwd(int C, const void* y2, const float* s2, const float* b2, const void* ys, const float* ss, const float* bs, const void* w1_down,
-                          void* out, void* y1, float* stats, long npix, hipStream_t s);   // returns the rows of `stats`
+int launch_join_conv1_fwd(const BnSide& y2, const BnSide& ys, const void* w1_down, void* out, void* y1, float* stats, int C, long npix,
+                          hipStream_t s);   // returns the rows of `stats`
 
 // ---------------------------------------------------------------- v2 patch-tile kernels (conv_tile.hip)
 // A tile is up to TP (128, or 64/32 for wgrad on tiny feature maps) q-pixels: `qr` consecutive q-rows of one image (tiles_per_img > 0) or `segs` whole images.
@@ -231,14 +235,14 @@ int launch_convT4_stream(int dt, const void* x, const void* w_up, void* y, const
                                                                            // y == nullptr (not with f8out): the statistics alone, same partial rows
 // last up-block join + one-plane tail conv as a per-wave MFMA stream (conv_fstream.hip; bf16, 64x64): returns stats rows or an error
 bool tail_fwd_stream_ok(int dt, int OC, int H, int W);
-int launch_tail_fwd_stream(int dt, const void* y2, const float* s2, const float* b2, const void* ys, const float* ss, const float* bs, const float* w,
-                           const float* bias, float* r_raw, float* stats, int N, int H, int W, hipStream_t s, int f8in = 0);
+int launch_tail_fwd_stream(int dt, const BnSide& y2, const BnSide& ys, const float* w, const float* bias, float* r_raw, float* stats, int N, int H,
+                           int W, hipStream_t s, int f8in = 0);
 // the same with the two branch outputs recomputed from the ConvTranspose2d inputs instead of read (conv_fstream.hip; bf16, 32x32 -> 64x64, 16 channels);
 // y2 / ys (both or neither): the kernel also stores the branch outputs [N][64][64][16] bf16, bit-identical to launch_convT4_stream's
 bool up5_tail_fwd_ok(int dt, int OC, int C, int Cin, int Hin, int Hout);
-int launch_up5_tail_fwd(const void* y1, const float* p1s, const float* p1b, const void* w2_up, const void* xin, const float* pxs, const float* pxb,
-                        const void* wu_up, const float* s2, const float* b2, const float* ss, const float* bs, const float* w, const float* bias,
-                        float* r_raw, float* stats, int N, hipStream_t s, void* y2 = nullptr, void* ys = nullptr);
+// y1 / xin: the two ConvTranspose2d inputs under their prologues (xin's may be empty); bn2 / bns: the folded BatchNorms of the recomputed branches
+int launch_up5_tail_fwd(const BnSide& y1, const void* w2_up, const BnSide& xin, const void* wu_up, Affine bn2, Affine bns, const float* w,
+                        const float* bias, float* r_raw, float* stats, int N, hipStream_t s, void* y2 = nullptr, void* ys = nullptr);
 // stem forward as a per-wave stream (bf16; stem_bwd.hip): returns stats rows (> 0) or an error
 bool stem_fwd_stream_ok(int dt, int S);
 int launch_stem_fwd_stream(int dt, const void* x, const float* w, void* y, float* stats, int N, int S, hipStream_t s);
@@ -272,17 +276,15 @@ struct BnFoldEntry { int g_off, b_off, rm_off, rv_off, scale_off, shift_off, C; 
 constexpr int kBnFoldMax = 96;                       // 96 x 32 B of kernel arguments per launch
 struct BnFoldTable { BnFoldEntry e[kBnFoldMax]; };
 int launch_bn_fold_eval(const BnFoldEntry* entries, int n, const float* params, const float* bnbuf, float* bnws, float eps, hipStream_t s);
-// out = relu(a*sa + ba + b*sb + bb)   (NHWC, T)
-int launch_join_fwd(int dt, const void* a, const float* sa, const float* ba, const void* b, const float* sb, const float* bb,
-                    void* out, long npix, int C, hipStream_t s);
-// out = relu?(a*sa + ba)
-int launch_affine_act(int dt, const void* a, const float* sa, const float* ba, int relu, void* out, long npix, int C,
-                      hipStream_t s);
-// BN-backward reductions.  g = dout * mask, mask = (out > 0) if out!=null else (y0*msk_scale+msk_shift > 0) if msk_scale else 1.
-// partials [nparts][1+NY][C]: sum g, sum g*y0, (sum g*y1).  Returns nparts.
-int launch_bn_bwd_reduce(int dt, const void* dout, const void* out, const float* msk_scale, const float* msk_shift,
-                         const void* y0, const void* y1, long npix, int C, float* partials, hipStream_t s,
-                         const float* msk_scale1 = nullptr, const float* msk_shift1 = nullptr);   // both masks: join recomputed
+// out = relu(bn(a.y) + bn(b.y)), bn = the side's fwd   (NHWC, T)
+int launch_join_fwd(int dt, const BnSide& a, const BnSide& b, void* out, long npix, int C, hipStream_t s);
+// out = relu?(bn(a.y))
+int launch_affine_act(int dt, const BnSide& a, int relu, void* out, long npix, int C, hipStream_t s);
+// BN-backward reductions over side a (and side b when b.y != null: a residual join).  g = dout * mask, mask = (out > 0) if out != null, else
+// (bn(a.y) > 0) if a.fwd.scale, else 1; a join with b.fwd.scale as well masks by bn(a.y) + bn(b.y) > 0 (the join recomputed, `out` not read).
+// partials [nparts][1+NY][C]: sum g, sum g*a.y, (sum g*b.y).  Returns nparts.
+int launch_bn_bwd_reduce(int dt, const void* dout, const void* out, const BnSide& a, const BnSide& b, float* partials, long npix, int C,
+                         hipStream_t s);
 // coefficients for dy = A*g + B*y + Cc, plus dgamma/dbeta (accumulated into grads with +=)
 struct BnBwdFinalizeArgs {
   const float* partials; int nparts; int C; int which /*0: y0, 1: y1*/; int ny; double count;
@@ -294,34 +296,32 @@ struct BnBwdFinalizeArgs {
 };
 int launch_bn_bwd_finalize(const BnBwdFinalizeArgs& a, hipStream_t s);
 int launch_bn_bwd_finalize2(const BnBwdFinalizeArgs& a0, const BnBwdFinalizeArgs& a1, hipStream_t s);   // two BNs of equal width, one launch
-// dy0 = A0*g + B0*y0 + C0 ; (dy1 = A1*g + B1*y1 + C1)
-int launch_bn_bwd_apply(int dt, const void* dout, const void* out, const float* msk_scale, const float* msk_shift,
-                        const void* y0, const float* A0, const float* B0, const float* C0, void* dy0,
-                        const void* y1, const float* A1, const float* B1, const float* C1, void* dy1,
-                        long npix, int C, hipStream_t s, const float* msk_scale1 = nullptr, const float* msk_shift1 = nullptr);
-// last up-block: residual-join backward with the incoming gradient recomputed from the reconstruction gradient (bn_elem.hip)
-bool tail_join_fusable(int dt, int OC, int N, int H, int W);
-int launch_tail_join_bwd_reduce(int dt, const float* d_raw, const float* w, int OC, int N, int H, int W, const float* ms, const float* mb,
-                                const float* ms1, const float* mb1, const void* y0, const void* y1, float* partials, hipStream_t s,
-                                float* wpartials = nullptr, int f8in = 0);
-int launch_tail_wgrad_finalize(const float* wpartials, int nparts, float* dW, hipStream_t s);
-int launch_tail_join_bwd_apply(int dt, const float* d_raw, const float* w, int OC, int N, int H, int W, const float* ms, const float* mb,
-                               const float* ms1, const float* mb1, const void* y0, const float* A0, const float* B0, const float* C0, void* dy0,
-                               const void* y1, const float* A1, const float* B1, const float* C1, void* dy1, hipStream_t s);
-// last up-block forward: residual join + tail conv in one pass, the joined activation is not stored (bn_elem.hip)
-bool tail_fwd_fusable(int dt, int OC, int N, int H, int W);
-int launch_tail_join_fwd(int dt, const void* y0, const float* ms, const float* mb, const void* y1, const float* ms1, const float* mb1,
-                         const float* w, const float* bias, float* r_raw, float* stats, int N, int H, int W, hipStream_t s);
+// dy0 = a.bwd(g, a.y) ; (dy1 = b.bwd(g, b.y) when b.y != null); the mask of g as in launch_bn_bwd_reduce
+int launch_bn_bwd_apply(int dt, const void* dout, const void* out, const BnSide& a, const BnSide& b, void* dy0, void* dy1, long npix, int C,
+                        hipStream_t s);
 // NCHW f32 variants for the output BatchNorm (decoder.bn2): recon = raw*scale+shift ; backward pieces
-int launch_affine_nchw(const float* raw, const float* scale, const float* shift, float* out, int N, int C, int HW, hipStream_t s);
+int launch_affine_nchw(const float* raw, Affine bn, float* out, int N, int C, int HW, hipStream_t s);
 int launch_bn_bwd_reduce_nchw(const float* dout, const float* y, int N, int C, int HW, float* partials, hipStream_t s);
-int launch_bn_bwd_apply_nchw(const float* dout, const float* y, const float* A, const float* B, const float* Cc, float* dy,
-                             int N, int C, int HW, hipStream_t s);
+int launch_bn_bwd_apply_nchw(const float* dout, const float* y, BnCoef k, float* dy, int N, int C, int HW, hipStream_t s);
 // Gaussian NLL gradient fused into the output BatchNorm's backward: d = coef / sigma^2 * gscale[0] * (scale*raw + shift - target) is never stored
-int launch_gauss_tail_reduce(const float* raw, const float* target, const float* scale, const float* shift, float sigma, float coef, const float* gscale,
-                             int N, int C, int HW, float* partials, hipStream_t s);      // partial rows (sum d, sum d*raw); returns nparts
-int launch_gauss_tail_apply(const float* raw, const float* target, const float* scale, const float* shift, float sigma, float coef, const float* gscale,
-                            const float* A, const float* B, const float* Cc, float* dy, int N, int C, int HW, hipStream_t s);
+int launch_gauss_tail_reduce(const float* raw, Affine bn, const float* target, float sigma, float coef, const float* gscale, float* partials, int N,
+                             int C, int HW, hipStream_t s);      // partial rows (sum d, sum d*raw); returns nparts
+int launch_gauss_tail_apply(const float* raw, Affine bn, BnCoef k, const float* target, float sigma, float coef, const float* gscale, float* dy, int N,
+                            int C, int HW, hipStream_t s);
+
+// ---------------------------------------------------------------- last up-block: join + one-plane tail conv (tail_join.hip)
+// y2 / ys: the block's two branch outputs under bn2 / the shortcut's BatchNorm; w: the tail conv's weights [OC][16][3][3] f32.
+// Backward: the residual join's BatchNorm backward with the incoming gradient recomputed from the reconstruction gradient d_raw
+bool tail_join_fusable(int dt, int OC, int N, int H, int W);
+int launch_tail_join_bwd_reduce(int dt, const float* d_raw, const float* w, const BnSide& y2, const BnSide& ys, float* partials, int OC, int N,
+                                int H, int W, hipStream_t s, float* wpartials = nullptr, int f8in = 0);
+int launch_tail_wgrad_finalize(const float* wpartials, int nparts, float* dW, hipStream_t s);
+int launch_tail_join_bwd_apply(int dt, const float* d_raw, const float* w, const BnSide& y2, const BnSide& ys, void* dy2, void* dys, int OC, int N,
+                               int H, int W, hipStream_t s);
+// Forward: residual join + tail conv in one pass, the joined activation is not stored
+bool tail_fwd_fusable(int dt, int OC, int N, int H, int W);
+int launch_tail_join_fwd(int dt, const BnSide& y2, const BnSide& ys, const float* w, const float* bias, float* r_raw, float* stats, int N, int H,
+                         int W, hipStream_t s);
 
 // ---------------------------------------------------------------- PixelCNN pieces (pixelcnn.hip; reference model.py:227-255)
 // InstanceNorm2d (affine = False, eps 1e-5, instance statistics always) forward / backward fused with the ReLU behind it, and the layout

@@ -1,4 +1,4 @@
-// Device helpers shared by the patch-tile kernels (conv_tile.hip, conv_wgrad_*.hip).
+// Device helpers shared by the patch-tile kernels (conv_tile.hip, conv_wgrad_*.hip) and, at the end, by the element-wise kernels.
 #pragma once
 #include "kernels.hpp"
 
@@ -142,6 +142,32 @@ __device__ __forceinline__ TileWalk xcd_tile_walk(int ntiles) {
   const int per = (ntiles + 7) >> 3;
   const int lo = (b & 7) * per;
   return TileWalk{lo + (b >> 3), B >> 3, min(ntiles, lo + per)};
+}
+
+// ---- shared by the element-wise BatchNorm kernels (bn_elem.hip) and the last up-block's join kernels (tail_join.hip)
+// Grid cap of the grid-stride elementwise kernels: 768 = three blocks per CU.  Per kernel it makes no difference (bn_bwd_apply 62 us,
+// affine_join 33 us at 512 .. 2048 blocks), the STEP gains 0.06 ms over 2048 (7.91 vs 7.98 ms, twice on one box; 512: 7.92, 640: 7.96,
+// 896: 8.00): fewer resident blocks leave the weight-gradient kernels of the side stream more of every CU.
+constexpr int kElemMaxBlocks = 768;
+
+// Per-thread channel-group partials -> per-block per-channel sums.  vals[NV][VE] per thread; threads with equal
+// (threadIdx.x % cvecs) share channels.  Writes out[v*C + cg*VE + j] for v<NV.
+template <int NV, int VE>
+__device__ __forceinline__ void block_channel_reduce(float (&vals)[NV][VE], int cvecs, int C, float* smem, float* out) {
+  // smem: blockDim.x * NV * VE floats
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int v = 0; v < NV; ++v)
+#pragma unroll
+    for (int j = 0; j < VE; ++j) smem[(t * NV + v) * VE + j] = vals[v][j];
+  __syncthreads();
+  for (int o = t; o < cvecs * NV * VE; o += blockDim.x) {
+    const int cg = o / (NV * VE), rem = o - cg * (NV * VE);
+    float s = 0.f;
+    for (int tt = cg; tt < (int)blockDim.x; tt += cvecs) s += smem[tt * NV * VE + rem];
+    const int v = rem / VE, j = rem - v * VE;
+    out[(long)v * C + cg * VE + j] = s;
+  }
 }
 
 }  // namespace mmvae

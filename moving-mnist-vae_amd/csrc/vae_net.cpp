@@ -541,26 +541,25 @@ int Net::bn_backward_coefs_join(const Pass& ps, const Bn& b2, const Bn& bs, int 
   return launch_bn_bwd_finalize2(g2, gs, s);
 }
 int Net::bn_relu_backward(const Pass& ps, const Bn& bn, const void* g, const void* y, void* dy, long npix, hipStream_t s, int nparts_ready) {
-  const BnRows r = ps.rows(bn);
-  const int np = nparts_ready > 0 ? nparts_ready : launch_bn_bwd_reduce(dt(), g, nullptr, r.scale, r.shift, y, nullptr, npix, bn.C, ps.part, s);
+  const BnSide a = ps.rows(bn).side(y);
+  const int np = nparts_ready > 0 ? nparts_ready : launch_bn_bwd_reduce(dt(), g, nullptr, a, BnSide{}, ps.part, npix, bn.C, s);
   MM_TRY(np);
   MM_TRY(bn_backward_coefs(ps, bn, np, 1, 0, (double)npix, s));
-  return launch_bn_bwd_apply(dt(), g, nullptr, r.scale, r.shift, y, r.A, r.B, r.C, dy, nullptr, nullptr, nullptr, nullptr, nullptr, npix, bn.C, s);
+  return launch_bn_bwd_apply(dt(), g, nullptr, a, BnSide{}, dy, nullptr, npix, bn.C, s);
 }
-int Net::join_backward(const Pass& ps, const Block& B, const Shortcut& sc, const void* g, bool g_masked, void* dy2, void* dys, hipStream_t s,
+int Net::join_backward(const Pass& ps, const Block& B, const BnSide& sc, const void* g, bool g_masked, void* dy2, void* dys, hipStream_t s,
                        int nparts_ready) {
-  const BnRows r2 = ps.rows(B.b2);
-  const void* y2 = ps.base + B.y2;
+  const BnSide s2 = ps.rows(B.b2).side(ps.base + B.y2);
   const long npix = (long)ps.N * B.Hout * B.Wout;
-  const bool m = !g_masked;        // the reduce applies the join's ReLU mask itself
-  const int np = nparts_ready > 0 ? nparts_ready : launch_bn_bwd_reduce(dt(), g, nullptr, m ? r2.scale : nullptr, m ? r2.shift : nullptr, y2, sc.y, npix, B.C,
-                                                                        ps.part, s, m ? sc.scale : nullptr, m ? sc.shift : nullptr);
+  // g_masked: plain sums, no forward rows; else the reduce applies the join's ReLU mask itself
+  const int np = nparts_ready > 0 ? nparts_ready
+                 : g_masked       ? launch_bn_bwd_reduce(dt(), g, nullptr, BnSide{s2.y}, BnSide{sc.y}, ps.part, npix, B.C, s)
+                                  : launch_bn_bwd_reduce(dt(), g, nullptr, s2, sc, ps.part, npix, B.C, s);
   MM_TRY(np);
   if (B.identity) MM_TRY(bn_backward_coefs(ps, B.b2, np, 2, 0, (double)npix, s));
   else MM_TRY(bn_backward_coefs_join(ps, B.b2, B.bs, np, (double)npix, s));
   if (!dy2) return MMVAE_OK;
-  return launch_bn_bwd_apply(dt(), g, nullptr, r2.scale, r2.shift, y2, r2.A, r2.B, r2.C, dy2, sc.y, sc.A, sc.B, sc.C, dys, npix, B.C, s, sc.scale,
-                             sc.shift);
+  return launch_bn_bwd_apply(dt(), g, nullptr, s2, sc, dy2, dys, npix, B.C, s);
 }
 
 // ------------------------------------------------------------------------------------------------ weight re-packs per entry point
@@ -692,8 +691,8 @@ int Net::encoder_fwd(int N, const float* x, const float* params, float* bnbuf, l
   for (size_t i = 0; i < enc.size(); ++i) {
     Block& B = enc[i];
     const double cnt = (double)N * B.Hout * B.Wout;
-    const BnRows r1 = ps.rows(B.b1), r2 = ps.rows(B.b2);
-    const Shortcut sc = ps.shortcut(B, xin);
+    const BnRows r1 = ps.rows(B.b1);
+    const BnSide s2 = ps.rows(B.b2).side(base + B.y2), sc = ps.shortcut(B, xin);
     // shortcut branch (conv + its BatchNorm) on the side stream, concurrently with conv1 -> bn1 -> conv2 -> bn2 -- unless one kernel takes conv1 with it
     const bool stream1 = B.r.fwd_c1_cs_stream, stream2 = B.r.fwd_c2_stream, fork = !B.identity && !stream1;
     if (stream1) {
@@ -722,7 +721,7 @@ int Net::encoder_fwd(int N, const float* x, const float* params, float* bnbuf, l
     MM_TRY(np);
     MM_TRY(bn_fwd(ps, B.b2, np, cnt, s, 0, B.c2.wscale));
     if (fork) MM_TRY(side_join(s));
-    MM_TRY(launch_join_fwd(dt(), base + B.y2, r2.scale, r2.shift, sc.y, sc.scale, sc.shift, base + B.out, (long)N * B.Hout * B.Wout, B.C, s));
+    MM_TRY(launch_join_fwd(dt(), s2, sc, base + B.out, (long)N * B.Hout * B.Wout, B.C, s));
     xin = base + B.out; xs = xb = nullptr;
   }
   // global average pool + the two 1x1 heads (model.py:123-128) as ONE k=Hf,s=Hf conv whose taps share W/(Hf*Wf)
@@ -788,7 +787,7 @@ int Net::encoder_bwd(int N, const float* d_mu, const float* d_logvar, const floa
     const float* xs = i == 0 ? r0.scale : nullptr;
     const float* xb = i == 0 ? r0.shift : nullptr;
     const BnRows r1 = ps.rows(B.b1);
-    const Shortcut sc = ps.shortcut(B, xin);
+    const BnSide sc = ps.shortcut(B, xin);
     // dy1 / dy2 / dys alternate between two sets, so this block only has to wait for the weight gradients of the block
     // before the previous one (the side stream may lag one block behind)
     // The two blocks visited first (small tensors) own private sets: with a deferred decoder join the side stream may still be
@@ -921,15 +920,15 @@ int Net::decoder_fwd(int N, const float* encv, const float* params, float* bnbuf
   if (cfg.blocks > 1) {
     // the first block of a deeper decoder has an identity shortcut: it needs the stem's activation as a tensor
     MM_TRY(fill_consts(ps, s));
-    MM_TRY(launch_affine_act(dt(), base + P.y0d, xs, xb, 1, base + P.act0d, (long)N * 4, 128, s));
+    MM_TRY(launch_affine_act(dt(), BnSide{base + P.y0d, {xs, xb}}, 1, base + P.act0d, (long)N * 4, 128, s));
     xin = base + P.act0d; xs = xb = nullptr;
   }
   int c1_done = 0;                 // rows of bn1 statistics the previous block's join kernel left for this block's conv1 (0: conv1 not done)
   for (int i = 0; i < nd; ++i) {
     Block& B = dec[i];
     const double cnt = (double)N * B.Hout * B.Wout;
-    const BnRows r1 = ps.rows(B.b1), r2 = ps.rows(B.b2);
-    const Shortcut sc = ps.shortcut(B, xin);
+    const BnRows r1 = ps.rows(B.b1);
+    const BnSide s2 = ps.rows(B.b2).side(base + B.y2), sc = ps.shortcut(B, xin);
     // a ConvTranspose2d forward: the per-wave stream (conv_fstream.hip) where routed -- on the up5 route statistics only, nothing in eval mode -- else the up conv
     auto convT = [&](const ConvW& w, bool stream, const void* x, long y, const float* pro_s, const float* pro_b, float* st, hipStream_t q) {
       const bool stats_only = B.r.fwd_stats_only;
@@ -960,31 +959,27 @@ int Net::decoder_fwd(int N, const float* encv, const float* params, float* bnbuf
     if (!B.identity) MM_TRY(side_join(s));
     if (i == nd - 1 && R.tail_fwd != TAIL_GATHER) break;     // the join of the last block happens inside the tail conv kernel
     if (B.r.fwd_join_conv1) {      // the join computes the next block's conv1 and bn1's statistics as well
-      c1_done = launch_join_conv1_fwd(B.C, base + B.y2, r2.scale, r2.shift, sc.y, sc.scale, sc.shift, ps.packed(dec[i + 1].c1.packD),
-                                      base + B.out, base + dec[i + 1].y1, stats, (long)N * B.Hout * B.Wout, s);
+      c1_done = launch_join_conv1_fwd(s2, sc, ps.packed(dec[i + 1].c1.packD), base + B.out, base + dec[i + 1].y1, stats, B.C,
+                                      (long)N * B.Hout * B.Wout, s);
       MM_TRY(c1_done);
     } else
-    MM_TRY(launch_join_fwd(dt(), base + B.y2, r2.scale, r2.shift, sc.y, sc.scale, sc.shift, base + B.out, (long)N * B.Hout * B.Wout, B.C, s));
+    MM_TRY(launch_join_fwd(dt(), s2, sc, base + B.out, (long)N * B.Hout * B.Wout, B.C, s));
     xin = base + B.out; xs = xb = nullptr;
   }
   // tail conv (+bias) and the output BatchNorm (model.py:193)
   float* r_raw = reinterpret_cast<float*>(base + P.r_raw);
   if (R.tail_fwd != TAIL_GATHER) {
     const Block& B = dec.back();     // (the join left to this kernel: xin is still the block's input)
-    const BnRows r1 = ps.rows(B.b1), r2 = ps.rows(B.b2);
-    const Shortcut sc = ps.shortcut(B, xin);
+    const BnSide s1 = ps.rows(B.b1).side(base + B.y1), s2 = ps.rows(B.b2).side(base + B.y2), sc = ps.shortcut(B, xin);
     if (R.tail_fwd == TAIL_UP5)
       // the join + tail conv with both branch outputs recomputed from the ConvTranspose2d inputs (0.34 GB) instead of read back (1.34 GB),
       // and (training) stored from here for the backward pass
-      np = launch_up5_tail_fwd(base + B.y1, r1.scale, r1.shift, ps.packed(B.c2.packU), xin, xs, xb, ps.packed(B.cs.packU), r2.scale, r2.shift,
-                               sc.scale, sc.shift, params + tail.off, params + tail_bias, r_raw, stats, N, s,
-                               stats ? base + B.y2 : nullptr, stats ? base + B.ys : nullptr);
+      np = launch_up5_tail_fwd(s1, ps.packed(B.c2.packU), BnSide{xin, {xs, xb}}, ps.packed(B.cs.packU), s2.fwd, sc.fwd, params + tail.off,
+                               params + tail_bias, r_raw, stats, N, s, stats ? base + B.y2 : nullptr, stats ? base + B.ys : nullptr);
     else if (R.tail_fwd == TAIL_STREAM)
-      np = launch_tail_fwd_stream(dt(), base + B.y2, r2.scale, r2.shift, sc.y, sc.scale, sc.shift, params + tail.off, params + tail_bias,
-                                  r_raw, stats, N, Sd, Sd, s, R.store8 ? 1 : 0);
+      np = launch_tail_fwd_stream(dt(), s2, sc, params + tail.off, params + tail_bias, r_raw, stats, N, Sd, Sd, s, R.store8 ? 1 : 0);
     else
-      np = launch_tail_join_fwd(dt(), base + B.y2, r2.scale, r2.shift, sc.y, sc.scale, sc.shift, params + tail.off, params + tail_bias,
-                                r_raw, stats, N, Sd, Sd, s);
+      np = launch_tail_join_fwd(dt(), s2, sc, params + tail.off, params + tail_bias, r_raw, stats, N, Sd, Sd, s);
   } else {
     // Conv2d(16 -> out_ch, k3 p1, bias): GEMM rows padded to 16 in LDS, epilogue stores the out_ch real rows as NCHW f32
     GatherArgs a; std::memset(&a, 0, sizeof(a));
@@ -996,7 +991,7 @@ int Net::decoder_fwd(int N, const float* encv, const float* params, float* bnbuf
   }
   MM_TRY(np);
   MM_TRY(bn_fwd(ps, bn_out, np, (double)N * Sd * Sd, s));
-  MM_TRY(launch_affine_nchw(r_raw, ps.rows(bn_out).scale, ps.rows(bn_out).shift, recon, N, cfg.out_ch, Sd * Sd, s));
+  MM_TRY(launch_affine_nchw(r_raw, ps.rows(bn_out).affine(), recon, N, cfg.out_ch, Sd * Sd, s));
   return MMVAE_OK;
 }
 
@@ -1027,17 +1022,16 @@ int Net::decoder_bwd(int N, const float* d_recon, const float* params, float* gr
     // 6.018 vs 6.018 ms over three A/B pairs; not kept)
   }
   // ---- output BN backward, tail conv backward
-  int np = gauss ? launch_gauss_tail_reduce(r_raw, gauss->target, ro.scale, ro.shift, gauss->sigma, gauss->coef, gauss->gscale, N, cfg.out_ch,
-                                            HW, part, s)
+  int np = gauss ? launch_gauss_tail_reduce(r_raw, ro.affine(), gauss->target, gauss->sigma, gauss->coef, gauss->gscale, part, N, cfg.out_ch, HW, s)
                  : launch_bn_bwd_reduce_nchw(d_recon, r_raw, N, cfg.out_ch, HW, part, s);
   MM_TRY(np);
   // (the tail conv's bias gradient, sum of d_raw per output channel, in closed form from the same sums: BnBwdFinalizeArgs::dbias_conv)
   MM_TRY(bn_backward_coefs(ps, bn_out, np, 1, 0, (double)N * HW, s, grads + tail_bias));
   if (gauss)
-    MM_TRY(launch_gauss_tail_apply(r_raw, gauss->target, ro.scale, ro.shift, gauss->sigma, gauss->coef, gauss->gscale, ro.A, ro.B, ro.C, d_raw,
-                                   N, cfg.out_ch, HW, s));
+    MM_TRY(launch_gauss_tail_apply(r_raw, ro.affine(), ro.coef(), gauss->target, gauss->sigma, gauss->coef, gauss->gscale, d_raw, N, cfg.out_ch,
+                                   HW, s));
   else
-    MM_TRY(launch_bn_bwd_apply_nchw(d_recon, r_raw, ro.A, ro.B, ro.C, d_raw, N, cfg.out_ch, HW, s));
+    MM_TRY(launch_bn_bwd_apply_nchw(d_recon, r_raw, ro.coef(), d_raw, N, cfg.out_ch, HW, s));
   if (!R.tail_wg_in_reduce) {      // (else the forward did not store the joined activation: the join-backward reduce pass below recomputes it)
     // dW[oc][ci][kh][kw]: P = d_raw (planar f32, out_ch planes staged as 16 zero-padded channels), G = the last up-block's output
     WgradArgs a; std::memset(&a, 0, sizeof(a));
@@ -1067,16 +1061,16 @@ int Net::decoder_bwd(int N, const float* d_recon, const float* params, float* gr
     const void* xin = i == 0 ? (cfg.blocks > 1 ? base + P.act0d : base + P.y0d) : base + dec[i - 1].out;
     const float* xs = (i == 0 && cfg.blocks <= 1) ? r0.scale : nullptr;
     const float* xb = (i == 0 && cfg.blocks <= 1) ? r0.shift : nullptr;
-    const BnRows r1 = ps.rows(B.b1), r2 = ps.rows(B.b2);
-    const Shortcut sc = ps.shortcut(B, xin);
+    const BnRows r1 = ps.rows(B.b1);
+    const BnSide s1 = r1.side(base + B.y1), s2 = ps.rows(B.b2).side(base + B.y2), sc = ps.shortcut(B, xin), in{xin, {xs, xb}};
     const int ds = i & 1;          // dy set of this block (see encoder_bwd)
     if (i + 2 <= nd - 1) MM_TRY(side_wait_mark(i + 2, s));
     const bool from_tail = R.tail_bwd_fused && i == nd - 1;
     // an identity shortcut's gradient is the masked incoming gradient itself: it goes straight into the block-input gradient
     const long dyso = B.identity ? P.g[cur ^ 1] : P.dys[ds];
     if (from_tail) {
-      np = launch_tail_join_bwd_reduce(dt(), d_raw, params + tail.off, cfg.out_ch, N, Sd, Sd, r2.scale, r2.shift, sc.scale, sc.shift, base + B.y2,
-                                       sc.y, part, s, R.tail_wg_in_reduce ? ps.wscratch : nullptr, R.store8 ? 1 : 0);
+      np = launch_tail_join_bwd_reduce(dt(), d_raw, params + tail.off, s2, sc, part, cfg.out_ch, N, Sd, Sd, s,
+                                       R.tail_wg_in_reduce ? ps.wscratch : nullptr, R.store8 ? 1 : 0);
       MM_TRY(np);
       if (R.tail_wg_in_reduce) {
         MM_TRY(side_fork(s));
@@ -1088,13 +1082,9 @@ int Net::decoder_bwd(int N, const float* d_recon, const float* params, float* gr
     if (B.r.bwd_join_stream) {   // the whole block in one pass (conv_joinbwd.hip); conv1 (1x1) follows once bn1's sums are final
       float* ws2 = reinterpret_cast<float*>(base + P.wscratch2);
       JoinBwdLaunch L;
-      L.d_raw = d_raw; L.w_tail = params + tail.off; L.y2 = base + B.y2; L.ys = sc.y;
-      L.ms2 = r2.scale; L.mb2 = r2.shift; L.mss = sc.scale; L.mbs = sc.shift;
-      L.A2 = r2.A; L.B2 = r2.B; L.C2 = r2.C;
-      L.As = sc.A; L.Bs = sc.B; L.Cs = sc.C;
-      L.y1 = base + B.y1; L.p1s = r1.scale; L.p1b = r1.shift;
-      L.wd2 = ps.packed(B.c2.packD); L.da1 = base + P.da1; L.part2 = ws2; L.bn_part = part;
-      L.xin = xin; L.pxs = xs; L.pxb = xb; L.wds = ps.packed(B.cs.packD); L.gin = base + P.g[cur ^ 1];
+      L.d_raw = d_raw; L.w_tail = params + tail.off; L.y2 = s2; L.ys = sc;
+      L.y1 = s1; L.wd2 = ps.packed(B.c2.packD); L.da1 = base + P.da1; L.part2 = ws2; L.bn_part = part;
+      L.xin = in; L.wds = ps.packed(B.cs.packD); L.gin = base + P.g[cur ^ 1];
       L.parts = ws2 + 1024L * 4096;                        // (at most 1024 blocks, one [16][16][16] partial image per conv each)
       L.N = N; L.f8in = R.store8 ? 1 : 0;
       const int nb = launch_join_bwd_stream(L, s);
@@ -1103,9 +1093,7 @@ int Net::decoder_bwd(int N, const float* d_recon, const float* params, float* gr
       MM_TRY(reduce_wgrad_parts(ps, B.cs, L.parts, nb, 16, s));
       MM_TRY(bn_backward_coefs(ps, B.b1, nb, 1, 0, (double)npi, s));
       Conv1BwdLaunch C1;
-      C1.da1 = base + P.da1; C1.y1 = base + B.y1; C1.ms = r1.scale; C1.mb = r1.shift;
-      C1.A = r1.A; C1.B = r1.B; C1.C = r1.C;
-      C1.xin = xin; C1.pxs = xs; C1.pxb = xb; C1.w1u = ps.packed(B.c1.packU);
+      C1.da1 = base + P.da1; C1.y1 = s1; C1.xin = in; C1.w1u = ps.packed(B.c1.packU);
       C1.gin = base + P.g[cur ^ 1]; C1.part = ws2; C1.nrows = (long)N * B.Hin;
       C1.mask_out = (i > 0 && dec[i - 1].r.bwd_join_grad) ? 1 : 0;
       const int nb1 = launch_conv1_bwd_stream(C1, s);
@@ -1116,8 +1104,7 @@ int Net::decoder_bwd(int N, const float* d_recon, const float* params, float* gr
       continue;
     }
     if (from_tail)
-      MM_TRY(launch_tail_join_bwd_apply(dt(), d_raw, params + tail.off, cfg.out_ch, N, Sd, Sd, r2.scale, r2.shift, sc.scale, sc.shift, base + B.y2,
-                                        r2.A, r2.B, r2.C, base + P.dy2[ds], sc.y, sc.A, sc.B, sc.C, base + P.dys[ds], s));
+      MM_TRY(launch_tail_join_bwd_apply(dt(), d_raw, params + tail.off, s2, sc, base + P.dy2[ds], base + P.dys[ds], cfg.out_ch, N, Sd, Sd, s));
     hipStream_t wsm = wgrad_stream(s);
     MM_TRY(side_fork(s));
     const bool fuse_c2 = B.r.bwd_fuse_c2, fuse_cs = B.r.bwd_fuse_cs;
@@ -1134,10 +1121,9 @@ int Net::decoder_bwd(int N, const float* d_recon, const float* params, float* gr
       if (!fuse_cs) MM_TRY(run_wgrad(ps, B.cs, xin, B.Hin, B.Win, xs, xb, base + P.dys[ds], B.Hout, B.Wout, nullptr, nullptr, wsm));
       if (fuse_c2) {
         // ... and bn1's backward sums come out of the same pass (the data gradient is in registers, y1 is the pass's P operand)
-        const JoinGrad j2{base + B.y2, r2.A, r2.B, r2.C};
         const int rcf = op_run_bwd_fused(dt(), geom(B.c2), N, base + B.y1, B.Hin, B.Win, r1.scale, r1.shift, 1,
                                          jg ? base + P.g[cur] : base + P.dy2[ds], B.Hout, B.Wout, ps.packed(B.c2.packD), base + P.da1, nullptr,
-                                         nullptr, grads + B.c2.off, s, wsc2, B.c2.wscale, B.C == 16 ? part : nullptr, nullptr, 1.f, jg ? &j2 : nullptr);
+                                         nullptr, grads + B.c2.off, s, wsc2, B.c2.wscale, B.C == 16 ? part : nullptr, nullptr, 1.f, jg ? &s2 : nullptr);
         if (rcf <= 0) { if (rcf == 0) set_error("decoder_bwd: fused backward of %s not taken", "conv2"); return rcf < 0 ? rcf : MMVAE_ERR_UNSUPPORTED; }
         if (B.C == 16) np_b1 = rcf;
       } else
@@ -1152,10 +1138,9 @@ int Net::decoder_bwd(int N, const float* d_recon, const float* params, float* gr
     if (B.identity)     // d_xin already holds the shortcut's share: the 1x1 conv's data gradient is added to it
       MM_TRY(run_up(ps, B.c1, base + P.dy1[ds], B.Hin, B.Win, base + P.g[cur ^ 1], B.Hin, B.Win, nullptr, nullptr, 0, nullptr, 1, s));
     else if (fuse_cs) {  // shortcut ConvT: weight gradient + data gradient + the 1x1 conv's share (dy1 (x) w1) and ITS weight gradient, one pass over dys
-      const JoinGrad js{sc.y, sc.A, sc.B, sc.C};
       const int rcf = op_run_bwd_fused(dt(), geom(B.cs), N, xin, B.Hin, B.Win, xs, xb, 1, jg ? base + P.g[cur] : base + P.dys[ds], B.Hout, B.Wout,
                                        ps.packed(B.cs.packD), base + P.g[cur ^ 1], base + P.dy1[ds], ps.packed(B.c1.packU), grads + B.cs.off, s,
-                                       reinterpret_cast<float*>(base + P.wscratch2), B.cs.wscale, nullptr, grads + B.c1.off, B.c1.wscale, jg ? &js : nullptr);
+                                       reinterpret_cast<float*>(base + P.wscratch2), B.cs.wscale, nullptr, grads + B.c1.off, B.c1.wscale, jg ? &sc : nullptr);
       if (rcf <= 0) { if (rcf == 0) set_error("decoder_bwd: fused backward of %s not taken", "upsample"); return rcf < 0 ? rcf : MMVAE_ERR_UNSUPPORTED; }
     } else              // one kernel: the 1x1 conv's data gradient (dy1, already on this block's input grid) is a second source of the shortcut's
       MM_TRY(run_down(ps, B.cs, base + P.dys[ds], B.Hout, B.Wout, base + P.g[cur ^ 1], B.Hin, B.Win, nullptr, nullptr, 0, nullptr, 0, dt(), s,

@@ -38,7 +38,12 @@ struct Bn {
   long row(Row r) const { return ws + r * row_floats(); }
   long scratch_floats() const { return kRows * row_floats(); }
 };
-struct BnRows { float *mean, *istd, *scale, *shift, *A, *B, *C; };   // device pointers to a Bn's scratch rows
+struct BnRows {   // device pointers to a Bn's scratch rows
+  float *mean, *istd, *scale, *shift, *A, *B, *C;
+  Affine affine() const { return Affine{scale, shift}; }
+  BnCoef coef() const { return BnCoef{A, B, C}; }
+  BnSide side(const void* y) const { return BnSide{y, affine(), coef()}; }   // the pre-BatchNorm tensor y under these rows
+};
 
 // The kernel routes of one block at the plan's batch size; Net::settle_routes says what each one is.
 struct BlockRoute {
@@ -135,9 +140,6 @@ class Net {
 
  private:
   Plan plan_;
-  // A block's shortcut operand at its join: the shortcut conv's output under its BatchNorm (B.ys, B.bs), or -- identity shortcut
-  // (model.py:40,52) -- the block input itself under a unit BatchNorm (scale 1, shift 0; backward A = 1, B = C = 0)
-  struct Shortcut { const void* y; const float *scale, *shift, *A, *B, *C; };
   // What one entry-point call binds once: the plan, the caller's buffers and the workspace regions every helper needs
   struct Pass {
     const Plan* P; char* base; const float* params; float* grads; float* bnbuf; long long* nbt; int N; bool training;
@@ -153,10 +155,11 @@ class Net {
     char* packed(long slot) const { return base + P->packed + slot * (long)esz; }
     const float* ones() const { return reinterpret_cast<const float*>(base + P->cvec); }
     const float* zeros() const { return ones() + 256; }
-    Shortcut shortcut(const Block& B, const void* xin) const {
-      if (B.identity) return Shortcut{xin, ones(), zeros(), ones(), zeros(), zeros()};
-      const BnRows r = rows(B.bs);
-      return Shortcut{base + B.ys, r.scale, r.shift, r.A, r.B, r.C};
+    // A block's shortcut operand at its join: the shortcut conv's output under its BatchNorm (B.ys, B.bs), or -- identity shortcut
+    // (model.py:40,52) -- the block input itself under a unit BatchNorm (scale 1, shift 0; backward A = 1, B = C = 0)
+    BnSide shortcut(const Block& B, const void* xin) const {
+      if (B.identity) return BnSide{xin, {ones(), zeros()}, {ones(), zeros(), zeros()}};
+      return rows(B.bs).side(base + B.ys);
     }
   };
   // plan(N) + the workspace-size check of every entry point; enqueues nothing
@@ -239,7 +242,7 @@ class Net {
   int bn_relu_backward(const Pass& ps, const Bn& bn, const void* g, const void* y, void* dy, long npix, hipStream_t s, int nparts_ready = 0);
   // Head of a residual block's backward: g, the join's output gradient, feeds bn2 (y2) and the shortcut's BatchNorm (sc): reduce -> both coefficient sets ->
   // apply into dy2 / dys.  g_masked: g already carries the join's ReLU mask (plain sums); nparts_ready as above; dy2 == nullptr: no apply launch.
-  int join_backward(const Pass& ps, const Block& B, const Shortcut& sc, const void* g, bool g_masked, void* dy2, void* dys, hipStream_t s,
+  int join_backward(const Pass& ps, const Block& B, const BnSide& sc, const void* g, bool g_masked, void* dy2, void* dys, hipStream_t s,
                     int nparts_ready = 0);
 };
 

@@ -48,7 +48,7 @@ U = 2.0 ** -24
 SLOP = 1.01                          # second-order terms of the first-order bounds
 EPS = float(np.float32(1e-5))        # the f32 scalars the entry point receives
 MOM = float(np.float32(0.1))
-ELEM_MAX_BLOCKS = 768                # kElemMaxBlocks of csrc/bn_elem.hip
+ELEM_MAX_BLOCKS = 768                # kElemMaxBlocks of csrc/tile_common.hpp
 GUARD = 1 << 16
 PATTERN = 0xA5
 gpu = pytest.mark.gpu

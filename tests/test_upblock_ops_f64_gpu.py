@@ -1,5 +1,5 @@
 """Float64 per-slice parity of the last up-block's fused kernels and the tail conv through the C ABI: mmvae_tail_join_fwd (f32, bf16),
-mmvae_tail_join_fwd_stream, mmvae_tail_join_bwd_reduce / _apply (VALU and MFMA forms of csrc/bn_elem.hip), mmvae_upblock_tail_fwd
+mmvae_tail_join_fwd_stream, mmvae_tail_join_bwd_reduce / _apply (VALU and MFMA forms of csrc/tail_join.hip), mmvae_upblock_tail_fwd
 (up5_tail_fwd_kernel), mmvae_upblock_bwd_fused + mmvae_conv1x1_bwd_fused (csrc/conv_joinbwd.hip) and mmvae_join_conv1x1_fwd
 (csrc/conv_joinfwd.hip), plus the += contract, determinism, the refusal paths and the documented buffer sizes (every output and scratch
 buffer is a window of the documented size inside a pattern-filled allocation: an overrun shows as changed guard bytes).
