@@ -489,7 +489,12 @@ MMVAE_API int mmvae_adam_step_guarded(float* params, const float* grads, float* 
  * scratch: device buffer of at least 2*numel(weight)*sizeof(dtype)+64 bytes for the packed weights.
  * mmvae_conv2d_fwd with weight == NULL reuses the packed weights an earlier call with the same geometry left in `scratch`.
  * pro_scale/pro_shift (per input channel, nullable): x := relu?(x*scale+shift) applied on load (fused BN+ReLU).
- * stats (nullable): per-channel (sum,sumsq) partials [rows][2][Cout]; the call returns `rows`. */
+ * stats (nullable): per-channel (sum,sumsq) partials [rows][2][Cout], taken from the f32 accumulators; the call returns `rows`,
+ * 1 <= rows <= MMVAE_CONV_STATS_MAX_ROWS (the capacity the caller provides); rows past `rows` are not written.
+ * Refused with nothing enqueued and y, stats and scratch untouched: a dtype other than MMVAE_F32 / MMVAE_BF16 (MMVAE_ERR_ARG; the weight
+ * gradient entry points below likewise); k*k > 25, Cin no multiple of the 16-byte vector (8 bf16 / 4 f32 channels), Cout no multiple of 4
+ * (MMVAE_ERR_UNSUPPORTED). */
+#define MMVAE_CONV_STATS_MAX_ROWS 4096
 MMVAE_API int mmvae_conv2d_fwd(int dtype, int transposed, const void* x, const float* weight, void* y, int N, int H, int W, int Cin, int Cout,
                      int k, int stride, int pad, const float* pro_scale, const float* pro_shift, int pro_relu, float* stats,
                      void* scratch, void* stream);
@@ -516,7 +521,11 @@ MMVAE_API int mmvae_conv2d_dgrad_ex(int dtype, int transposed, const void* dy, c
                           int Cout, int k, int stride, int pad, int accumulate, const void* dy2, const float* w2, int C2, void* scratch,
                           void* stream);
 /* dW (f32, weight layout) += ... ; pro_* as in fwd (applied to x).  scratch: MMVAE_WGRAD_SCRATCH_BYTES of device memory
- * (per-block partial images, summed by a second kernel: no atomics, bit-reproducible), owned by the caller. */
+ * (per-block partial images, summed by a second kernel: no atomics, bit-reproducible), owned by the caller.
+ * Refused with nothing enqueued, dW and scratch untouched: a NULL scratch (MMVAE_ERR_ARG); k*k > 25, or Cin or Cout no multiple of the
+ * 16-byte vector (8 bf16 / 4 f32 channels) (MMVAE_ERR_UNSUPPORTED); and, on the fallback kernel (the shapes no other
+ * weight-gradient kernel takes), a weight of Cin*Cout*k*k elements that is no multiple of 256, which the reduce does not take: this needs
+ * a channel count that is no multiple of 16 -- bf16 8 -> 8 1x1, f32 4 -> 4 or 4 -> 16 3x3 (MMVAE_ERR_ARG). */
 #define MMVAE_WGRAD_SCRATCH_BYTES (64u << 20)
 MMVAE_API int mmvae_conv2d_wgrad(int dtype, int transposed, const void* x, const void* dy, float* dweight, int N, int H, int W, int Cin,
                        int Cout, int k, int stride, int pad, const float* pro_scale, const float* pro_shift, int pro_relu,

@@ -423,9 +423,27 @@ static inline ConvGeom geom_for(int transposed, int Cin, int Cout, int k, int s,
 }
 static inline long numel_w(int Cin, int Cout, int k) { return (long)Cin * Cout * k * k; }
 static inline int out_size(int transposed, int H, int k, int s, int p) { return transposed ? (H - 1) * s - 2 * p + k : conv_down_size(H, k, s, p); }
+// Refusals of the single-op conv entry points, asked before anything is enqueued.  The dtype: anything that is not f32 used to run as bf16.
+static_assert(MMVAE_CONV_STATS_MAX_ROWS >= kGatherMaxGridX * kMaxPhases, "statistics rows: one per block and stride phase");
+static int conv_dtype_refused(const char* who, int dt) {
+  if (dt == MMVAE_F32 || dt == MMVAE_BF16) return MMVAE_OK;
+  set_error("%s: dtype=%d unsupported", who, dt);
+  return MMVAE_ERR_ARG;
+}
+// launch_gather_gemm's own conditions, which the forward would otherwise only reach after its packing launch
+static int conv_fwd_refused(int dt, int Cin, int Cout, int k) {
+  if (const int rc = conv_dtype_refused("conv2d_fwd", dt); rc < 0) return rc;
+  const int ve = dt == MMVAE_F32 ? 4 : 8;
+  if (k < 1 || k * k > kMaxTaps) { set_error("conv2d_fwd: k=%d unsupported (at most %d taps)", k, kMaxTaps); return MMVAE_ERR_UNSUPPORTED; }
+  if (Cin < 1 || Cout < 1 || Cin % ve != 0 || Cout % 4 != 0) {
+    set_error("conv2d_fwd: unsupported Cin=%d Cout=%d (Cin a multiple of %d, Cout of 4)", Cin, Cout, ve); return MMVAE_ERR_UNSUPPORTED;
+  }
+  return MMVAE_OK;
+}
 
 int mmvae_conv2d_fwd(int dt, int transposed, const void* x, const float* w, void* y, int N, int H, int W, int Cin, int Cout, int k,
                      int s, int p, const float* ps, const float* pb, int relu, float* stats, void* scratch, void* st) {
+  if (const int rc = conv_fwd_refused(dt, Cin, Cout, k); rc < 0) return rc;
   const ConvGeom g = geom_for(transposed, Cin, Cout, k, s, p);
   const int Ho = out_size(transposed, H, k, s, p), Wo = out_size(transposed, W, k, s, p);
   // weight == NULL: `scratch` still holds the packed weights of an earlier call with the same geometry (pack once, run many)
@@ -504,6 +522,7 @@ int mmvae_conv2d_wgrad(int dt, int transposed, const void* x, const void* dy, fl
   const ConvGeom g = geom_for(transposed, Cin, Cout, k, s, p);
   const int Ho = out_size(transposed, H, k, s, p), Wo = out_size(transposed, W, k, s, p);
   if (!scratch) { set_error("conv2d_wgrad: scratch (MMVAE_WGRAD_SCRATCH_BYTES) required"); return MMVAE_ERR_ARG; }
+  if (const int rc = conv_dtype_refused("conv2d_wgrad", dt); rc < 0) return rc;
   static_assert(MMVAE_WGRAD_SCRATCH_BYTES == kWgradScratchBytes, "public scratch size out of sync");
   float* sc = static_cast<float*>(scratch);
   if (!transposed) return op_run_wgrad(dt, g, N, dy, Ho, Wo, nullptr, nullptr, 0, x, H, W, ps, pb, relu, dw, stream_of(st), sc);
@@ -512,6 +531,7 @@ int mmvae_conv2d_wgrad(int dt, int transposed, const void* x, const void* dy, fl
 int mmvae_conv2d_wgrad_pair(int dt, const void* x, const void* dy, const void* dy_sc, float* dw, float* dw_sc, int N, int H, int W, int Cin, int Cout,
                             const float* ps, const float* pb, int relu, void* scratch, void* st) {
   if (!scratch || !x || !dy || !dy_sc || !dw || !dw_sc || N < 1) { set_error("conv2d_wgrad_pair: bad argument"); return MMVAE_ERR_ARG; }
+  if (const int rc = conv_dtype_refused("conv2d_wgrad_pair", dt); rc < 0) return rc;
   const ConvGeom g = geom_for(0, Cin, Cout, 3, 2, 1), gs = geom_for(0, Cin, Cout, 1, 2, 0);
   const int Ho = out_size(0, H, 3, 2, 1), Wo = out_size(0, W, 3, 2, 1);
   const int rc = op_run_wgrad_pair(dt, g, gs, N, dy, dy_sc, Ho, Wo, x, H, W, ps, pb, relu, dw, dw_sc, stream_of(st), static_cast<float*>(scratch), 1.f, 1.f);
@@ -524,6 +544,7 @@ int mmvae_convT_bwd_fused(int dt, const void* x, const void* dy, const float* w,
   const ConvGeom g = geom_for(1, Cin, Cout, k, s, p);
   const int Ho = out_size(1, H, k, s, p), Wo = out_size(1, W, k, s, p);
   if (!scratch || !wscratch) { set_error("convT_bwd_fused: scratch buffers required"); return MMVAE_ERR_ARG; }
+  if (const int rc = conv_dtype_refused("convT_bwd_fused", dt); rc < 0) return rc;
   if (!op_bwd_fusable(dt, g, N, H, W, Ho, Wo)) { set_error("convT_bwd_fused: shape not supported (bf16, 16 / 32 -> 16 channels, k4 s2 p1, 32x32 -> 64x64 or 16x16 -> 32x32)"); return MMVAE_ERR_UNSUPPORTED; }
   char* sc = static_cast<char*>(scratch);
   int rc = op_pack_down(dt, g, w, sc, stream_of(st)); if (rc < 0) return rc;

@@ -860,13 +860,16 @@ int launch_wgrad(int dt, WgradArgs a, hipStream_t s) {
   a.pix_per_block = (int)(steps_per * PK);
   const int gx = (int)(((long)a.M + a.pix_per_block - 1) / a.pix_per_block);
   dim3 grid(gx, tiles, zg), block(256);
-  if (dt == DT_F32) hipLaunchKernelGGL((wgrad_kernel<float>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((wgrad_kernel<bf16_t>), grid, block, 0, s, a);
-  MM_CHECK_RC(check_launch("wgrad"));
   WgradReduceArgs u; memset(&u, 0, sizeof(u));
   u.part = a.scratch; u.dW = a.dW; u.Ca = a.Ca; u.Cb = a.Cb; u.ntaps = a.ntaps; u.nparts = gx;
   u.Ca_valid = a.Ca_valid; u.Cb_valid = a.Cb_valid; u.sA = a.sA; u.sB = a.sB; u.scale = a.scale;
   for (int t = 0; t < 25; ++t) u.tap_off[t] = a.tap_off[t];
+  // the reduce's refusals (an image that is no multiple of 256 elements: bf16 8 -> 8 1x1, f32 4 -> 4) come before the first launch, like
+  // every other refusal of this path: nothing is enqueued and the scratch stays as it was
+  if (const int rcr = wgrad_reduce_check(u); rcr < 0) { note_launch_bytes(0.0); return rcr; }     // (no launch will take the bytes noted above)
+  if (dt == DT_F32) hipLaunchKernelGGL((wgrad_kernel<float>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((wgrad_kernel<bf16_t>), grid, block, 0, s, a);
+  MM_CHECK_RC(check_launch("wgrad"));
   return launch_wgrad_reduce(u, s);
 }
 

@@ -91,8 +91,9 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(WgradReduceArgs a) {
   }
 }
 
-int launch_wgrad_reduce(WgradReduceArgs a, hipStream_t s) {
-  if (a.nparts < 1) return MMVAE_OK;
+// The reduce's own refusals, without a launch: a caller whose kernel writes the partial images asks BEFORE it enqueues that kernel, so that
+// a refused call has enqueued nothing.  `a` is normalised in place (shared destinations folded into the part axis, part_stride filled in).
+static int wgrad_reduce_prepare(WgradReduceArgs& a) {
   // taps that share a destination become extra parts of a one-tap image (all of them must then share it)
   bool distinct = true;
   for (int t = 0; t < a.ntaps && distinct; ++t)
@@ -106,6 +107,15 @@ int launch_wgrad_reduce(WgradReduceArgs a, hipStream_t s) {
   }
   const long wsize = (long)a.ntaps * a.Ca * a.Cb;
   if (wsize % 256) { set_error("wgrad_reduce: %ld elements not a multiple of 256", wsize); return MMVAE_ERR_ARG; }
+  return MMVAE_OK;
+}
+int wgrad_reduce_check(WgradReduceArgs a) { return wgrad_reduce_prepare(a); }
+
+int launch_wgrad_reduce(WgradReduceArgs a, hipStream_t s) {
+  if (a.nparts < 1) return MMVAE_OK;
+  const int rcp = wgrad_reduce_prepare(a);
+  if (rcp < 0) return rcp;
+  const long wsize = (long)a.ntaps * a.Ca * a.Cb;
   a.exclusive = 1;
   note_launch_bytes((double)a.nparts * a.part_stride * 4.0);
   // elements per block: 256 .. 32 (whole 128-byte lines per part), aiming at >= 256 blocks

@@ -144,6 +144,7 @@ int launch_gather3(int dt, int out_dt, const GatherArgs& a, int gx, hipStream_t 
 struct WgradReduceArgs { const float* part; float* dW; int Ca, Cb, ntaps, nparts, Ca_valid, Cb_valid, sA, sB; int tap_off[25]; float scale; int exclusive;
                          long part_stride; /* floats between two partial images (0: ntaps * Ca * Cb) */ };
 int launch_wgrad_reduce(WgradReduceArgs a, hipStream_t s);
+int wgrad_reduce_check(WgradReduceArgs a);        // launch_wgrad_reduce's refusals alone (< 0), nothing enqueued: asked before the producing kernel is
 constexpr size_t kWgradScratchBytes = 64u << 20;   // capacity of the partial-image scratch every wgrad caller provides
 // ---- pipelined all-phases patch kernel (conv_patch.hip)
 struct PatchPhase { int ph, pw, Hq, Wq, ntaps, tap0; long w_off; int w_vec0, koff0; };
