@@ -406,6 +406,32 @@ MMVAE_API int mmvae_scatter_panel(const float* pts, int64_t n, int stride, int c
 MMVAE_API int mmvae_latent_stats(const float* mu, const float* logvar, const float* enc, int N, int d, int accumulate, double* acc,
                                  void* stream);
 
+/* ------------------------------------------------------------------ aggregate-posterior densities (ELBO surgery, Hoffman & Johnson 2016)
+ * N samples z [N][d] against a bank of M diagonal Gaussian posteriors mu, logvar [M][d] (dense f32 device arrays):
+ *   t_ijd = -0.5 * ((z_id - mu_jd)^2 * exp(-logvar_jd) + logvar_jd + log(2 pi)),      s_ij = sum_d t_ijd,
+ *   log_qz[i]         = logsumexp_j s_ij  - log M        f64 [N]     (log of the aggregate posterior q(z) = mean_j q(z | x_j) at z_i)
+ *   log_qz_dims[i][d] = logsumexp_j t_ijd - log M        f64 [N][d]  (log of its d-th marginal), skipped when log_qz_dims is NULL.
+ * Every maximum is subtracted before any exponential is taken (an online log-sum-exp over groups of 8 bank rows).
+ * Precision: the terms are formed in f32 from the f32 inputs (exp(-logvar) and the additive constant of a bank entry are formed in f64
+ * and rounded once to f32; the arithmetic runs in the base-2 domain).  Sums of exponentials are f32 over the 8 rows of a group only and
+ * f64 from there on; the joint's sum over d is f32 inside a tile of at most 32 dimensions and f64 across tiles.  The outputs are f64.
+ * Outputs and determinism: every element of log_qz (and of log_qz_dims) is written, nothing is accumulated into what was there.  The bank
+ * is cut into chunks of rows by a rule that depends on (N, M, d) alone; the (max, sum) pairs of the chunks go through `scratch` and are
+ * combined in chunk order in f64; with a single chunk the sweep writes the output itself by the same formula.  No atomics: the same bits
+ * every run.  Every scratch word that is read was written earlier by the same call, so the scratch may hold anything on entry.  No
+ * allocation, no host read, no synchronisation: a handful of launches on `stream`, capturable.  log_qz has the same bits whether or not
+ * log_qz_dims is asked for.
+ * scratch: 16-byte aligned device memory of at least mmvae_posterior_mixture_scratch_bytes(N, M, d) bytes (a function of the shape
+ * alone, 0 for a shape the call refuses): the re-laid bank (12 bytes per bank entry), the padded samples and the chunk pairs.
+ * Ranges: 1 <= d <= 512, 1 <= N, M <= 2^20; above them MMVAE_ERR_UNSUPPORTED.  A non-positive N, M or d, a NULL pointer (log_qz_dims may
+ * be NULL), a misaligned or too-small scratch: MMVAE_ERR_ARG.  Nothing is enqueued on an error.
+ * Domain: |z|, |mu| <= 1e4 and |logvar| <= 30.  Inside it every term is finite in f32 (at most about 4e21 in magnitude), the running
+ * maximum is finite and no NaN appears.  Outside it (and for non-finite inputs) the output values are unspecified; nothing is written
+ * out of bounds. */
+MMVAE_API size_t mmvae_posterior_mixture_scratch_bytes(int N, int M, int d);
+MMVAE_API int mmvae_posterior_mixture(const float* z, int N, const float* mu, const float* logvar, int M, int d, double* log_qz,
+                                      double* log_qz_dims, void* scratch, size_t scratch_bytes, void* stream);
+
 /* ------------------------------------------------------------------ nearest training frames of a sample (memorised or drawn?)
  * Exact k nearest neighbours of M query planes among F resident frames.  queries [M][D], frames [F][D]: dense device uint8, 16-byte
  * aligned.  d(m, f) = sum_{i<D} (queries[m][i] - t(frames[f][i]))^2 with t the identity when lut is NULL and lut[.] (256 device bytes)

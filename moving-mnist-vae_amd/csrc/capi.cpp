@@ -369,6 +369,12 @@ int mmvae_scatter_panel(const float* pts, int64_t n, int stride, int col_x, int 
 int mmvae_latent_stats(const float* mu, const float* logvar, const float* enc, int N, int d, int accumulate, double* acc, void* st) {
   return launch_latent_stats(mu, logvar, enc, N, d, accumulate, acc, stream_of(st));
 }
+// ---- aggregate-posterior densities (arguments are checked in the launcher)
+size_t mmvae_posterior_mixture_scratch_bytes(int N, int M, int d) { return posterior_mixture_scratch_bytes(N, M, d); }
+int mmvae_posterior_mixture(const float* z, int N, const float* mu, const float* logvar, int M, int d, double* log_qz, double* log_qz_dims,
+                            void* scratch, size_t scratch_bytes, void* st) {
+  return launch_posterior_mixture(z, N, mu, logvar, M, d, log_qz, log_qz_dims, scratch, scratch_bytes, stream_of(st));
+}
 // ---- nearest training frames (arguments are checked in the launcher)
 size_t mmvae_nearest_frames_scratch_bytes(int M, int64_t F, int D, int k) { return nearest_frames_scratch_bytes(M, (long)F, D, k); }
 int mmvae_nearest_frames(const uint8_t* queries, int M, const uint8_t* frames, int64_t F, int D, const uint8_t* lut, int k, int32_t* out_dist,

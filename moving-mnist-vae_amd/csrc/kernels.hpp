@@ -438,6 +438,12 @@ int launch_frame_quality(const mmvae_panel_col* a, const mmvae_panel_col* b, int
 int launch_scatter_panel(const float* pts, long n, int stride, int col_x, int col_y, const float* xform, int side, int radius16,
                          const unsigned char* tone, unsigned char* out, long out_row_stride, hipStream_t s);
 int launch_latent_stats(const float* mu, const float* logvar, const float* enc, int N, int d, int accumulate, double* acc, hipStream_t s);
+// aggregate-posterior densities (posterior_mixture.hip): log_qz[N] and (nullable) log_qz_dims[N][d] f64 = logsumexp over the M bank
+// posteriors (mu, logvar [M][d]) of the joint / per-dimension Gaussian log-density of z [N][d], minus log M.  The scratch size is a
+// function of the shape alone (0 for a shape the launcher refuses); both check their arguments before anything is enqueued.
+size_t posterior_mixture_scratch_bytes(int N, int M, int d);
+int launch_posterior_mixture(const float* z, int N, const float* mu, const float* logvar, int M, int d, double* log_qz, double* log_qz_dims,
+                             void* scratch, size_t scratch_bytes, hipStream_t s);
 // exact k nearest frames of M uint8 query planes among F frames of D bytes (neighbours.hip): squared distances in integers, ties to the
 // lower frame index, lut (nullable, 256 device bytes) applied to the frames only.  The scratch size is a function of the shape alone
 // (0 for a shape the launcher refuses); both check their arguments before anything is enqueued.

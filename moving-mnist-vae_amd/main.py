@@ -4,7 +4,8 @@ Mirrors the loop body of the reference ``main.py:362-429`` (normalise ->
 forward -> loss -> bookkeeping -> zero_grad / backward / step) so that a user
 of the reference can swap ``from main import train`` for this one.  Around the
 loop: held-out evaluation (``evaluate``, ``latent_stats``; the per-frame MSE /
-PSNR / SSIM behind ``evaluate(quality=True)`` live in ``quality.py``), the model-name
+PSNR / SSIM behind ``evaluate(quality=True)`` live in ``quality.py``, the ELBO split
+behind ``evaluate(decomposition=True)`` in ``decomposition.py``), the model-name
 grammar (``select_model``), the reference's samplers (``generate*``) and its
 checkpoint format.  The plotting branch (``main.py:401-424``) hangs off
 ``args.plot_callback``: ``make_plot_callback`` in ``panels.py`` returns one, and
@@ -34,6 +35,7 @@ import torch
 from .data import (KMEANS_FILE_NOTE, GeneratedClips, MovingMNISTClips, QuantiserFit, choose_transformer, clips_from_npz_array,  # noqa: F401
                    fit_quantiser, generate_batch, generate_clips, load_idx_images, load_kmeans_file, nearest_frames, pixel_histogram,
                    quantise_frames, resize_frames, resize_quantise_frames, save_kmeans_file, save_moving_mnist_files, velocity_table)
+from .decomposition import _decompose, decomposition_to_host, elbo_decomposition, posterior_mixture  # noqa: F401
 from .model import VAE
 from .monitor import TensorHistograms, make_histogram_callback, tensor_histograms  # noqa: F401
 from .panels import (column, gray_lut, latent_slide, make_plot_callback, neighbour_sheet, plot_neighbours, plot_pixelcnn, plot_pixelvae,  # noqa: F401
@@ -112,7 +114,7 @@ def train(model, data_loader, optimizer, device, args, epoch=0, data_mean=0, dat
 
 
 def evaluate(model, data_loader, device, args, data_mean=0, data_std=1, iw_samples=0, weighted=False, generator=None,
-             return_per_image=False, latent_stats=False, quality=False, centres=None) -> dict:
+             return_per_image=False, latent_stats=False, quality=False, centres=None, decomposition=False) -> dict:
     """Held-out evaluation of the HIP model (the reference builds a test loader, main.py:497, and never reads it): one eval-mode pass
     over ``data_loader`` under ``torch.no_grad()``; the model's train / eval mode is restored afterwards and no parameter or buffer
     changes.  Batches are prepared as in ``train``.  Per-image terms come from ``model.per_image_terms`` (and ``model.iw_bound``
@@ -135,10 +137,21 @@ def evaluate(model, data_loader, device, args, data_mean=0, data_std=1, iw_sampl
     ``quality=True`` adds ``quality``: {'mse', 'psnr', 'ssim'} of the reconstruction against the input as 8-bit pictures
     (``reconstruction_quality`` on every batch, ``centres`` the k-means centres of its grey table): ``mse`` and ``ssim`` are means per
     image, ``psnr = 10 log10(65025 / mean mse)``.  The sums join the f64 device sums above and come back in the same single copy;
-    ``per_image`` gains 'mse' and 'ssim'.  Needs 11 <= input_image_size <= 64.  Without the flag nothing changes, keys or bits."""
+    ``per_image`` gains 'mse' and 'ssim'.  Needs 11 <= input_image_size <= 64.  Without the flag nothing changes, keys or bits.
+    ``decomposition=True`` adds ``decomposition``: the split of the averaged KL term over this data set (``elbo_decomposition``, which
+    see for the keys: ``mi``, ``tc``, ``dwkl``, ``marginal_kl``, ``kl_sampled``, ``kl_analytic``, ``log_m`` as floats, ``dwkl_per_dim``
+    as a numpy array, the counts ``n`` = ``m`` = ``n_images``).  Every batch's ``mu``, ``logvar`` and ``encoding`` are kept on the device
+    as f32 (3 * 4 * n_images * z bytes), one ``elbo_decomposition`` call follows the loop and its result comes back in one more
+    device-to-host copy; ``per_image`` gains 'log_qz'.  Known limits: ``mi <= log_m`` by construction (each sample's own posterior is in
+    the bank), so a value near ``log_m`` means saturated, not measured; all figures are Monte-Carlo estimates from one sample per image.
+    A PixelCNN on its own has ``decomposition`` None; a model built with ``require_rsample=False`` has no q(z|x) density and raises
+    ValueError, as ``iw_bound`` does.  Without the flag nothing changes, keys or bits."""
     if not hasattr(model, "per_image_terms"):
         raise TypeError("evaluate() drives the HIP VAE of this package (it needs model.per_image_terms)")
     latent = not model.only_pixelcnn
+    want_dec = bool(decomposition) and latent
+    if want_dec and not model.require_rsample:
+        raise ValueError("evaluate(decomposition=True) needs q(z|x): the model was built with require_rsample=False")
     categorical = VAE.is_categorical(model)
     weight = getattr(args, "data_ratio_of_labels", None) if (weighted and categorical) else None
     was_training = bool(model.training)
@@ -147,6 +160,7 @@ def evaluate(model, data_loader, device, args, data_mean=0, data_std=1, iw_sampl
     kept = {"nll": [], "kl": [], "iw_bound": []}
     if quality:
         kept.update(mse=[], ssim=[])
+    bank = ([], [], [])                            # mu, logvar, encoding of every batch (f32, on the device), with `decomposition`
     n_images = 0
     model.eval()
     try:
@@ -167,6 +181,9 @@ def evaluate(model, data_loader, device, args, data_mean=0, data_std=1, iw_sampl
                 nll, kl = model.per_image_terms(target, mu, logvar, reconstruction, weight=weight)
                 if want_latent:
                     acc, have_lv = _latent_stats_into(model, mu, logvar, encoding, acc), logvar is not None
+                if want_dec:
+                    for rows, t in zip(bank, (mu, logvar, encoding)):
+                        rows.append(t.detach().reshape(N, -1).float().clone())
                 iw = model.iw_bound(image, target, iw_samples, generator=generator, weight=weight) if iw_samples else None
                 if sums is None:
                     sums = torch.zeros(5 if quality else 3, dtype=torch.float64, device=nll.device)
@@ -214,6 +231,15 @@ def evaluate(model, data_loader, device, args, data_mean=0, data_std=1, iw_sampl
         out["per_image"] = {k: (torch.cat(v) if v else None) for k, v in kept.items()}
     if latent_stats:
         out["latent"] = latent_out
+    if decomposition:
+        out["decomposition"] = None
+        if want_dec:
+            dec, log_qz = _decompose(*(torch.cat(rows) for rows in bank), None, "evaluate(decomposition=True)")
+            out["decomposition"] = decomposition_to_host(dec)
+            if return_per_image:
+                out["per_image"]["log_qz"] = log_qz
+        elif return_per_image:
+            out["per_image"]["log_qz"] = None
     return out
 
 
