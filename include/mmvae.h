@@ -562,6 +562,35 @@ MMVAE_API int mmvae_conv2d_wgrad(int dtype, int transposed, const void* x, const
 MMVAE_API int mmvae_conv2d_wgrad_pair(int dtype, const void* x, const void* dy, const void* dy_shortcut, float* dweight, float* dweight_sc, int N,
                             int H, int W, int Cin, int Cout, const float* pro_scale, const float* pro_shift, int pro_relu, void* scratch,
                             void* stream);
+/* The forward sibling of mmvae_conv2d_wgrad_pair: a residual block's conv1 (Conv2d 3x3 stride 2 pad 1) AND its 1x1 stride-2 shortcut conv from ONE
+ * read of their common input x (what encoder.layer1 runs in a bf16 64x64 step: conv3_stream_kernel with the shortcut's second weight set,
+ * second output and second statistics rows).  bf16, 32 -> 32 channels, 32x32 -> 16x16.
+ *   y [N,16,16,32] = conv3x3(pro(x), weight (32,32,3,3)), y_sc [N,16,16,32] = conv1x1(pro(x), weight_sc (32,32,1,1)); pro_* as in mmvae_conv2d_fwd
+ *   (pro_scale and pro_shift both or neither);
+ *   stats, stats_sc (nullable): per-channel (sum, sumsq) partials [rows][2][32] of y and of y_sc, taken from the f32 accumulators.  The call
+ *   returns `rows`, 1 <= rows <= MMVAE_FWD_PAIR_MAX_ROWS (the capacity the caller provides for each); a block without work writes a row of zeros;
+ *   rows past `rows` are not written.
+ * scratch: MMVAE_FWD_PAIR_SCRATCH_BYTES for the packed weights ([cout][tap][cin], then [cout][cin]).
+ * Refused with nothing enqueued and y, y_sc, both statistics tensors and scratch untouched: a dtype other than MMVAE_F32 / MMVAE_BF16, a null
+ * x / weight / weight_sc / y / y_sc / scratch, pro_scale without pro_shift, N < 1 (MMVAE_ERR_ARG); f32 or any other shape (MMVAE_ERR_UNSUPPORTED). */
+#define MMVAE_FWD_PAIR_MAX_ROWS 512
+#define MMVAE_FWD_PAIR_SCRATCH_BYTES 20480u
+MMVAE_API int mmvae_conv2d_fwd_pair(int dtype, const void* x, const float* weight, const float* weight_sc, void* y, void* y_sc, int N, int H, int W,
+                          int Cin, int Cout, const float* pro_scale, const float* pro_shift, int pro_relu, float* stats, float* stats_sc,
+                          void* scratch, void* stream);
+/* The data gradient of a Conv2d (32,32,3,3) stride 1 pad 1 on 16x16 maps WITH the backward sums of the BatchNorm + ReLU in front of that conv
+ * from the same pass (encoder.layer1.conv2's data gradient and bn1's reduce in a bf16 64x64 step):
+ *   dx [N,16,16,32] = dgrad(dy [N,16,16,32]), bit for bit mmvae_conv2d_dgrad's on this shape;
+ *   sums [rows][2][32] = partial rows of (sum g, sum g * y_pre) per channel, g = dx AS STORED (the bf16-rounded value) where
+ *   y_pre * bn_scale + bn_shift > 0 and 0 elsewhere; y_pre [N,16,16,32] is that BatchNorm's input, (bn_scale, bn_shift) its forward coefficients.
+ * Returns `rows`, 1 <= rows <= MMVAE_DGRAD_BN_SUMS_MAX_ROWS (the caller's capacity); a block without work writes a row of zeros; rows past
+ * `rows` are not written.  scratch: MMVAE_DGRAD_BN_SUMS_SCRATCH_BYTES (the weights packed [cin][flipped tap][cout]).
+ * Refused with nothing enqueued and dx, sums and scratch untouched: a dtype other than MMVAE_F32 / MMVAE_BF16, any null pointer, N < 1
+ * (MMVAE_ERR_ARG); f32 or H != 16 (MMVAE_ERR_UNSUPPORTED). */
+#define MMVAE_DGRAD_BN_SUMS_MAX_ROWS 768
+#define MMVAE_DGRAD_BN_SUMS_SCRATCH_BYTES 18432u
+MMVAE_API int mmvae_conv2d_dgrad_bn_sums(int dtype, const void* dy, const float* weight, void* dx, const void* y_pre, const float* bn_scale,
+                               const float* bn_shift, float* sums, int N, int H, void* scratch, void* stream);
 /* ---- BatchNorm2d in training mode and the 1-channel stem, op level (what a maintainer binds instead of torch.nn.BatchNorm2d,
  * model.py:14,20,30,95,..., and of encoder.conv1 + encoder.bn1, model.py:94-95,103)
  * Tensors are NHWC [npix][C] of `dtype`; statistics, parameters and their gradients are f32.
@@ -589,6 +618,18 @@ MMVAE_API int mmvae_stem_fwd(int dtype, const void* x, const float* weight, void
 MMVAE_API int mmvae_stem_bwd(int dtype, const void* g, const void* y0, const void* x, const float* weight, const float* gamma,
                    const float* bn_scale, const float* bn_shift, const float* save_mean, const float* save_istd, float* dweight,
                    float* dgamma, float* dbeta, int N, int S, void* scratch, void* stream);
+/* mmvae_stem_bwd with the incoming gradient never stored: g is recomputed row by row as the data gradient of encoder.layer1's conv1 (Conv2d
+ * (32,32,3,3) stride 2 pad 1) plus its 1x1 stride-2 shortcut (32,32,1,1) from their output gradients dy1, dys [N,16,16,32] -- both in one f32
+ * accumulator, rounded to bf16 once -- and then treated exactly as mmvae_stem_bwd treats a stored g (what a bf16 64x64 step runs).
+ * bf16, S = 64.  The same chain (patch gram, the backward pass, the finalize), the same outputs (dweight +=, dgamma +=, dbeta +=; dgamma and
+ * dbeta nullable) and the same scratch carve of MMVAE_BN_SCRATCH_BYTES; its last MMVAE_STEM_DG_PACK_BYTES hold the two packed weights.
+ * Refused with nothing enqueued, outputs and scratch untouched: a dtype other than MMVAE_F32 / MMVAE_BF16, a null operand (gamma, dgamma, dbeta
+ * excepted), N < 1 (MMVAE_ERR_ARG); f32 or S != 64 (MMVAE_ERR_UNSUPPORTED). */
+#define MMVAE_STEM_DG_PACK_BYTES 32768u
+MMVAE_API int mmvae_stem_bwd_dg(int dtype, const void* dy1, const void* dys, const float* weight_c1, const float* weight_sc, const void* y0,
+                      const void* x, const float* weight, const float* gamma, const float* bn_scale, const float* bn_shift,
+                      const float* save_mean, const float* save_istd, float* dweight, float* dgamma, float* dbeta, int N, int S, void* scratch,
+                      void* stream);
 /* ConvTranspose2d backward in one pass over dy (bf16; Cin = 16 or 32, Cout = 16, k4 s2 p1, 32x32 -> 64x64 or 16x16 -> 32x32; else
  * MMVAE_ERR_UNSUPPORTED):
  * dweight (Cin,Cout,4,4) += , dx [N,H,W,Cin] = d(loss)/dx  (+ x2 (x) w2: x2 [N,H,W,16], w2 f32 (Cin,16,1,1), both nullable).

@@ -471,14 +471,19 @@ int mmvae_conv2d_fwd(int dt, int transposed, const void* x, const float* w, void
   if (w) { int rc = op_pack_up(dt, g, w, scratch, stream_of(st), 1.f, 0, q.wfrag); if (rc < 0) return rc; }
   return op_run_up(dt, g, scratch, N, x, H, W, y, Ho, Wo, ps, pb, relu, stats, 0, stream_of(st), q);
 }
+// A 3x3 Conv2d weight (Cout,Cin,3,3) packed [cin][flipped tap][cout]: its stride-1 data gradient is then a forward conv over dy
+// (dx[n,h,w,ci] = sum_{kh,kw,co} dy[n, h+1-kh, w+1-kw, co] W[co][ci][kh][kw], tap' = 8 - tap), as Net::packs_enc_bwd packs encoder.layer1.conv2
+static int pack_flipped3(int dt, const float* w, void* dst, int Cin, int Cout, hipStream_t s) {
+  PackArgs pf; std::memset(&pf, 0, sizeof(pf));
+  pf.src = w; pf.dst = dst; pf.cols = Cin; pf.K = Cout; pf.ntaps = 9; pf.s_col = 9; pf.s_k = Cin * 9; pf.scale = 1.f;
+  for (int t = 0; t < 9; ++t) pf.tap_off[t] = 8 - t;
+  return launch_pack(dt, pf, s);
+}
 int mmvae_conv2d_dgrad(int dt, int transposed, const void* dy, const float* w, void* dx, int N, int H, int W, int Cin, int Cout, int k,
                        int s, int p, void* scratch, void* st) {
   if (!transposed && s == 1 && conv3_stream_ok(dt, Cin, Cout, k, s, p, H, W)) {
     // encoder.layer1.conv2's shape: the data gradient as a forward conv over dy with the weights packed [cin][flipped tap][cout]
-    PackArgs pf; std::memset(&pf, 0, sizeof(pf));
-    pf.src = w; pf.dst = scratch; pf.cols = Cin; pf.K = Cout; pf.ntaps = 9; pf.s_col = 9; pf.s_k = Cin * 9; pf.scale = 1.f;
-    for (int t = 0; t < 9; ++t) pf.tap_off[t] = 8 - t;
-    int rc = launch_pack(dt, pf, stream_of(st)); if (rc < 0) return rc;
+    int rc = pack_flipped3(dt, w, scratch, Cin, Cout, stream_of(st)); if (rc < 0) return rc;
     rc = launch_conv3_stream(dt, 1, dy, scratch, nullptr, dx, nullptr, nullptr, nullptr, 0, nullptr, nullptr, N, H, stream_of(st));
     return rc < 0 ? rc : MMVAE_OK;
   }
@@ -543,6 +548,36 @@ int mmvae_conv2d_wgrad_pair(int dt, const void* x, const void* dy, const void* d
   const int rc = op_run_wgrad_pair(dt, g, gs, N, dy, dy_sc, Ho, Wo, x, H, W, ps, pb, relu, dw, dw_sc, stream_of(st), static_cast<float*>(scratch), 1.f, 1.f);
   if (rc == 0) { set_error("conv2d_wgrad_pair: shape not supported (bf16, 32 -> 32 channels, 32x32 -> 16x16)"); return MMVAE_ERR_UNSUPPORTED; }
   return rc < 0 ? rc : MMVAE_OK;
+}
+// ---- the encoder-entry kernels of a bf16 64x64 training step, each as the launches Net::encoder_fwd / Net::encoder_bwd make around
+// encoder.layer1.  Every refusal returns before anything is enqueued (the packing launches included).
+static_assert(MMVAE_FWD_PAIR_SCRATCH_BYTES >= (32 * 9 * 32 + 32 * 32) * 2, "pair scratch: the [cout][tap][cin] and the [32][32] pack");
+static_assert(MMVAE_DGRAD_BN_SUMS_SCRATCH_BYTES >= 32 * 9 * 32 * 2, "dgrad scratch: the [cin][flipped tap][cout] pack");
+int mmvae_conv2d_fwd_pair(int dt, const void* x, const float* w, const float* w_sc, void* y, void* y_sc, int N, int H, int W, int Cin, int Cout,
+                          const float* ps, const float* pb, int relu, float* stats, float* stats_sc, void* scratch, void* st) {
+  if (const int rc = conv_dtype_refused("conv2d_fwd_pair", dt); rc < 0) return rc;
+  if (!x || !w || !w_sc || !y || !y_sc || !scratch || N < 1 || (ps != nullptr) != (pb != nullptr)) {
+    set_error("conv2d_fwd_pair: bad argument (x, both weights, both outputs and scratch required; pro_scale and pro_shift go together)");
+    return MMVAE_ERR_ARG;
+  }
+  if (!conv3_stream_ok(dt, Cin, Cout, 3, 2, 1, H, W)) {
+    set_error("conv2d_fwd_pair: shape not supported (bf16, 32 -> 32 channels, 32x32 -> 16x16)"); return MMVAE_ERR_UNSUPPORTED;
+  }
+  char* sc = static_cast<char*>(scratch);
+  void* wsp = sc + (size_t)32 * 9 * 32 * dtype_size(dt);
+  int rc = op_pack_down(dt, geom_for(0, Cin, Cout, 3, 2, 1), w, sc, stream_of(st)); if (rc < 0) return rc;
+  rc = op_pack_down(dt, geom_for(0, Cin, Cout, 1, 2, 0), w_sc, wsp, stream_of(st)); if (rc < 0) return rc;
+  return launch_conv3_stream(dt, 2, x, sc, wsp, y, y_sc, ps, pb, relu, stats, stats_sc, N, H / 2, stream_of(st));
+}
+int mmvae_conv2d_dgrad_bn_sums(int dt, const void* dy, const float* w, void* dx, const void* y_pre, const float* bn_scale, const float* bn_shift,
+                               float* sums, int N, int H, void* scratch, void* st) {
+  if (const int rc = conv_dtype_refused("conv2d_dgrad_bn_sums", dt); rc < 0) return rc;
+  if (!dy || !w || !dx || !y_pre || !bn_scale || !bn_shift || !sums || !scratch || N < 1) {
+    set_error("conv2d_dgrad_bn_sums: bad argument (every operand and scratch required, N >= 1)"); return MMVAE_ERR_ARG;
+  }
+  if (dt != MMVAE_BF16 || H != 16) { set_error("conv2d_dgrad_bn_sums: shape not supported (bf16, 32 -> 32 channels, 16x16 maps)"); return MMVAE_ERR_UNSUPPORTED; }
+  int rc = pack_flipped3(dt, w, scratch, 32, 32, stream_of(st)); if (rc < 0) return rc;
+  return launch_conv3_stream_bwd(dt, dy, scratch, dx, y_pre, bn_scale, bn_shift, sums, N, H, stream_of(st));
 }
 int mmvae_convT_bwd_fused(int dt, const void* x, const void* dy, const float* w, float* dw, void* dx, int N, int H, int W, int Cin, int Cout, int k,
                           int s, int p, const float* ps, const float* pb, int relu, const void* x2, const float* w2, float* dw2, void* scratch,
@@ -633,6 +668,34 @@ int mmvae_stem_bwd(int dt, const void* g, const void* y0, const void* x, const f
   int rc = launch_stem_gram(dt, x, gram, gram_floats, R, N, Sz, H1, H1, stream_of(st));
   if (rc < 0) return rc;
   const int np = launch_stem_bwd(dt, g, y0, x, bn_scale, bn_shift, part, part_floats, N, Sz, H1, H1, stream_of(st));
+  if (np < 0) return np;
+  return launch_stem_bwd_finalize(part, np, R, w, nullptr, (double)N * H1 * H1, gamma, save_mean, save_istd, dgamma, dbeta, dw, stream_of(st));
+}
+// mmvae_stem_bwd's chain with the incoming gradient recomputed from encoder.layer1's dy tensors (launch_stem_bwd_dg): the same carve, the two
+// transposed-form weight packs (op_pack_up, no fragment order: what Net::packs_enc_bwd leaves for this kernel) in the scratch's last 32 KB
+static_assert(MMVAE_STEM_DG_PACK_BYTES >= (32 * 9 * 32 + 32 * 32) * 2 && MMVAE_STEM_DG_PACK_BYTES % 256 == 0, "stem DG packs");
+int mmvae_stem_bwd_dg(int dt, const void* dy1, const void* dys, const float* w_c1, const float* w_sc, const void* y0, const void* x, const float* w,
+                      const float* gamma, const float* bn_scale, const float* bn_shift, const float* save_mean, const float* save_istd, float* dw,
+                      float* dgamma, float* dbeta, int N, int Sz, void* scratch, void* st) {
+  if (const int rc = conv_dtype_refused("stem_bwd_dg", dt); rc < 0) return rc;
+  if (!dy1 || !dys || !w_c1 || !w_sc || !y0 || !x || !w || !bn_scale || !bn_shift || !save_mean || !save_istd || !dw || !scratch || N < 1) {
+    set_error("stem_bwd_dg: bad argument (every operand but gamma, dgamma, dbeta required; N >= 1)"); return MMVAE_ERR_ARG;
+  }
+  if (!stem_bwd_dg_ok(dt, Sz)) { set_error("stem_bwd_dg: bf16 and image size 64 only (dtype=%d, S=%d)", dt, Sz); return MMVAE_ERR_UNSUPPORTED; }
+  const int H1 = Sz / 2;
+  double* R = static_cast<double*>(scratch);
+  float* gram = reinterpret_cast<float*>(R + 1024);
+  const long gram_floats = 1024L * stem_bwd_part_floats();
+  float* part = gram + gram_floats;
+  const long part_floats = (long)(MMVAE_BN_SCRATCH_BYTES - MMVAE_STEM_DG_PACK_BYTES - 1024 * 8) / 4 - gram_floats;
+  static_assert((MMVAE_BN_SCRATCH_BYTES - MMVAE_STEM_DG_PACK_BYTES - 1024 * 8) / 4 - 1024L * (64 + 32 * 32) >= 768L * (64 + 32 * 32), "768 partial rows fit");
+  char* pk1 = static_cast<char*>(scratch) + (MMVAE_BN_SCRATCH_BYTES - MMVAE_STEM_DG_PACK_BYTES);
+  char* pks = pk1 + (size_t)32 * 9 * 32 * dtype_size(dt);
+  int rc = op_pack_up(dt, geom_for(0, 32, 32, 3, 2, 1), w_c1, pk1, stream_of(st)); if (rc < 0) return rc;
+  rc = op_pack_up(dt, geom_for(0, 32, 32, 1, 2, 0), w_sc, pks, stream_of(st)); if (rc < 0) return rc;
+  rc = launch_stem_gram(dt, x, gram, gram_floats, R, N, Sz, H1, H1, stream_of(st));
+  if (rc < 0) return rc;
+  const int np = launch_stem_bwd_dg(dy1, dys, pk1, pks, y0, x, bn_scale, bn_shift, part, part_floats, N, Sz, H1, H1, stream_of(st));
   if (np < 0) return np;
   return launch_stem_bwd_finalize(part, np, R, w, nullptr, (double)N * H1 * H1, gamma, save_mean, save_istd, dgamma, dbeta, dw, stream_of(st));
 }
