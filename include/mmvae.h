@@ -431,6 +431,39 @@ MMVAE_API int mmvae_latent_stats(const float* mu, const float* logvar, const flo
 MMVAE_API size_t mmvae_posterior_mixture_scratch_bytes(int N, int M, int d);
 MMVAE_API int mmvae_posterior_mixture(const float* z, int N, const float* mu, const float* logvar, int M, int d, double* log_qz,
                                       double* log_qz_dims, void* scratch, size_t scratch_bytes, void* stream);
+/* The gradient of both outputs with respect to z, mu and logvar (training against the split: the beta-TCVAE penalty of Chen et al. 2018).
+ * z, mu, logvar as above; log_qz f64 [N] and log_qz_dims f64 [N][d] are the outputs mmvae_posterior_mixture wrote for these very inputs;
+ * g_joint f64 [N] and g_dims f64 [N][d] are the upstream gradients of log_qz and log_qz_dims.  Either g may be NULL, meaning zero, but
+ * not both; log_qz_dims may be NULL if and only if g_dims is NULL.  With
+ *   r_ij   = exp(s_ij  - (log_qz[i]         + log M))       (sum_j r_ij = 1)
+ *   rd_ijd = exp(t_ijd - (log_qz_dims[i][d] + log M))
+ *   a_ijd  = g_joint[i] * r_ij + g_dims[i][d] * rd_ijd
+ *   u_ijd  = (z_id - mu_jd) * exp(-logvar_jd)
+ * the outputs, dense f32 device arrays, are
+ *   d_z[i][d]      = - sum_j a_ijd * u_ijd                              [N][d]
+ *   d_mu[j][d]     =   sum_i a_ijd * u_ijd                              [M][d]
+ *   d_logvar[j][d] =   sum_i a_ijd * 0.5 * ((z_id - mu_jd) * u_ijd - 1) [M][d]
+ * Every element of the three is written, nothing is accumulated into what was there, and nothing outside them and the scratch is written.
+ * Determinism: d_z is a sum over the bank and d_mu / d_logvar are sums over the samples; each is taken by a sweep of its own that keeps
+ * one output row per lane (the other side is staged through LDS), cut into chunks by a rule that depends on (N, M, d) alone; the chunks'
+ * partial sums go through `scratch` and are combined in chunk order.  Fixed summation order, no atomics: the same bits every run.
+ * Precision: the terms are formed in f32 (the bank entries as in the forward; g_joint, g_dims and log_qz_dims + log M are rounded once to
+ * f32, log_qz + log M stays f64 and is subtracted from the f64 joint exponent).  No f32 sum is carried over more than the 8 terms of a
+ * group (16 inside a tile of the joint exponent); every longer sum is f64 and is rounded once to f32 at the store.
+ * Capturable: no allocation, no host read, no synchronisation; five launches on `stream`.
+ * scratch: 16-byte aligned device memory of at least mmvae_posterior_mixture_bwd_scratch_bytes(N, M, d) bytes (a function of the shape
+ * alone, 0 for a shape the call refuses).  Every scratch word that is read was written earlier by the same call.
+ * Ranges: 1 <= d <= 512 and 1 <= N, M <= 16384 (training batches; evaluation-size banks are not the use); above them
+ * MMVAE_ERR_UNSUPPORTED.  A non-positive N, M or d, a NULL required pointer, both g_joint and g_dims NULL, g_dims without log_qz_dims, a
+ * misaligned or too-small scratch: MMVAE_ERR_ARG.  Nothing is enqueued on an error, and mmvae_last_error() names the value.
+ * Domain: the forward's, |z|, |mu| <= 1e4 and |logvar| <= 30, with log_qz / log_qz_dims the forward's outputs and finite upstream
+ * gradients.  Inside it every output is finite: the largest u is about 2e17 and the largest (z - mu) * u about 4e21, both finite in
+ * f32, and a weight that underflows to 0 multiplies a finite number.  Outside it the output values are unspecified; nothing is written
+ * out of bounds. */
+MMVAE_API size_t mmvae_posterior_mixture_bwd_scratch_bytes(int N, int M, int d);
+MMVAE_API int mmvae_posterior_mixture_bwd(const float* z, int N, const float* mu, const float* logvar, int M, int d, const double* log_qz,
+                                          const double* log_qz_dims, const double* g_joint, const double* g_dims, float* d_z, float* d_mu,
+                                          float* d_logvar, void* scratch, size_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------ nearest training frames of a sample (memorised or drawn?)
  * Exact k nearest neighbours of M query planes among F resident frames.  queries [M][D], frames [F][D]: dense device uint8, 16-byte

@@ -7,7 +7,7 @@ a GPU; constructing / running the model does, and fails loudly when the HIP libr
 from .data import (GeneratedClips, MovingMNISTClips, QuantiserFit, choose_transformer, clips_from_npz_array, fit_quantiser,  # noqa: F401
                    generate_batch, generate_clips, load_idx_images, load_kmeans_file, nearest_frames, pixel_histogram, quantise_frames,
                    resize_frames, resize_quantise_frames, save_kmeans_file, save_moving_mnist_files, velocity_table)
-from .decomposition import elbo_decomposition, posterior_mixture  # noqa: F401
+from .decomposition import elbo_decomposition, latent_penalty, make_latent_penalty, posterior_mixture  # noqa: F401
 from .main import (checkpoint_variant, evaluate, generate, generate_only_pixelcnn, latent_stats, load_checkpoint, save_checkpoint,  # noqa: F401
                    select_model, train)
 from .monitor import TensorHistograms, make_histogram_callback, tensor_histograms  # noqa: F401

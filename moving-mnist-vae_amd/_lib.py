@@ -82,6 +82,8 @@ PROTOTYPES = {
     "mmvae_latent_stats": (c_int, [P, P, P, c_int, c_int, c_int, P, P]),
     "mmvae_posterior_mixture_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
     "mmvae_posterior_mixture": (c_int, [P, c_int, P, P, c_int, c_int, P, P, P, c_size_t, P]),
+    "mmvae_posterior_mixture_bwd_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "mmvae_posterior_mixture_bwd": (c_int, [P, c_int, P, P, c_int, c_int, P, P, P, P, P, P, P, P, c_size_t, P]),
     "mmvae_nearest_frames_scratch_bytes": (c_size_t, [c_int, c_int64, c_int, c_int]),
     "mmvae_nearest_frames": (c_int, [P, c_int, P, c_int64, c_int, P, c_int, P, P, P, c_size_t, P]),
     "mmvae_tensor_hist_chunks": (c_int64, [P, c_int, c_int64, P, c_int64]),
@@ -144,6 +146,7 @@ FRAME_BYTES_U8, FRAME_MIN_S, FRAME_MAX_S = 5, 11, 64             # MMVAE_FRAME_B
 SCATTER_MAX_SIDE, SCATTER_MIN_RADIUS16, SCATTER_MAX_RADIUS16 = 512, 12, 128      # mmvae_scatter_panel's accepted ranges
 LATENT_STATS_ROWS, LATENT_STATS_MAX_D = 6, 512                                   # mmvae_latent_stats: rows of acc, widest latent
 MIXTURE_MAX_D, MIXTURE_MAX_N, MIXTURE_MIN_CHUNK = 512, 1 << 20, 64           # mmvae_posterior_mixture: widest latent, most samples / bank rows, fewest rows of a bank chunk
+MIXTURE_BWD_MAX_N = 16384                                                        # mmvae_posterior_mixture_bwd: most samples / bank rows
 NEAREST_MAX_M, NEAREST_MAX_K, NEAREST_MAX_D = 64, 8, 16384                       # mmvae_nearest_frames: queries, neighbours, bytes per plane
 CLIPGEN_MAX_G, CLIPGEN_MAX_T, CLIPGEN_MAX_K, CLIPGEN_MAX_D, CLIPGEN_DIRECTIONS = 32, 32, 4, 1 << 24, 4096       # MMVAE_CLIPGEN_*
 

@@ -375,6 +375,13 @@ int mmvae_posterior_mixture(const float* z, int N, const float* mu, const float*
                             void* scratch, size_t scratch_bytes, void* st) {
   return launch_posterior_mixture(z, N, mu, logvar, M, d, log_qz, log_qz_dims, scratch, scratch_bytes, stream_of(st));
 }
+size_t mmvae_posterior_mixture_bwd_scratch_bytes(int N, int M, int d) { return posterior_mixture_bwd_scratch_bytes(N, M, d); }
+int mmvae_posterior_mixture_bwd(const float* z, int N, const float* mu, const float* logvar, int M, int d, const double* log_qz,
+                                const double* log_qz_dims, const double* g_joint, const double* g_dims, float* d_z, float* d_mu,
+                                float* d_logvar, void* scratch, size_t scratch_bytes, void* st) {
+  return launch_posterior_mixture_bwd(z, N, mu, logvar, M, d, log_qz, log_qz_dims, g_joint, g_dims, d_z, d_mu, d_logvar, scratch, scratch_bytes,
+                                      stream_of(st));
+}
 // ---- nearest training frames (arguments are checked in the launcher)
 size_t mmvae_nearest_frames_scratch_bytes(int M, int64_t F, int D, int k) { return nearest_frames_scratch_bytes(M, (long)F, D, k); }
 int mmvae_nearest_frames(const uint8_t* queries, int M, const uint8_t* frames, int64_t F, int D, const uint8_t* lut, int k, int32_t* out_dist,

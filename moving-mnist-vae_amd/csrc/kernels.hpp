@@ -444,6 +444,12 @@ int launch_latent_stats(const float* mu, const float* logvar, const float* enc, 
 size_t posterior_mixture_scratch_bytes(int N, int M, int d);
 int launch_posterior_mixture(const float* z, int N, const float* mu, const float* logvar, int M, int d, double* log_qz, double* log_qz_dims,
                              void* scratch, size_t scratch_bytes, hipStream_t s);
+// their gradient (posterior_mixture_bwd.hip): d_z [N][d], d_mu, d_logvar [M][d] f32 from the saved outputs and the upstream gradients
+// g_joint [N], g_dims [N][d] f64 (either nullable, not both; log_qz_dims nullable with g_dims).  Written, not accumulated; N, M <= 16384.
+size_t posterior_mixture_bwd_scratch_bytes(int N, int M, int d);
+int launch_posterior_mixture_bwd(const float* z, int N, const float* mu, const float* logvar, int M, int d, const double* log_qz,
+                                 const double* log_qz_dims, const double* g_joint, const double* g_dims, float* d_z, float* d_mu,
+                                 float* d_logvar, void* scratch, size_t scratch_bytes, hipStream_t s);
 // exact k nearest frames of M uint8 query planes among F frames of D bytes (neighbours.hip): squared distances in integers, ties to the
 // lower frame index, lut (nullable, 256 device bytes) applied to the frames only.  The scratch size is a function of the shape alone
 // (0 for a shape the launcher refuses); both check their arguments before anything is enqueued.

@@ -13,7 +13,9 @@ the picture panels (``plot_vae`` / ``plot_pixelcnn`` / ``plot_pixelvae``) and th
 scatter plot (``scatter_plot``) live there too.  The per-parameter histograms of
 ``wandb.hook_torch`` (``main.py:456``) hang off ``args.stats_callback``, called
 between ``backward`` and ``step``: ``make_histogram_callback`` in ``monitor.py``
-returns one.  The device-side input pipeline
+returns one.  A further loss term on the latent code hangs off
+``args.latent_penalty`` (``make_latent_penalty`` in ``decomposition.py``: the
+beta-TCVAE objective of Chen et al. 2018).  The device-side input pipeline
 (``quantise_frames``, ``fit_quantiser``, ``MovingMNISTClips``, ...) lives in
 ``data.py``.  The reference's ``main.py`` carries those names, so this module
 re-exports them.
@@ -35,7 +37,8 @@ import torch
 from .data import (KMEANS_FILE_NOTE, GeneratedClips, MovingMNISTClips, QuantiserFit, choose_transformer, clips_from_npz_array,  # noqa: F401
                    fit_quantiser, generate_batch, generate_clips, load_idx_images, load_kmeans_file, nearest_frames, pixel_histogram,
                    quantise_frames, resize_frames, resize_quantise_frames, save_kmeans_file, save_moving_mnist_files, velocity_table)
-from .decomposition import _decompose, decomposition_to_host, elbo_decomposition, posterior_mixture  # noqa: F401
+from .decomposition import (LatentPenalty, _decompose, decomposition_to_host, elbo_decomposition, latent_penalty, make_latent_penalty,  # noqa: F401
+                            posterior_mixture)
 from .model import VAE
 from .monitor import TensorHistograms, make_histogram_callback, tensor_histograms  # noqa: F401
 from .panels import (column, gray_lut, latent_slide, make_plot_callback, neighbour_sheet, plot_neighbours, plot_pixelcnn, plot_pixelvae,  # noqa: F401
@@ -66,6 +69,7 @@ def train(model, data_loader, optimizer, device, args, epoch=0, data_mean=0, dat
     model.train(True)
     plot_callback = getattr(args, "plot_callback", None)
     stats_callback = getattr(args, "stats_callback", None)
+    penalty_fn = getattr(args, "latent_penalty", None)                     # make_latent_penalty(...): beta-TCVAE and its kin
     # HIP model: the step scalars stay on the device (model._last_group) and are read back once, after the loop or
     # when the plot callback needs them -- the host never waits for the GPU in the middle of a step.
     pending = []                      # (position in the lists, scalar group)
@@ -95,6 +99,11 @@ def train(model, data_loader, optimizer, device, args, epoch=0, data_mean=0, dat
             nlls.append(nll_v)
             kls.append(kl_v)
             mmds.append(mmd_v)
+        if penalty_fn is not None:
+            # (alpha - 1) MI + (beta - 1) TC + (gamma - 1) DWKL of this batch, through plain autograd.  Under deferred=True the VALUE of
+            # `loss` is not defined yet at this point (its kernels run behind the decoder's backward pass): only the gradient of the sum is
+            # used, and the four returned lists stay the reference's -- the penalty's own figures are penalty_fn.to_host()'s.
+            loss = loss + penalty_fn(mu, logvar, encoding).to(loss.dtype)
         optimizer.zero_grad()                                                # main.py:397-399
         loss.backward()
         if stats_callback is not None:                                       # main.py:456 (wandb.hook_torch): the gradients, before the step
