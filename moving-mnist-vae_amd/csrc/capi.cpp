@@ -459,39 +459,33 @@ int mmvae_conv2d_fwd(int dt, int transposed, const void* x, const float* w, void
   if (const int rc = conv_fwd_refused(dt, Cin, Cout, k); rc < 0) return rc;
   const ConvGeom g = geom_for(transposed, Cin, Cout, k, s, p);
   const int Ho = out_size(transposed, H, k, s, p), Wo = out_size(transposed, W, k, s, p);
+  const MapIn in(x, H, W, Affine{ps, pb}, relu);
+  const MapOut out(y, Ho, Wo, stats);
   // weight == NULL: `scratch` still holds the packed weights of an earlier call with the same geometry (pack once, run many)
   SecondSrc q;
   if (!transposed && conv3_stream_ok(dt, Cin, Cout, k, s, p, H, W)) {      // the first encoder block's 3x3 convs: per-wave stream
     if (w) { int rc = op_pack_down(dt, g, w, scratch, stream_of(st)); if (rc < 0) return rc; }
-    return launch_conv3_stream(dt, s, x, scratch, nullptr, y, nullptr, ps, pb, relu, stats, nullptr, N, Ho, stream_of(st));
+    return launch_conv3_stream(dt, s, in, scratch, nullptr, out, MapOut(), N, stream_of(st));
   }
   if (!transposed) {
     q.wfrag = op_down_layout(dt, g, H, W).frag;
     if (w) { int rc = op_pack_down(dt, g, w, scratch, stream_of(st), 1.f, 0, q.wfrag); if (rc < 0) return rc; }
-    return op_run_down(dt, dt, g, scratch, N, x, H, W, y, Ho, Wo, ps, pb, relu, stats, 0, stream_of(st), q);
+    return op_run_down(dt, dt, g, scratch, in, out, N, stream_of(st), q);
   }
   if (convT4_stream_ok(dt, Cin, Cout, k, s, p, H, W)) {                   // the decoder's widest ConvT layers: per-wave stream
     if (w) { int rc = op_pack_up(dt, g, w, scratch, stream_of(st)); if (rc < 0) return rc; }
-    return launch_convT4_stream(dt, x, scratch, y, ps, pb, relu, stats, N, H, stream_of(st));
+    return launch_convT4_stream(dt, in, scratch, out, N, stream_of(st));
   }
   q.wfrag = op_up_layout(dt, g, Ho, Wo).frag;
   if (w) { int rc = op_pack_up(dt, g, w, scratch, stream_of(st), 1.f, 0, q.wfrag); if (rc < 0) return rc; }
-  return op_run_up(dt, g, scratch, N, x, H, W, y, Ho, Wo, ps, pb, relu, stats, 0, stream_of(st), q);
-}
-// A 3x3 Conv2d weight (Cout,Cin,3,3) packed [cin][flipped tap][cout]: its stride-1 data gradient is then a forward conv over dy
-// (dx[n,h,w,ci] = sum_{kh,kw,co} dy[n, h+1-kh, w+1-kw, co] W[co][ci][kh][kw], tap' = 8 - tap), as Net::packs_enc_bwd packs encoder.layer1.conv2
-static int pack_flipped3(int dt, const float* w, void* dst, int Cin, int Cout, hipStream_t s) {
-  PackArgs pf; std::memset(&pf, 0, sizeof(pf));
-  pf.src = w; pf.dst = dst; pf.cols = Cin; pf.K = Cout; pf.ntaps = 9; pf.s_col = 9; pf.s_k = Cin * 9; pf.scale = 1.f;
-  for (int t = 0; t < 9; ++t) pf.tap_off[t] = 8 - t;
-  return launch_pack(dt, pf, s);
+  return op_run_up(dt, g, scratch, in, out, N, stream_of(st), q);
 }
 int mmvae_conv2d_dgrad(int dt, int transposed, const void* dy, const float* w, void* dx, int N, int H, int W, int Cin, int Cout, int k,
                        int s, int p, void* scratch, void* st) {
   if (!transposed && s == 1 && conv3_stream_ok(dt, Cin, Cout, k, s, p, H, W)) {
-    // encoder.layer1.conv2's shape: the data gradient as a forward conv over dy with the weights packed [cin][flipped tap][cout]
-    int rc = pack_flipped3(dt, w, scratch, Cin, Cout, stream_of(st)); if (rc < 0) return rc;
-    rc = launch_conv3_stream(dt, 1, dy, scratch, nullptr, dx, nullptr, nullptr, nullptr, 0, nullptr, nullptr, N, H, stream_of(st));
+    // encoder.layer1.conv2's shape: the data gradient as a forward conv over dy with the weights packed [cin][flipped tap][cout] (op_pack_flipped3)
+    int rc = op_pack_flipped3(dt, w, scratch, Cin, Cout, stream_of(st)); if (rc < 0) return rc;
+    rc = launch_conv3_stream(dt, 1, MapIn(dy, H, W), scratch, nullptr, MapOut(dx, H, W), MapOut(), N, stream_of(st));
     return rc < 0 ? rc : MMVAE_OK;
   }
   // everything else: the launch Net::run_up / Net::run_down make, with neither option
@@ -516,6 +510,8 @@ int mmvae_conv2d_dgrad_ex(int dt, int transposed, const void* dy, const float* w
   const ConvGeom g = geom_for(transposed, Cin, Cout, k, s, p);
   const int Ho = out_size(transposed, H, k, s, p), Wo = out_size(transposed, W, k, s, p);
   char* sc = static_cast<char*>(scratch);
+  const MapIn in(dy, Ho, Wo);
+  const MapOut out(dx, H, W, nullptr, accumulate != 0);
   SecondSrc q;
   if (dy2) {
     // Conv2d (C2, Cin, 1, 1) on the main layer's input: with the main Conv2d's stride (encoder downsample.0), stride 1 beside a ConvTranspose2d
@@ -529,11 +525,11 @@ int mmvae_conv2d_dgrad_ex(int dt, int transposed, const void* dy, const float* w
   if (!transposed) {
     q.wfrag = op_up_layout(dt, g, H, W, accumulate != 0).frag;
     int rc = op_pack_up(dt, g, w, scratch, stream_of(st), 1.f, 0, q.wfrag); if (rc < 0) return rc;
-    return op_run_up(dt, g, scratch, N, dy, Ho, Wo, dx, H, W, nullptr, nullptr, 0, nullptr, accumulate != 0, stream_of(st), q);
+    return op_run_up(dt, g, scratch, in, out, N, stream_of(st), q);
   }
   q.wfrag = op_down_layout(dt, g, Ho, Wo).frag;
   int rc = op_pack_down(dt, g, w, scratch, stream_of(st), 1.f, 0, q.wfrag); if (rc < 0) return rc;
-  return op_run_down(dt, dt, g, scratch, N, dy, Ho, Wo, dx, H, W, nullptr, nullptr, 0, nullptr, accumulate != 0, stream_of(st), q);
+  return op_run_down(dt, dt, g, scratch, in, out, N, stream_of(st), q);
 }
 int mmvae_conv2d_wgrad(int dt, int transposed, const void* x, const void* dy, float* dw, int N, int H, int W, int Cin, int Cout, int k,
                        int s, int p, const float* ps, const float* pb, int relu, void* scratch, void* st) {
@@ -542,9 +538,11 @@ int mmvae_conv2d_wgrad(int dt, int transposed, const void* x, const void* dy, fl
   if (!scratch) { set_error("conv2d_wgrad: scratch (MMVAE_WGRAD_SCRATCH_BYTES) required"); return MMVAE_ERR_ARG; }
   if (const int rc = conv_dtype_refused("conv2d_wgrad", dt); rc < 0) return rc;
   static_assert(MMVAE_WGRAD_SCRATCH_BYTES == kWgradScratchBytes, "public scratch size out of sync");
-  float* sc = static_cast<float*>(scratch);
-  if (!transposed) return op_run_wgrad(dt, g, N, dy, Ho, Wo, nullptr, nullptr, 0, x, H, W, ps, pb, relu, dw, stream_of(st), sc);
-  return op_run_wgrad(dt, g, N, x, H, W, ps, pb, relu, dy, Ho, Wo, nullptr, nullptr, 0, dw, stream_of(st), sc);
+  WgradOpts o;
+  o.scratch = static_cast<float*>(scratch);
+  const MapIn in(x, H, W, Affine{ps, pb}, relu), grad(dy, Ho, Wo);
+  if (!transposed) return op_run_wgrad(dt, g, grad, in, dw, N, stream_of(st), o);
+  return op_run_wgrad(dt, g, in, grad, dw, N, stream_of(st), o);
 }
 int mmvae_conv2d_wgrad_pair(int dt, const void* x, const void* dy, const void* dy_sc, float* dw, float* dw_sc, int N, int H, int W, int Cin, int Cout,
                             const float* ps, const float* pb, int relu, void* scratch, void* st) {
@@ -552,7 +550,9 @@ int mmvae_conv2d_wgrad_pair(int dt, const void* x, const void* dy, const void* d
   if (const int rc = conv_dtype_refused("conv2d_wgrad_pair", dt); rc < 0) return rc;
   const ConvGeom g = geom_for(0, Cin, Cout, 3, 2, 1), gs = geom_for(0, Cin, Cout, 1, 2, 0);
   const int Ho = out_size(0, H, 3, 2, 1), Wo = out_size(0, W, 3, 2, 1);
-  const int rc = op_run_wgrad_pair(dt, g, gs, N, dy, dy_sc, Ho, Wo, x, H, W, ps, pb, relu, dw, dw_sc, stream_of(st), static_cast<float*>(scratch), 1.f, 1.f);
+  WgradOpts o;
+  o.scratch = static_cast<float*>(scratch);
+  const int rc = op_run_wgrad_pair(dt, g, gs, MapIn(dy, Ho, Wo), dy_sc, MapIn(x, H, W, Affine{ps, pb}, relu), dw, dw_sc, N, stream_of(st), o);
   if (rc == 0) { set_error("conv2d_wgrad_pair: shape not supported (bf16, 32 -> 32 channels, 32x32 -> 16x16)"); return MMVAE_ERR_UNSUPPORTED; }
   return rc < 0 ? rc : MMVAE_OK;
 }
@@ -574,7 +574,8 @@ int mmvae_conv2d_fwd_pair(int dt, const void* x, const float* w, const float* w_
   void* wsp = sc + (size_t)32 * 9 * 32 * dtype_size(dt);
   int rc = op_pack_down(dt, geom_for(0, Cin, Cout, 3, 2, 1), w, sc, stream_of(st)); if (rc < 0) return rc;
   rc = op_pack_down(dt, geom_for(0, Cin, Cout, 1, 2, 0), w_sc, wsp, stream_of(st)); if (rc < 0) return rc;
-  return launch_conv3_stream(dt, 2, x, sc, wsp, y, y_sc, ps, pb, relu, stats, stats_sc, N, H / 2, stream_of(st));
+  return launch_conv3_stream(dt, 2, MapIn(x, H, W, Affine{ps, pb}, relu), sc, wsp, MapOut(y, H / 2, W / 2, stats), MapOut(y_sc, H / 2, W / 2, stats_sc), N,
+                             stream_of(st));
 }
 int mmvae_conv2d_dgrad_bn_sums(int dt, const void* dy, const float* w, void* dx, const void* y_pre, const float* bn_scale, const float* bn_shift,
                                float* sums, int N, int H, void* scratch, void* st) {
@@ -583,8 +584,8 @@ int mmvae_conv2d_dgrad_bn_sums(int dt, const void* dy, const float* w, void* dx,
     set_error("conv2d_dgrad_bn_sums: bad argument (every operand and scratch required, N >= 1)"); return MMVAE_ERR_ARG;
   }
   if (dt != MMVAE_BF16 || H != 16) { set_error("conv2d_dgrad_bn_sums: shape not supported (bf16, 32 -> 32 channels, 16x16 maps)"); return MMVAE_ERR_UNSUPPORTED; }
-  int rc = pack_flipped3(dt, w, scratch, 32, 32, stream_of(st)); if (rc < 0) return rc;
-  return launch_conv3_stream_bwd(dt, dy, scratch, dx, y_pre, bn_scale, bn_shift, sums, N, H, stream_of(st));
+  int rc = op_pack_flipped3(dt, w, scratch, 32, 32, stream_of(st)); if (rc < 0) return rc;
+  return launch_conv3_stream_bwd(dt, MapIn(dy, H, H), scratch, BnSide{y_pre, {bn_scale, bn_shift}}, MapOut(dx, H, H, sums), N, stream_of(st));
 }
 int mmvae_convT_bwd_fused(int dt, const void* x, const void* dy, const float* w, float* dw, void* dx, int N, int H, int W, int Cin, int Cout, int k,
                           int s, int p, const float* ps, const float* pb, int relu, const void* x2, const float* w2, float* dw2, void* scratch,
@@ -593,7 +594,7 @@ int mmvae_convT_bwd_fused(int dt, const void* x, const void* dy, const float* w,
   const int Ho = out_size(1, H, k, s, p), Wo = out_size(1, W, k, s, p);
   if (!scratch || !wscratch) { set_error("convT_bwd_fused: scratch buffers required"); return MMVAE_ERR_ARG; }
   if (const int rc = conv_dtype_refused("convT_bwd_fused", dt); rc < 0) return rc;
-  if (!op_bwd_fusable(dt, g, N, H, W, Ho, Wo)) { set_error("convT_bwd_fused: shape not supported (bf16, 16 / 32 -> 16 channels, k4 s2 p1, 32x32 -> 64x64 or 16x16 -> 32x32)"); return MMVAE_ERR_UNSUPPORTED; }
+  if (!op_bwd_fusable(dt, g, MapIn::shape(H, W), MapIn::shape(Ho, Wo), N)) { set_error("convT_bwd_fused: shape not supported (bf16, 16 / 32 -> 16 channels, k4 s2 p1, 32x32 -> 64x64 or 16x16 -> 32x32)"); return MMVAE_ERR_UNSUPPORTED; }
   char* sc = static_cast<char*>(scratch);
   int rc = op_pack_down(dt, g, w, sc, stream_of(st)); if (rc < 0) return rc;
   const void* w2p = nullptr;
@@ -604,8 +605,11 @@ int mmvae_convT_bwd_fused(int dt, const void* x, const void* dy, const float* w,
     w2p = pa.dst;
   }
   if (dw2 && !w2p) { set_error("convT_bwd_fused: dw2 needs x2 and w2"); return MMVAE_ERR_ARG; }
-  rc = op_run_bwd_fused(dt, g, N, x, H, W, ps, pb, relu, dy, Ho, Wo, sc, dx, w2p ? x2 : nullptr, w2p, dw, stream_of(st), static_cast<float*>(wscratch), 1.f,
-                        nullptr, dw2, 1.f);
+  SecondSrc q;
+  if (w2p) { q.x2 = x2; q.w2 = w2p; }
+  WgradOpts o;
+  o.scratch = static_cast<float*>(wscratch); o.dW2 = dw2;
+  rc = op_run_bwd_fused(dt, g, sc, MapIn(x, H, W, Affine{ps, pb}, relu), MapIn(dy, Ho, Wo), q, dx, dw, N, stream_of(st), o);
   if (rc == 0) { set_error("convT_bwd_fused: not taken"); return MMVAE_ERR_UNSUPPORTED; }
   return rc < 0 ? rc : MMVAE_OK;
 }
@@ -644,21 +648,10 @@ static_assert(MMVAE_STEM_SCRATCH_BYTES >= 32 * 25 * 16, "stem scratch: 32 column
 int mmvae_stem_fwd(int dt, const void* x, const float* w, void* y, int N, int Sz, float* stats, void* scratch, void* st) {
   if (!scratch || N < 1 || Sz < 9 || Sz > 64) { set_error("stem_fwd: bad arguments"); return MMVAE_ERR_ARG; }
   if (stem_fwd_stream_ok(dt, Sz)) return launch_stem_fwd_stream(dt, x, w, y, stats, N, Sz, stream_of(st));
-  const int H1 = (Sz + 4 - 5) / 2 + 1;
-  const int cpad = dt == DT_F32 ? 4 : 8;
-  PackArgs pa; std::memset(&pa, 0, sizeof(pa));
-  pa.src = w; pa.dst = scratch;
-  pa.cols = 32; pa.K = cpad; pa.K_valid = 1; pa.ntaps = 25; pa.s_col = 25; pa.s_k = 25; pa.scale = 1.f;
-  for (int t = 0; t < 25; ++t) pa.tap_off[t] = t;
-  int rc = launch_pack(dt, pa, stream_of(st));
+  const int H1 = conv_down_size(Sz, 5, 2, 2);
+  const int rc = op_pack_stem(dt, w, 1, scratch, stream_of(st));
   if (rc < 0) return rc;
-  GatherArgs a; std::memset(&a, 0, sizeof(a));
-  a.x = x; a.w = scratch; a.y = y; a.stats = stats;
-  a.x_planar = 2; a.x_planes = 1;
-  a.N = N; a.Hi = Sz; a.Wi = Sz; a.Cin = cpad; a.Ho = H1; a.Wo = H1; a.Cout = 32; a.SI = 2; a.SO = 1;
-  a.nphase = 1; a.phases[0] = Phase{0, 0, H1, H1, 25, 0, 0};
-  for (int kh = 0; kh < 5; ++kh) for (int kw = 0; kw < 5; ++kw) a.taps[kh * 5 + kw] = Tap{kh - 2, kw - 2};
-  return launch_gather_gemm(dt, dt, a, stream_of(st));
+  return op_run_stem(dt, scratch, x, 1, Sz, MapOut(y, H1, H1, stats), N, stream_of(st));
 }
 int mmvae_stem_bwd(int dt, const void* g, const void* y0, const void* x, const float* w, const float* gamma, const float* bn_scale,
                    const float* bn_shift, const float* save_mean, const float* save_istd, float* dw, float* dgamma, float* dbeta, int N, int Sz,
@@ -743,13 +736,8 @@ int mmvae_upblock_bwd_fused(const float* d_raw, const float* tw, const void* y2,
   L.N = N;
   const int nb = launch_join_bwd_stream(L, stream_of(st));
   if (nb < 0) return nb;
-  for (int k = 0; k < 2; ++k) {
-    WgradReduceArgs u; std::memset(&u, 0, sizeof(u));
-    u.part = k ? L.parts : L.part2; u.dW = k ? dwu : dw2; u.Ca = 16; u.Cb = 16; u.ntaps = 16; u.nparts = nb;
-    u.Ca_valid = 16; u.Cb_valid = 16; u.sA = 16 * 16; u.sB = 16; u.scale = 1.f;
-    for (int t = 0; t < 16; ++t) u.tap_off[t] = t;
-    rc = launch_wgrad_reduce(u, stream_of(st)); if (rc < 0) return rc;
-  }
+  rc = launch_wgrad_reduce(reduce_args(L.part2, nb, dw2, 16, 16, 16), stream_of(st)); if (rc < 0) return rc;
+  rc = launch_wgrad_reduce(reduce_args(L.parts, nb, dwu, 16, 16, 16), stream_of(st)); if (rc < 0) return rc;
   return launch_partial_rowsum(L.bn_part, nb, 32, bn1_sums, stream_of(st));
 }
 int mmvae_upblock_tail_fwd(const void* y1, const float* s1, const float* b1, const float* w2, const void* xin, const float* sx, const float* bx,
@@ -783,7 +771,7 @@ int mmvae_convT4_stats(int dt, const void* x, const float* w, const float* ps, c
   if (dt != DT_BF16) { set_error("convT4_stats: bf16 only"); return MMVAE_ERR_UNSUPPORTED; }
   if (e4m3_out) { set_error("convT4_stats: the e4m3 storage mode has no statistics-only form"); return MMVAE_ERR_UNSUPPORTED; }
   int rc = op_pack_up(dt, geom_for(1, 16, 16, 4, 2, 1), w, scratch, stream_of(st)); if (rc < 0) return rc;
-  return launch_convT4_stream(dt, x, scratch, nullptr, ps, pb, 1, stats, N, 32, stream_of(st));
+  return launch_convT4_stream(dt, MapIn(BnSide{x, {ps, pb}}, 32, 32), scratch, MapOut(nullptr, 64, 64, stats), N, stream_of(st));
 }
 int mmvae_conv1x1_bwd_fused(const void* da1, const void* y1, const float* s1, const float* b1, const float* A1, const float* B1, const float* C1,
                             const void* xin, const float* sx, const float* bx, const float* w1, float* dw1, void* gin, int64_t rows, void* scratch,
@@ -799,9 +787,7 @@ int mmvae_conv1x1_bwd_fused(const void* da1, const void* y1, const float* s1, co
   C.part = reinterpret_cast<float*>(sc + 4096); C.nrows = (long)rows;
   const int nb = launch_conv1_bwd_stream(C, stream_of(st));
   if (nb < 0) return nb;
-  WgradReduceArgs u; std::memset(&u, 0, sizeof(u));
-  u.part = C.part; u.dW = dw1; u.Ca = 16; u.Cb = 16; u.ntaps = 1; u.nparts = nb; u.Ca_valid = 16; u.Cb_valid = 16; u.sA = 16; u.sB = 1; u.scale = 1.f;
-  return launch_wgrad_reduce(u, stream_of(st));
+  return launch_wgrad_reduce(reduce_args(C.part, nb, dw1, 16, 16, 1), stream_of(st));
 }
 int mmvae_join_conv1x1_fwd(const void* y2, const float* s2, const float* b2, const void* ys, const float* ss, const float* bs, const float* w1, int C,
                            void* out, void* y1, float* stats, int64_t npix, void* scratch, void* st) {

@@ -201,20 +201,21 @@ bool conv3_stream_ok(int dt, int Cin, int Cout, int k, int s, int p, int Hin, in
 
 // y [N][Ho][16][32] = conv3x3(x [N][s*Ho][s*16][32], stride s, pad 1) with the packed [32][9][32] weights; wsc / ysc / stats_sc (optional, s = 2):
 // the 1x1 stride-2 shortcut on the same input, packed [32][32].  Returns the number of partial rows (> 0) or an error.
-int launch_conv3_stream(int dt, int stride, const void* x, const void* w, const void* wsc, void* y, void* ysc, const float* pro_scale,
-                        const float* pro_shift, int pro_relu, float* stats, float* stats_sc, int N, int Ho, hipStream_t s) {
-  if (dt != DT_BF16 || (stride != 1 && stride != 2) || (wsc && stride != 2) || ((wsc != nullptr) != (ysc != nullptr))) {
+int launch_conv3_stream(int dt, int stride, const MapIn& x, const void* w, const void* wsc, const MapOut& y, const MapOut& ysc, int N,
+                        hipStream_t s) {
+  if (dt != DT_BF16 || (stride != 1 && stride != 2) || (wsc && stride != 2) || ((wsc != nullptr) != (ysc.y != nullptr))) {
     set_error("conv3_stream: bf16, stride 1 or 2, shortcut only with stride 2"); return MMVAE_ERR_UNSUPPORTED;
   }
+  const int Ho = y.H;
   Conv3StreamArgs a; memset(&a, 0, sizeof(a));
-  a.x = x; a.w = w; a.wsc = wsc; a.y = y; a.ysc = ysc; a.pro_scale = pro_scale; a.pro_shift = pro_shift; a.pro_relu = pro_relu;
-  a.stats = stats; a.stats_sc = stats_sc; a.N = N; a.Ho = Ho; a.Hi = stride * Ho;
+  a.x = x.x; a.w = w; a.wsc = wsc; a.y = y.y; a.ysc = ysc.y; a.pro_scale = x.pro.scale; a.pro_shift = x.pro.shift; a.pro_relu = x.relu;
+  a.stats = y.stats; a.stats_sc = ysc.stats; a.N = N; a.Ho = Ho; a.Hi = stride * Ho;
   a.HS = Ho % 8 == 0 ? 8 : Ho;
   a.nunits = N * (Ho / a.HS);
   // blocks: measured per kernel at 5120 frames : stride 1 62 us at 512, 55 at 768 / 1024; stride 2 flat
   int gx = stride == 1 ? 768 : 512;
   while (gx > 8 && (long)gx * 4 > a.nunits) gx -= 8;
-  const bool pro = pro_scale != nullptr;
+  const bool pro = x.pro.scale != nullptr;
   const size_t lds = 2048 + 4 * (size_t)((3 + stride) * (stride * 16 + 2) * 64);
 #define MMVAE_C3(S_, SC_, P_) hipLaunchKernelGGL((conv3_stream_kernel<S_, SC_, P_>), dim3(gx), dim3(256), lds, s, a)
   if (stride == 2) { if (wsc) { if (pro) MMVAE_C3(2, true, true); else MMVAE_C3(2, true, false); } else { if (pro) MMVAE_C3(2, false, true); else MMVAE_C3(2, false, false); } }
@@ -228,11 +229,11 @@ int launch_conv3_stream(int dt, int stride, const void* x, const void* w, const 
 // The data gradient of a 3x3 stride-1 32 -> 32 Conv2d as a forward conv over dy (w: the conv's weights packed [cin][flipped tap][cout]) with
 // the backward sums of the BatchNorm + ReLU in front of that conv from the same pass (rows [sum g][sum g * ym], g masked by ym * ms + mb > 0):
 // encoder.layer1.conv2's dgrad and bn1's reduce in one kernel.  Returns the number of partial rows (> 0) or an error.
-int launch_conv3_stream_bwd(int dt, const void* dy, const void* w_flipped, void* dx, const void* ym, const float* ms, const float* mb, float* sums,
-                            int N, int H, hipStream_t s) {
+int launch_conv3_stream_bwd(int dt, const MapIn& dy, const void* w_flipped, const BnSide& mask, const MapOut& dx, int N, hipStream_t s) {
+  const int H = dy.H; const void* const ym = mask.y; const float* const ms = mask.fwd.scale; const float* const mb = mask.fwd.shift; float* const sums = dx.stats;
   if (dt != DT_BF16 || H != 16 || !ym || !ms || !mb || !sums) { set_error("conv3_stream_bwd: bf16, 16x16 maps, mask operand and sums required"); return MMVAE_ERR_UNSUPPORTED; }
   Conv3StreamArgs a; memset(&a, 0, sizeof(a));
-  a.x = dy; a.w = w_flipped; a.y = dx; a.stats = sums; a.ym = ym; a.ms = ms; a.mb = mb; a.N = N; a.Ho = H; a.Hi = H;
+  a.x = dy.x; a.w = w_flipped; a.y = dx.y; a.stats = sums; a.ym = ym; a.ms = ms; a.mb = mb; a.N = N; a.Ho = H; a.Hi = H;
   a.HS = 8; a.nunits = N * (H / a.HS);
   int gx = 768;
   while (gx > 8 && (long)gx * 4 > a.nunits) gx -= 8;
@@ -839,8 +840,9 @@ bool convT4_stream_ok(int dt, int Cin, int Cout, int k, int s, int p, int Hin, i
   return dt == DT_BF16 && Cin == 16 && Cout == 16 && k == 4 && s == 2 && p == 1 && Hin == Win && (Win == 32 || Win == 16);
 }
 // y [N][2H][2H][16] = conv_transpose2d(x [N][H][H][16]) with the packed per-phase "up" weights; returns stats rows (> 0) or an error
-int launch_convT4_stream(int dt, const void* x, const void* w_up, void* y, const float* pro_scale, const float* pro_shift, int pro_relu, float* stats,
-                         int N, int Hin, hipStream_t s, int f8out) {
+int launch_convT4_stream(int dt, const MapIn& in, const void* w_up, const MapOut& out, int N, hipStream_t s, int f8out) {
+  const int Hin = in.H; const void* const x = in.x; void* const y = out.y; float* const stats = out.stats;
+  const float* const pro_scale = in.pro.scale; const float* const pro_shift = in.pro.shift; const int pro_relu = in.relu;
   if (!convT4_stream_ok(dt, 16, 16, 4, 2, 1, Hin, Hin)) { set_error("convT4_stream: bf16, 16 -> 16 channels, k4 s2 p1, 16x16 or 32x32 input"); return MMVAE_ERR_UNSUPPORTED; }
   ConvT4StreamArgs a; memset(&a, 0, sizeof(a));
   a.x = x; a.w = w_up; a.y = y; a.pro_scale = pro_scale; a.pro_shift = pro_shift; a.pro_relu = pro_relu; a.stats = stats;

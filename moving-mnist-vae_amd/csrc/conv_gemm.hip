@@ -273,6 +273,12 @@ bool make_tile_geom(TileGeom& g, int N, int Hq, int Wq, int Hi, int Wi, int SI, 
 
 constexpr size_t kV2MaxLds = 60 * 1024;
 
+// what PatchArgs / DeepArgs / PosArgs share with the GatherArgs they are made from: the tensors, the prologue, the statistics rows, accumulate
+template <class B> static void copy_operands(B& b, const GatherArgs& a) {
+  b.x = a.x; b.w = a.w; b.y = a.y; b.pro_scale = a.pro_scale; b.pro_shift = a.pro_shift; b.pro_relu = a.pro_relu;
+  b.stats = a.stats; b.accumulate = a.accumulate;
+}
+
 // Pipelined all-phases patch kernel: eligible when the weights of every phase together with one patch fit LDS.
 // Returns >0 (stats rows) when it ran, 0 when not eligible, <0 on error.
 static int try_patch(int dt, int out_dt, const GatherArgs& a, hipStream_t s) {
@@ -286,8 +292,7 @@ static int try_patch(int dt, int out_dt, const GatherArgs& a, hipStream_t s) {
   const int cin_vecs = a.Cin / VE;
   if (!a.x_planar && (256 % cin_vecs) != 0) return 0;
   PatchArgs b; memset(&b, 0, sizeof(b));
-  b.x = a.x; b.w = a.w; b.y = a.y; b.pro_scale = a.pro_scale; b.pro_shift = a.pro_shift; b.pro_relu = a.pro_relu;
-  b.bias = a.bias; b.stats = a.stats; b.accumulate = a.accumulate;
+  copy_operands(b, a); b.bias = a.bias;
   b.Cin = a.Cin; b.Cout = a.Cout; b.Ho = a.Ho; b.Wo = a.Wo; b.SO = a.SO; b.nphase = a.nphase;
   b.x_planar = a.x_planar; b.x_planes = a.x_planes; b.y_planes = a.y_planes;
   int ct16 = (a.Cout + 15) / 16; if (ct16 == 3) ct16 = 4;
@@ -431,14 +436,10 @@ static int try_deep2(int dt, int out_dt, const GatherArgs& a, hipStream_t s, boo
   const int cpt = a.Cin * (a.fp8 ? 1 : ES) / 64;
   DeepArgs b; memset(&b, 0, sizeof(b));
   b.fp8 = a.fp8;
-  b.x = a.x; b.w = a.w; b.y = a.y; b.pro_scale = a.pro_scale; b.pro_shift = a.pro_shift; b.pro_relu = a.pro_relu;
-  b.bias = a.bias; b.stats = a.stats; b.accumulate = a.accumulate; b.wfrag = a.wfrag;
+  copy_operands(b, a); b.bias = a.bias; b.wfrag = a.wfrag;
   b.N = a.N; b.Hi = a.Hi; b.Wi = a.Wi; b.Cin = a.Cin; b.Ho = a.Ho; b.Wo = a.Wo; b.Cout = a.Cout; b.SI = a.SI; b.SO = a.SO;
   b.nphase = a.nphase; b.Hq = Hq; b.Wq = Wq; b.ntaps_all = ntaps_all;
-  for (int p = 0; p < a.nphase; ++p) {
-    const Phase& ph = a.phases[p];
-    b.phases[p] = DeepPhase{ph.ph, ph.pw, ph.Hq, ph.Wq, ph.ntaps, ph.tap0, ph.w_off};
-  }
+  for (int p = 0; p < a.nphase; ++p) b.phases[p] = a.phases[p];
   for (int t = 0; t < kMaxTaps; ++t) b.taps[t] = a.taps[t];
   for (b.cpt_log2 = 0; (1 << b.cpt_log2) < cpt; ++b.cpt_log2) {}
   b.nw = a.Cout / 32 < 8 ? a.Cout / 32 : 8;
@@ -480,8 +481,7 @@ static int try_pos(int dt, int out_dt, const GatherArgs& a, hipStream_t s, bool 
   if (a.Hi >= 8 && a.Cout < 128) return 0;      // an 8x8 input tile is 131 KB of LDS (one block per CU): with two waves per block deep2 wins (measured)
   if ((long)a.N * a.Ho * a.Wo * a.Cout >= (1L << 32)) return 0;
   PosArgs b; memset(&b, 0, sizeof(b));
-  b.x = a.x; b.w = a.w; b.y = a.y; b.pro_scale = a.pro_scale; b.pro_shift = a.pro_shift; b.pro_relu = a.pro_relu;
-  b.stats = a.stats; b.accumulate = a.accumulate; b.N = a.N; b.Cout = a.Cout;
+  copy_operands(b, a); b.N = a.N; b.Cout = a.Cout;
   b.nw = a.Cout / 32 < 8 ? a.Cout / 32 : 8;
   if ((a.Cout / 32) % b.nw != 0 || (64 * b.nw) % (a.Cin / 8) != 0) return 0;
   return launch_pos_conv(a.gk, a.gs, a.gp, up, a.Hi, a.Ho, a.Cin, dry ? nullptr : &b, s);
@@ -801,11 +801,7 @@ static int try_wgrad2(int dt, const WgradArgs& a, hipStream_t s) {
   b.dW = a.scratch; b.partial = 1;
   const int rc = launch_wgrad2(dt, b, (int)gx, tiles_ab, zg, ta16, tb16, s);
   if (rc < 0) return rc;
-  WgradReduceArgs u; memset(&u, 0, sizeof(u));
-  u.part = a.scratch; u.dW = a.dW; u.Ca = a.Ca; u.Cb = a.Cb; u.ntaps = a.ntaps; u.nparts = (int)gx;
-  u.Ca_valid = a.Ca_valid; u.Cb_valid = a.Cb_valid; u.sA = a.sA; u.sB = a.sB; u.scale = a.scale;
-  for (int t = 0; t < 25; ++t) u.tap_off[t] = a.tap_off[t];
-  const int rc2 = launch_wgrad_reduce(u, s);
+  const int rc2 = launch_wgrad_reduce(reduce_args(a, a.scratch, (int)gx), s);
   return rc2 < 0 ? rc2 : 1;
 }
 
@@ -860,10 +856,7 @@ int launch_wgrad(int dt, WgradArgs a, hipStream_t s) {
   a.pix_per_block = (int)(steps_per * PK);
   const int gx = (int)(((long)a.M + a.pix_per_block - 1) / a.pix_per_block);
   dim3 grid(gx, tiles, zg), block(256);
-  WgradReduceArgs u; memset(&u, 0, sizeof(u));
-  u.part = a.scratch; u.dW = a.dW; u.Ca = a.Ca; u.Cb = a.Cb; u.ntaps = a.ntaps; u.nparts = gx;
-  u.Ca_valid = a.Ca_valid; u.Cb_valid = a.Cb_valid; u.sA = a.sA; u.sB = a.sB; u.scale = a.scale;
-  for (int t = 0; t < 25; ++t) u.tap_off[t] = a.tap_off[t];
+  const WgradReduceArgs u = reduce_args(a, a.scratch, gx);
   // the reduce's refusals (an image that is no multiple of 256 elements: bf16 8 -> 8 1x1, f32 4 -> 4) come before the first launch, like
   // every other refusal of this path: nothing is enqueued and the scratch stays as it was
   if (const int rcr = wgrad_reduce_check(u); rcr < 0) { note_launch_bytes(0.0); return rcr; }     // (no launch will take the bytes noted above)

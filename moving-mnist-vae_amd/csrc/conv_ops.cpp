@@ -63,33 +63,30 @@ int op_pack_up(int dt, const ConvGeom& g, const float* w, void* dst, hipStream_t
   return MMVAE_OK;
 }
 
-static void wgrad_args(WgradArgs& a, const ConvGeom& g, int N, const void* P, int Hs, int Ws, const float* proP_s, const float* proP_b, int proP_relu,
-                       const void* G, int Hl, int Wl, const float* proG_s, const float* proG_b, int proG_relu, float* dW, float* scratch, float scale) {
+void wgrad_args(WgradArgs& a, const ConvGeom& g, int N, const MapIn& P, const MapIn& G, float* dW, float* scratch, float scale, int ntaps) {
   std::memset(&a, 0, sizeof(a));
   const int kk = g.k * g.k;
-  a.P = P; a.G = G; a.dW = dW; a.scratch = scratch;
-  a.proP_scale = proP_s; a.proP_shift = proP_b; a.proP_relu = proP_relu;
-  a.proG_scale = proG_s; a.proG_shift = proG_b; a.proG_relu = proG_relu;
-  a.N = N; a.Hp = Hs; a.Wp = Ws; a.Ca = g.D0; a.Hg = Hl; a.Wg = Wl; a.Cb = g.D1; a.Cb_valid = g.D1; a.Ca_valid = g.D0;
-  a.stride = g.s; a.pad = g.p; a.ksz = g.k; a.sA = g.D1 * kk; a.sB = kk; a.ntaps = kk; a.scale = scale;
-  for (int t = 0; t < kk && t < 25; ++t) a.tap_off[t] = t;
+  if (ntaps <= 0) ntaps = kk;
+  a.P = P.x; a.G = G.x; a.dW = dW; a.scratch = scratch;
+  a.proP_scale = P.pro.scale; a.proP_shift = P.pro.shift; a.proP_relu = P.relu;
+  a.proG_scale = G.pro.scale; a.proG_shift = G.pro.shift; a.proG_relu = G.relu;
+  a.N = N; a.Hp = P.H; a.Wp = P.W; a.Ca = g.D0; a.Hg = G.H; a.Wg = G.W; a.Cb = g.D1; a.Cb_valid = g.D1; a.Ca_valid = g.D0;
+  a.stride = g.s; a.pad = g.p; a.ksz = g.k; a.sA = g.D1 * kk; a.sB = kk; a.ntaps = ntaps; a.scale = scale;
+  for (int t = 0; t < ntaps && t < 25; ++t) a.tap_off[t] = t;
 }
 
-// The GatherArgs of a run_down / run_up launch, without the data pointers and the per-call options (prologue, statistics, accumulate, second
-// source, weight layout): op_run_down / op_run_up fill those in, the layout queries below ask the dispatcher with them left null.
-static bool down_args(GatherArgs& a, const ConvGeom& g, int N, int Hl, int Wl, int Hs, int Ws) {
+bool down_args(GatherArgs& a, const ConvGeom& g, int N, int Hl, int Wl, int Hs, int Ws, int ntaps) {
   std::memset(&a, 0, sizeof(a));
-  if (g.k * g.k > kMaxTaps) return false;
+  if (ntaps <= 0) ntaps = g.k * g.k;
+  if (ntaps > kMaxTaps || ntaps > g.k * g.k) return false;
   a.N = N; a.Hi = Hl; a.Wi = Wl; a.Cin = g.D1; a.Ho = Hs; a.Wo = Ws; a.Cout = g.D0; a.SI = g.s; a.SO = 1;
   a.gk = g.k; a.gs = g.s; a.gp = g.p; a.gup = 1;
   a.nphase = 1;
-  a.phases[0] = Phase{0, 0, Hs, Ws, g.k * g.k, 0, 0};
-  for (int kh = 0; kh < g.k; ++kh)
-    for (int kw = 0; kw < g.k; ++kw) a.taps[kh * g.k + kw] = Tap{kh - g.p, kw - g.p};
+  a.phases[0] = Phase{0, 0, Hs, Ws, ntaps, 0, 0};
+  for (int t = 0; t < ntaps; ++t) a.taps[t] = Tap{t / g.k - g.p, t % g.k - g.p};
   return true;
 }
-// skip_empty: stride phases without a tap are left out (the launch accumulates, or is a second source) instead of being zero-filled
-static bool up_args(GatherArgs& a, const ConvGeom& g, int N, int Hs, int Ws, int Hl, int Wl, bool skip_empty) {
+bool up_args(GatherArgs& a, const ConvGeom& g, int N, int Hs, int Ws, int Hl, int Wl, bool skip_empty) {
   std::memset(&a, 0, sizeof(a));
   if (g.s > 2 || g.k * g.k > kMaxTaps) return false;
   a.N = N; a.Hi = Hs; a.Wi = Ws; a.Cin = g.D0; a.Ho = Hl; a.Wo = Wl; a.Cout = g.D1; a.SI = 1; a.SO = g.s;
@@ -134,86 +131,100 @@ ConvLayout op_up_layout(int dt, const ConvGeom& g, int Hl, int Wl, int allow_emp
   return layout_of(dt, a);
 }
 
-int op_run_down(int dt, int out_dt, const ConvGeom& g, const void* packed, int N, const void* L, int Hl, int Wl, void* S, int Hs, int Ws,
-                const float* pro_s, const float* pro_b, int relu, float* stats, int accumulate, hipStream_t s, const SecondSrc& x2) {
-  GatherArgs a;
-  if (!down_args(a, g, N, Hl, Wl, Hs, Ws)) { set_error("run_down: k=%d too large", g.k); return MMVAE_ERR_UNSUPPORTED; }
+// the prologue, statistics rows and accumulate of a launch's operands, its second source and the layout of its packed weights
+static void set_operands(GatherArgs& a, const void* packed, const MapIn& in, const MapOut& out, const SecondSrc& x2) {
   if (x2.x2) { a.x2 = x2.x2; a.w2 = x2.w2; a.Cin2 = x2.Cin2; a.x2_ph = 0; a.x2_pw = 0; }
   a.fp8 = x2.fp8; a.wfrag = x2.wfrag; a.wfrag2 = x2.wfrag2;
-  a.x = L; a.w = packed; a.y = S;
-  a.pro_scale = pro_s; a.pro_shift = pro_b; a.pro_relu = relu; a.stats = stats; a.accumulate = accumulate;
+  a.x = in.x; a.w = packed; a.y = out.y;
+  a.pro_scale = in.pro.scale; a.pro_shift = in.pro.shift; a.pro_relu = in.relu; a.stats = out.stats; a.accumulate = out.accumulate;
+}
+
+int op_run_down(int dt, int out_dt, const ConvGeom& g, const void* packed, const MapIn& L, const MapOut& S, int N, hipStream_t s, const SecondSrc& x2) {
+  GatherArgs a;
+  if (!down_args(a, g, N, L.H, L.W, S.H, S.W)) { set_error("run_down: k=%d too large", g.k); return MMVAE_ERR_UNSUPPORTED; }
+  set_operands(a, packed, L, S, x2);
   return launch_gather_gemm(dt, out_dt, a, s);
 }
 
-int op_run_up(int dt, const ConvGeom& g, const void* packed, int N, const void* S, int Hs, int Ws, void* L, int Hl, int Wl,
-              const float* pro_s, const float* pro_b, int relu, float* stats, int accumulate, hipStream_t s, const SecondSrc& x2) {
+int op_run_up(int dt, const ConvGeom& g, const void* packed, const MapIn& S, const MapOut& L, int N, hipStream_t s, const SecondSrc& x2) {
   GatherArgs a;
-  if (!up_args(a, g, N, Hs, Ws, Hl, Wl, accumulate != 0)) { set_error("run_up: k=%d s=%d unsupported", g.k, g.s); return MMVAE_ERR_UNSUPPORTED; }
-  if (x2.x2) { a.x2 = x2.x2; a.w2 = x2.w2; a.Cin2 = x2.Cin2; a.x2_ph = 0; a.x2_pw = 0; }
-  a.fp8 = x2.fp8; a.wfrag = x2.wfrag; a.wfrag2 = x2.wfrag2;
-  a.x = S; a.w = packed; a.y = L;
-  a.pro_scale = pro_s; a.pro_shift = pro_b; a.pro_relu = relu; a.stats = stats; a.accumulate = accumulate;
+  if (!up_args(a, g, N, S.H, S.W, L.H, L.W, L.accumulate != 0)) { set_error("run_up: k=%d s=%d unsupported", g.k, g.s); return MMVAE_ERR_UNSUPPORTED; }
+  set_operands(a, packed, S, L, x2);
   if (a.nphase == 0) return 1;
   return launch_gather_gemm(dt, dt, a, s);
 }
 
-int op_run_wgrad(int dt, const ConvGeom& g, int N, const void* P, int Hs, int Ws, const float* proP_s, const float* proP_b, int proP_relu,
-                 const void* G, int Hl, int Wl, const float* proG_s, const float* proG_b, int proG_relu, float* dW, hipStream_t s,
-                 float* scratch, float scale, WgradReduceArgs* defer) {
+int op_run_wgrad(int dt, const ConvGeom& g, const MapIn& P, const MapIn& G, float* dW, int N, hipStream_t s, const WgradOpts& o) {
   if (g.k * g.k > 25) { set_error("wgrad: k=%d too large", g.k); return MMVAE_ERR_UNSUPPORTED; }
-  if (defer) defer->nparts = 0;
+  if (o.defer) o.defer->nparts = 0;
   WgradArgs a;
-  wgrad_args(a, g, N, P, Hs, Ws, proP_s, proP_b, proP_relu, G, Hl, Wl, proG_s, proG_b, proG_relu, dW, scratch, scale);
-  a.defer = defer;
+  wgrad_args(a, g, N, P, G, dW, o.scratch, o.scale);
+  a.defer = o.defer;
   return launch_wgrad(dt, a, s);
 }
 
 // A 3x3 stride-2 conv and the 1x1 stride-2 shortcut on the same input (a residual block's conv1 / downsample.0): both weight gradients from one
 // pass over the block input.  Returns 1 when taken, 0 when the shapes are not the stream kernel's (the caller runs the two separately), <0 on error.
-int op_run_wgrad_pair(int dt, const ConvGeom& g, const ConvGeom& gs, int N, const void* P, const void* P2, int Hs, int Ws, const void* G, int Hl, int Wl,
-                      const float* proG_s, const float* proG_b, int proG_relu, float* dW, float* dW2, hipStream_t s, float* scratch, float scale,
-                      float scale2) {
+int op_run_wgrad_pair(int dt, const ConvGeom& g, const ConvGeom& gs, const MapIn& P, const void* P2, const MapIn& G, float* dW, float* dW2, int N,
+                      hipStream_t s, const WgradOpts& o) {
   if (g.k != 3 || g.p != 1 || gs.k != 1 || gs.p != 0 || gs.s != g.s || gs.D0 != g.D0 || gs.D1 != g.D1) return 0;
   WgradArgs a;
-  wgrad_args(a, g, N, P, Hs, Ws, nullptr, nullptr, 0, G, Hl, Wl, proG_s, proG_b, proG_relu, dW, scratch, scale);
-  return try_wgrad_stream_pair(dt, a, P2, dW2, scale2, s);
+  wgrad_args(a, g, N, MapIn(P.x, P.H, P.W), G, dW, o.scratch, o.scale);      // (no prologue on the dy side)
+  return try_wgrad_stream_pair(dt, a, P2, dW2, o.scale2, s);
 }
 
+// The shape predicates: the launch's WgradArgs without data.  The kernels' conditions want a scratch (its address is not used).
+static bool shape_args(WgradArgs& a, const ConvGeom& g, const MapIn& P, const MapIn& G, int N) {
+  static float scratch = 0.f;
+  if (g.k * g.k > 25) return false;
+  wgrad_args(a, g, N, P, G, nullptr, &scratch);
+  return true;
+}
 // whether op_run_wgrad runs this layer on the per-wave stream kernel (whose partial images are <= 19 MB and whose reduce can be deferred)
-bool op_wgrad_is_stream(int dt, const ConvGeom& g, int N, int Hs, int Ws, int Hl, int Wl, bool proP, bool proG) {
-  if (g.k * g.k > 25) return false;
+bool op_wgrad_is_stream(int dt, const ConvGeom& g, const MapIn& P, const MapIn& G, int N) {
   WgradArgs a;
-  float dummy = 0.f;
-  wgrad_args(a, g, N, nullptr, Hs, Ws, proP ? &dummy : nullptr, proP ? &dummy : nullptr, 1, nullptr, Hl, Wl, proG ? &dummy : nullptr, proG ? &dummy : nullptr, 1,
-             nullptr, &dummy, 1.f);
-  return wgrad_stream_shape(dt, a);
+  return shape_args(a, g, P, G, N) && wgrad_stream_shape(dt, a);
+}
+bool op_bwd_fusable(int dt, const ConvGeom& g, const MapIn& P, const MapIn& G, int N) {
+  WgradArgs a;
+  return shape_args(a, g, MapIn(nullptr, P.H, P.W), MapIn(nullptr, G.H, G.W), N) && dgrad_wgrad_stream_shape(dt, a);
+}
+// whether op_run_bwd_fused takes this layer with a join gradient `jg` (see kernels.hpp)
+bool op_bwd_fusable_jg(int dt, const ConvGeom& g, const MapIn& P, const MapIn& G, int N, bool has_x2, bool bn_sums) {
+  WgradArgs a;
+  return shape_args(a, g, P, MapIn(nullptr, G.H, G.W), N) && dgrad_wgrad_stream_jg_shape(dt, a, has_x2, bn_sums);
 }
 
-bool op_bwd_fusable(int dt, const ConvGeom& g, int N, int Hs, int Ws, int Hl, int Wl) {
-  if (g.k * g.k > 25) return false;
-  WgradArgs a;
-  float dummy = 0.f;
-  wgrad_args(a, g, N, nullptr, Hs, Ws, nullptr, nullptr, 0, nullptr, Hl, Wl, nullptr, nullptr, 0, nullptr, &dummy, 1.f);
-  return dgrad_wgrad_stream_shape(dt, a);
-}
-
-int op_run_bwd_fused(int dt, const ConvGeom& g, int N, const void* P, int Hs, int Ws, const float* proP_s, const float* proP_b, int proP_relu,
-                     const void* G, int Hl, int Wl, const void* packed_down, void* dP, const void* x2, const void* w2_packed, float* dW,
-                     hipStream_t s, float* scratch, float scale, float* bn_part, float* dW2, float scale2, const BnSide* jg) {
+int op_run_bwd_fused(int dt, const ConvGeom& g, const void* packed_down, const MapIn& P, const MapIn& G, const SecondSrc& x2, void* dP, float* dW, int N,
+                     hipStream_t s, const WgradOpts& o) {
   if (g.k * g.k > 25) return 0;
   WgradArgs a;
-  wgrad_args(a, g, N, P, Hs, Ws, proP_s, proP_b, proP_relu, G, Hl, Wl, nullptr, nullptr, 0, dW, scratch, scale);
+  wgrad_args(a, g, N, P, MapIn(G.x, G.H, G.W), dW, o.scratch, o.scale);      // (G is a gradient: no prologue)
   a.M = a.N * a.Hp * a.Wp;
-  return try_dgrad_wgrad_stream(dt, a, packed_down, dP, x2, w2_packed, bn_part, s, dW2, scale2, jg);
+  return try_dgrad_wgrad_stream(dt, a, packed_down, dP, x2.x2, x2.w2, o.bn_part, s, o.dW2, o.scale2, o.jg);
 }
 
-// whether op_run_bwd_fused takes this layer with a join gradient `jg` (see kernels.hpp)
-bool op_bwd_fusable_jg(int dt, const ConvGeom& g, int N, int Hs, int Ws, int Hl, int Wl, bool proP, bool has_x2, bool bn_sums) {
-  if (g.k * g.k > 25) return false;
-  WgradArgs a;
-  float dummy = 0.f;
-  wgrad_args(a, g, N, nullptr, Hs, Ws, proP ? &dummy : nullptr, proP ? &dummy : nullptr, 1, nullptr, Hl, Wl, nullptr, nullptr, 0, nullptr, &dummy, 1.f);
-  return dgrad_wgrad_stream_jg_shape(dt, a, has_x2, bn_sums);
+int op_pack_flipped3(int dt, const float* w, void* dst, int Cin, int Cout, hipStream_t s, float scale) {
+  PackArgs pf; std::memset(&pf, 0, sizeof(pf));
+  pf.src = w; pf.dst = dst; pf.cols = Cin; pf.K = Cout; pf.ntaps = 9; pf.s_col = 9; pf.s_k = Cin * 9; pf.scale = scale;
+  for (int t = 0; t < 9; ++t) pf.tap_off[t] = 8 - t;
+  return launch_pack(dt, pf, s);
+}
+
+static inline int stem_cpad(int dt) { return dt == DT_F32 ? 4 : 8; }
+int op_pack_stem(int dt, const float* w, int in_ch, void* dst, hipStream_t s) {
+  PackArgs pa; std::memset(&pa, 0, sizeof(pa));
+  pa.src = w; pa.dst = dst;
+  pa.cols = 32; pa.K = stem_cpad(dt); pa.K_valid = in_ch; pa.ntaps = 25; pa.s_col = 25 * in_ch; pa.s_k = 25; pa.scale = 1.f;
+  for (int t = 0; t < 25; ++t) pa.tap_off[t] = t;
+  return launch_pack(dt, pa, s);
+}
+int op_run_stem(int dt, const void* packed, const void* x, int in_ch, int S, const MapOut& y, int N, hipStream_t s) {
+  GatherArgs a;
+  down_args(a, ConvGeom{32, stem_cpad(dt), 5, 2, 2}, N, S, S, y.H, y.W);
+  a.x = x; a.w = packed; a.y = y.y; a.stats = y.stats;
+  a.x_planar = 2; a.x_planes = in_ch;
+  return launch_gather_gemm(dt, dt, a, s);
 }
 
 }  // namespace mmvae

@@ -267,10 +267,8 @@ int try_wgrad_pos(int dt, const WgradArgs& a, hipStream_t s) {
   if (!launched) return 0;
   const int rc = check_launch("wgrad_pos");
   if (rc) return rc;
-  WgradReduceArgs u; std::memset(&u, 0, sizeof(u));
-  u.part = a.scratch; u.dW = a.dW; u.Ca = a.Ca; u.Cb = a.Cb; u.ntaps = a.ntaps; u.nparts = nsplit;
-  u.Ca_valid = a.Ca; u.Cb_valid = a.Cb; u.sA = a.sA; u.sB = a.sB; u.scale = a.scale;
-  for (int t = 0; t < 25; ++t) u.tap_off[t] = a.tap_off[t];
+  WgradReduceArgs u = reduce_args(a, a.scratch, nsplit);
+  u.Ca_valid = a.Ca; u.Cb_valid = a.Cb;      // (a's own may be 0 = all; checked above)
   const int rr = launch_wgrad_reduce(u, s);
   return rr < 0 ? rr : 1;
 }

@@ -549,17 +549,13 @@ static int wstream_fill(const WgradArgs& a, WStreamArgs& b, int kind, bool x2 = 
 }
 // dW2 (optional, X2 passes): the 1x1 conv's weight (16 outputs = x2 channels, Ca inputs = P channels, row-major) receives the extra image
 static int wstream_reduce(const WgradArgs& a, int gx, hipStream_t s, bool x2 = false, float* dW2 = nullptr, float scale2 = 1.f) {
-  WgradReduceArgs u; memset(&u, 0, sizeof(u));
-  u.part = a.scratch; u.dW = a.dW; u.Ca = a.Ca; u.Cb = a.Cb; u.ntaps = a.ntaps; u.nparts = gx;
-  u.Ca_valid = a.Ca_valid; u.Cb_valid = a.Cb_valid; u.sA = a.sA; u.sB = a.sB; u.scale = a.scale;
+  WgradReduceArgs u = reduce_args(a, a.scratch, gx);
   u.part_stride = (long)a.ntaps * a.Ca * a.Cb + (x2 ? 16L * a.Ca : 0);
-  for (int t = 0; t < 25; ++t) u.tap_off[t] = a.tap_off[t];
   if (a.defer && !x2) { *a.defer = u; return 0; }
   const int rc = launch_wgrad_reduce(u, s);
   if (rc < 0 || !x2 || !dW2) return rc;
-  WgradReduceArgs v; memset(&v, 0, sizeof(v));
-  v.part = a.scratch + (long)a.ntaps * a.Ca * a.Cb; v.part_stride = u.part_stride; v.dW = dW2; v.Ca = 16; v.Cb = a.Ca; v.ntaps = 1; v.nparts = gx;
-  v.Ca_valid = 16; v.Cb_valid = a.Ca; v.sA = a.Ca; v.sB = 1; v.scale = scale2;
+  WgradReduceArgs v = reduce_args(a.scratch + (long)a.ntaps * a.Ca * a.Cb, gx, dW2, 16, a.Ca, 1, scale2);
+  v.part_stride = u.part_stride;
   return launch_wgrad_reduce(v, s);
 }
 
@@ -605,16 +601,12 @@ int try_wgrad_stream_pair(int dt, const WgradArgs& a, const void* P2, float* dW2
   const int rc = a.proG_scale ? launch_wstream_t<3, 2, 1, 16, 2, 2, false, true, false, false, false, 2, true>(b, gx, s)
                               : launch_wstream_t<3, 2, 1, 16, 2, 2, false, false, false, false, false, 2, true>(b, gx, s);
   if (rc < 0) return rc;
-  WgradReduceArgs u; memset(&u, 0, sizeof(u));
-  u.part = a.scratch; u.dW = a.dW; u.Ca = a.Ca; u.Cb = a.Cb; u.ntaps = a.ntaps; u.nparts = gx;
-  u.Ca_valid = a.Ca_valid; u.Cb_valid = a.Cb_valid; u.sA = a.sA; u.sB = a.sB; u.scale = a.scale;
+  WgradReduceArgs u = reduce_args(a, a.scratch, gx);
   u.part_stride = (long)(a.ntaps + 1) * a.Ca * a.Cb;
-  for (int t = 0; t < 25; ++t) u.tap_off[t] = a.tap_off[t];
   int rc2 = launch_wgrad_reduce(u, s);
   if (rc2 < 0) return rc2;
-  WgradReduceArgs v; memset(&v, 0, sizeof(v));
-  v.part = a.scratch + (long)a.ntaps * a.Ca * a.Cb; v.part_stride = u.part_stride; v.dW = dW2; v.Ca = a.Ca; v.Cb = a.Cb; v.ntaps = 1; v.nparts = gx;
-  v.Ca_valid = a.Ca; v.Cb_valid = a.Cb; v.sA = a.Cb; v.sB = 1; v.scale = scale2;
+  WgradReduceArgs v = reduce_args(a.scratch + (long)a.ntaps * a.Ca * a.Cb, gx, dW2, a.Ca, a.Cb, 1, scale2);
+  v.part_stride = u.part_stride;
   rc2 = launch_wgrad_reduce(v, s);
   return rc2 < 0 ? rc2 : 1;
 }

@@ -14,6 +14,33 @@ struct BnCoef { const float* A = nullptr; const float* B = nullptr; const float*
 // a pre-BatchNorm tensor with its rows: one side of a residual join, or a consumer's input under its BatchNorm + ReLU prologue (bwd unused)
 struct BnSide { const void* y = nullptr; Affine fwd; BnCoef bwd; };
 
+// ---------------------------------------------------------------- the conv path's operands (conv_ops.hpp, the stream launchers below, Net::run_*)
+// One argument per tensor here as well, in the same order: input maps, output maps, the batch size, the stream, then defaulted options.
+// An input map: the tensor [N][H][W][C], and the prologue its consumer applies on load, relu?(x * pro.scale + pro.shift) (pro empty: x as it is).
+// From a BnSide the ReLU is on: a consumer's input under its BatchNorm + ReLU.  Without a size (Net::run_*) the callee fills it in from the layer.
+struct MapIn {
+  const void* x = nullptr; int H = 0, W = 0; Affine pro; int relu = 0;
+  MapIn() = default;
+  MapIn(const void* x_) : x(x_) {}
+  MapIn(const void* x_, int H_, int W_, Affine pro_ = Affine(), int relu_ = 0) : x(x_), H(H_), W(W_), pro(pro_), relu(relu_) {}
+  MapIn(const BnSide& t) : x(t.y), pro(t.fwd), relu(1) {}
+  MapIn(const BnSide& t, int H_, int W_, int relu_ = 1) : x(t.y), H(H_), W(W_), pro(t.fwd), relu(relu_) {}
+  // the operand of a shape query: no data; has_pro says whether the launch will carry a prologue -- the predicates test pro.scale for null and
+  // read nothing through it, so it points at a constant here and nowhere else
+  static MapIn shape(int H_, int W_, bool has_pro = false) {
+    static const float one = 1.f;
+    return has_pro ? MapIn(nullptr, H_, W_, Affine{&one, &one}, 1) : MapIn(nullptr, H_, W_);
+  }
+};
+// An output map: the tensor, the BatchNorm statistics rows its producer leaves (nullable), and whether the result is added to what y holds.
+struct MapOut {
+  void* y = nullptr; int H = 0, W = 0; float* stats = nullptr; int accumulate = 0;
+  MapOut() = default;
+  MapOut(void* y_, float* stats_ = nullptr) : y(y_), stats(stats_) {}
+  MapOut(void* y_, int H_, int W_, float* stats_ = nullptr, int accumulate_ = 0) : y(y_), H(H_), W(W_), stats(stats_), accumulate(accumulate_) {}
+  static MapOut add(void* y_, int H_ = 0, int W_ = 0) { return MapOut(y_, H_, W_, nullptr, 1); }     // y += result
+};
+
 // ---------------------------------------------------------------- gather GEMM
 // y[n, hq*SO+ph, wq*SO+pw, co] (+)= bias[co] + sum_{t<ntaps} sum_{ci}
 //        pro(x[n, hq*SI+dh[t], wq*SI+dw[t], ci]) * w[co][t][ci]
@@ -143,6 +170,22 @@ size_t gather3_lds_bytes(const GatherArgs& a, int dt, int CT);
 int launch_gather3(int dt, int out_dt, const GatherArgs& a, int gx, hipStream_t s);
 struct WgradReduceArgs { const float* part; float* dW; int Ca, Cb, ntaps, nparts, Ca_valid, Cb_valid, sA, sB; int tap_off[25]; float scale; int exclusive;
                          long part_stride; /* floats between two partial images (0: ntaps * Ca * Cb) */ };
+// the reduce of the nparts partial images a kernel left at `part` for the weight gradient `a`: a's image shape, weight strides, taps and scale
+inline WgradReduceArgs reduce_args(const WgradArgs& a, const float* part, int nparts) {
+  WgradReduceArgs u = {};
+  u.part = part; u.dW = a.dW; u.Ca = a.Ca; u.Cb = a.Cb; u.ntaps = a.ntaps; u.nparts = nparts;
+  u.Ca_valid = a.Ca_valid; u.Cb_valid = a.Cb_valid; u.sA = a.sA; u.sB = a.sB; u.scale = a.scale;
+  for (int t = 0; t < 25; ++t) u.tap_off[t] = a.tap_off[t];
+  return u;
+}
+// ... and of whole images [Ca][Cb][ntaps] into a dense weight of that shape (the fused backward passes' partial images)
+inline WgradReduceArgs reduce_args(const float* part, int nparts, float* dW, int Ca, int Cb, int ntaps, float scale = 1.f) {
+  WgradReduceArgs u = {};
+  u.part = part; u.dW = dW; u.Ca = Ca; u.Cb = Cb; u.ntaps = ntaps; u.nparts = nparts;
+  u.Ca_valid = Ca; u.Cb_valid = Cb; u.sA = Cb * ntaps; u.sB = ntaps; u.scale = scale;
+  for (int t = 0; t < ntaps && t < 25; ++t) u.tap_off[t] = t;
+  return u;
+}
 int launch_wgrad_reduce(WgradReduceArgs a, hipStream_t s);
 int wgrad_reduce_check(WgradReduceArgs a);        // launch_wgrad_reduce's refusals alone (< 0), nothing enqueued: asked before the producing kernel is
 constexpr size_t kWgradScratchBytes = 64u << 20;   // capacity of the partial-image scratch every wgrad caller provides
@@ -169,7 +212,7 @@ void patch_conv_x2_carve(PatchArgs& a, int dt);
 int patch_conv_slots(const PatchArgs& a, int dt);
 int launch_patch_conv(int dt, int out_dt, const PatchArgs& a, int gx, hipStream_t s);   // returns stats rows (= gx) or <0
 // ---- deep-layer implicit GEMM (conv_deep2.inc): resident unpadded patch, weights from L2 straight into MFMA fragments
-struct DeepPhase { int ph, pw, Hq, Wq, ntaps, tap0; long w_off; };
+using DeepPhase = Phase;
 struct DeepArgs {
   const void* x; const void* w; void* y;
   const float* pro_scale; const float* pro_shift; int pro_relu;
@@ -225,15 +268,15 @@ bool stem_bwd_fusable(int S);
 // 32 -> 32 channel 3x3 forward convs on 16-pixel-wide output maps as a per-wave stream, optionally with the block's 1x1 stride-2 shortcut
 // from the same input rows (conv_fstream.hip): returns stats rows (> 0) or an error
 bool conv3_stream_ok(int dt, int Cin, int Cout, int k, int s, int p, int Hin, int Win);
-int launch_conv3_stream_bwd(int dt, const void* dy, const void* w_flipped, void* dx, const void* ym, const float* ms, const float* mb, float* sums,
-                            int N, int H, hipStream_t s);
-int launch_conv3_stream(int dt, int stride, const void* x, const void* w, const void* wsc, void* y, void* ysc, const float* pro_scale,
-                        const float* pro_shift, int pro_relu, float* stats, float* stats_sc, int N, int Ho, hipStream_t s);
+// dy (H x H, no prologue) -> dx, with the backward sums (dx.stats) of the BatchNorm + ReLU `mask` = the conv's input under its rows
+int launch_conv3_stream_bwd(int dt, const MapIn& dy, const void* w_flipped, const BnSide& mask, const MapOut& dx, int N, hipStream_t s);
+// x -> y (y.H x 16; x is stride * y.H wide), and (ysc.y, with wsc) the 1x1 stride-2 shortcut's output from the same rows
+int launch_conv3_stream(int dt, int stride, const MapIn& x, const void* w, const void* wsc, const MapOut& y, const MapOut& ysc, int N,
+                        hipStream_t s);
 // ConvTranspose2d(16 -> 16, k4 s2 p1) forward on 16x16 / 32x32 inputs as a per-wave stream (conv_fstream.hip)
 bool convT4_stream_ok(int dt, int Cin, int Cout, int k, int s, int p, int Hin, int Win);
-int launch_convT4_stream(int dt, const void* x, const void* w_up, void* y, const float* pro_scale, const float* pro_shift, int pro_relu, float* stats,
-                         int N, int Hin, hipStream_t s, int f8out = 0);    // f8out: y leaves as e4m3 bytes (32x32 inputs only)
-                                                                           // y == nullptr (not with f8out): the statistics alone, same partial rows
+int launch_convT4_stream(int dt, const MapIn& x, const void* w_up, const MapOut& y, int N, hipStream_t s, int f8out = 0);
+// x.H x x.H -> twice that; f8out: y leaves as e4m3 bytes (32x32 inputs only); y.y == nullptr (not with f8out): the statistics alone, same partial rows
 // last up-block join + one-plane tail conv as a per-wave MFMA stream (conv_fstream.hip; bf16, 64x64): returns stats rows or an error
 bool tail_fwd_stream_ok(int dt, int OC, int H, int W);
 int launch_tail_fwd_stream(int dt, const BnSide& y2, const BnSide& ys, const float* w, const float* bias, float* r_raw, float* stats, int N, int H,

@@ -8,6 +8,8 @@
 
 #include <cstring>
 
+#include "conv_ops.hpp"
+
 namespace mmvae {
 
 #define MM_TRY(expr)            \
@@ -58,13 +60,9 @@ const PixelPlan& PixelNet::plan(int N, int S) {
   return plan_;
 }
 
-// taps of layer L: t = 7 kh + kw for the first ntaps positions; forward offset (kh - 3, kw - 3), data gradient the mirrored one
-static void fill_taps(GatherArgs& a, int ntaps, bool mirrored) {
-  for (int t = 0; t < ntaps; ++t) {
-    const int kh = t / 7, kw = t % 7;
-    a.taps[t] = mirrored ? Tap{3 - kh, 3 - kw} : Tap{kh - 3, kw - 3};
-  }
-}
+// A layer is a 7x7 stride-1 pad-3 conv masked to its first ntaps taps, t = 7 kh + kw: forward offset (kh - 3, kw - 3) -- down_args' order --,
+// data gradient the mirrored one
+static inline ConvGeom geom7(int D0, int D1) { return ConvGeom{D0, D1, 7, 1, 3}; }
 
 int PixelNet::pack(const float* params, char* base, bool data_grad, hipStream_t s) {
   const PixelPlan& P = plan_;
@@ -97,11 +95,9 @@ int PixelNet::conv(int i, int N, int S, const void* x, const float* params, char
     MM_TRY(launch_fill_f32(bias, 0.f, 16, s));
     if (hipMemcpyAsync(bias, params + L.b_off, (size_t)L.cout * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) { set_error("pixelcnn: bias copy failed"); return MMVAE_ERR_HIP; }
   }
-  GatherArgs a; std::memset(&a, 0, sizeof(a));
+  GatherArgs a;
+  down_args(a, geom7(L.cout_p, L.cin_p), N, S, S, S, S, L.ntaps);
   a.x = x; a.w = base + P.packed + L.packF * e; a.y = base + P.h[i]; a.bias = bias;
-  a.N = N; a.Hi = S; a.Wi = S; a.Cin = L.cin_p; a.Ho = S; a.Wo = S; a.Cout = L.cout_p; a.SI = 1; a.SO = 1;
-  a.nphase = 1; a.phases[0] = Phase{0, 0, S, S, L.ntaps, 0, 0};
-  fill_taps(a, L.ntaps, false);
   return launch_gather_gemm(dtype, dtype, a, s);
 }
 
@@ -191,21 +187,18 @@ int PixelNet::backward(int N, int S, const float* x, const float* d_out, const f
     }
     // weight gradient over the layer's taps: dW[co][ci][t] += sum_pix dy[pix][co] * x[pix + off_t][ci]
     {
-      WgradArgs w; std::memset(&w, 0, sizeof(w));
-      w.P = dy; w.G = xin; w.dW = grads + L.w_off; w.scratch = wsc;
-      w.N = N; w.Hp = S; w.Wp = S; w.Ca = L.cout_p; w.Ca_valid = L.cout; w.Hg = S; w.Wg = S; w.Cb = L.cin_p; w.Cb_valid = L.cin;
-      w.stride = 1; w.pad = 3; w.ksz = 7; w.sA = L.cin * 49; w.sB = 49; w.ntaps = L.ntaps; w.scale = 1.f;
-      for (int t = 0; t < L.ntaps; ++t) w.tap_off[t] = t;
+      WgradArgs w;      // the unpadded weight's strides, its real channels, the mask's taps
+      wgrad_args(w, geom7(L.cout_p, L.cin_p), N, MapIn(dy, S, S), MapIn(xin, S, S), grads + L.w_off, wsc, 1.f, L.ntaps);
+      w.Ca_valid = L.cout; w.Cb_valid = L.cin; w.sA = L.cin * 49;
       MM_TRY(launch_wgrad(dtype, w, s));
     }
     if (i == 0 && !d_x) break;
     // data gradient: dx[pix][ci] = sum_t sum_co dy[pix - off_t][co] * W[co][ci][t]
     {
-      GatherArgs a; std::memset(&a, 0, sizeof(a));
+      GatherArgs a;
+      down_args(a, geom7(L.cin_p, L.cout_p), N, S, S, S, S, L.ntaps);
+      for (int t = 0; t < L.ntaps; ++t) a.taps[t] = Tap{-a.taps[t].dh, -a.taps[t].dw};
       a.x = dy; a.w = base + P.packed + L.packB * e; a.y = base + P.g[cur ^ 1];
-      a.N = N; a.Hi = S; a.Wi = S; a.Cin = L.cout_p; a.Ho = S; a.Wo = S; a.Cout = L.cin_p; a.SI = 1; a.SO = 1;
-      a.nphase = 1; a.phases[0] = Phase{0, 0, S, S, L.ntaps, 0, 0};
-      fill_taps(a, L.ntaps, true);
       MM_TRY(launch_gather_gemm(dtype, dtype, a, s));
     }
     cur ^= 1;

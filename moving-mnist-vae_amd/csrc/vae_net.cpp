@@ -256,7 +256,7 @@ void Net::settle_routes(int N, NetRoute& R) {
     r.bwd_pair_wgrad = plain && dt() == DT_BF16 && g.k == 3 && g.s == 2 && g.p == 1 && gs.k == 1 && gs.s == 2 && gs.p == 0 && g.D0 == 32 &&
                        g.D1 == 32 && gs.D0 == 32 && gs.D1 == 32 && B.Hout == 16 && B.Hin == 32;
     // encoder.layer1 (the block the step ends on): conv2's weight gradient is a stream pass, whose reduce can wait (encoder_bwd says for what)
-    r.bwd_c2_late_reduce = i == 0 && !B.c2.fp8 && op_wgrad_is_stream(dt(), geom(B.c2), N, B.Hout, B.Wout, B.Hout, B.Wout, false, true);
+    r.bwd_c2_late_reduce = i == 0 && !B.c2.fp8 && op_wgrad_is_stream(dt(), geom(B.c2), MapIn::shape(B.Hout, B.Wout), MapIn::shape(B.Hout, B.Wout, true), N);
     // encoder.layer1.conv2's data gradient + bn1's backward sums in one stream pass (bf16, 32 -> 32 channels, 16x16 maps, one block per stage)
     r.bwd_c2_dgrad_stream = i == 0 && !B.identity && r.fwd_c2_stream;
   }
@@ -289,14 +289,15 @@ void Net::settle_routes(int N, NetRoute& R) {
     // are ONE pass over its dy tensor on the caller's stream (wgrad_stream_kernel with DG): dy2 / dys (671 MB each at N = 5120 in
     // uplayer5) are read once instead of twice.  (Not asked where join_bwd_stream takes the whole block.)
     const bool own = !B.identity && !r.bwd_join_stream;
-    r.bwd_fuse_c2 = own && !B.c2.fp8 && op_bwd_fusable(dt(), geom(B.c2), N, B.Hin, B.Win, B.Hout, B.Wout);
-    r.bwd_fuse_cs = own && !B.cs.fp8 && op_bwd_fusable(dt(), geom(B.cs), N, B.Hin, B.Win, B.Hout, B.Wout) && B.C == 16;
+    const MapIn small = MapIn::shape(B.Hin, B.Win), small_pro = MapIn::shape(B.Hin, B.Win, true), large = MapIn::shape(B.Hout, B.Wout);
+    r.bwd_fuse_c2 = own && !B.c2.fp8 && op_bwd_fusable(dt(), geom(B.c2), small, large, N);
+    r.bwd_fuse_cs = own && !B.cs.fp8 && op_bwd_fusable(dt(), geom(B.cs), small, large, N) && B.C == 16;
     // Join-gradient form of a block's backward (blocks on 16-wide maps, uplayer4): the block above hands down its input gradient already masked
     // by this block's join ReLU (conv1_bwd_stream_kernel, MASK: join_bwd_stream's block), the BatchNorm-backward reduce runs unmasked, and dy2 / dys
     // are evaluated by the loaders of the two fused passes -- the bn_bwd_apply launch (840 MB at N = 5120) and both dy tensors disappear.
     r.bwd_join_grad = last_js && i == nd - 2 && dt() == DT_BF16 && join_grad_ && own && B.C == 16 && !B.c2.fp8 && !B.cs.fp8 && !B.c1.fp8 &&
-                      !(i == 0 && cfg.blocks <= 1) && op_bwd_fusable_jg(dt(), geom(B.c2), N, B.Hin, B.Win, B.Hout, B.Wout, true, false, true) &&
-                      op_bwd_fusable_jg(dt(), geom(B.cs), N, B.Hin, B.Win, B.Hout, B.Wout, false, true, false);
+                      !(i == 0 && cfg.blocks <= 1) && op_bwd_fusable_jg(dt(), geom(B.c2), small_pro, large, N, false, true) &&
+                      op_bwd_fusable_jg(dt(), geom(B.cs), small, large, N, true, false);
   }
   // Last up-block forward as one kernel (join + tail conv, the joined activation is never stored); the backward then needs the recomputing wgrad
   // (tail_wg_in_reduce: inside the join-backward reduce pass) and the recomputing join backward.  Shapes it does not take keep join -> conv.
@@ -375,23 +376,22 @@ int Net::pack_down(const Pass& ps, const ConvW& w, hipStream_t s) {
 int Net::pack_up(const Pass& ps, const ConvW& w, hipStream_t s) {
   return op_pack_up(dt(), geom(w), ps.params + w.off, ps.packed(w.packU), s, w.wscale, (w.fp8 && w.tr) ? 1 : 0, w.fragU);
 }
-int Net::run_down(const Pass& ps, const ConvW& w, const void* L, int Hl, int Wl, void* S, int Hs, int Ws,
-                  const float* pro_s, const float* pro_b, int relu, float* stats, int accumulate, int out_dt, hipStream_t s,
-                  const ConvW* w2, const void* x2) {
+// the second source and the layouts of the packed weights of a run_down / run_up launch (fwd: the launch is the layer's forward)
+SecondSrc Net::second_src(const Pass& ps, const ConvW& w, bool fwd, bool frag, const ConvW* w2, const void* x2) const {
   SecondSrc q;
   if (w2) { q.x2 = x2; q.w2 = ps.packed(w2->packU); q.Cin2 = w2->D0; }
-  q.fp8 = (w.fp8 && !w.tr) ? 1 : 0;               // a Conv2d's forward
-  q.wfrag = w.fragD; q.wfrag2 = w2 ? w2->fragU : 0;
-  return op_run_down(dt(), out_dt, geom(w), ps.packed(w.packD), ps.N, L, Hl, Wl, S, Hs, Ws, pro_s, pro_b, relu, stats, accumulate, s, q);
+  q.fp8 = (w.fp8 && fwd) ? 1 : 0;
+  q.wfrag = frag; q.wfrag2 = w2 ? w2->fragU : 0;
+  return q;
 }
-int Net::run_up(const Pass& ps, const ConvW& w, const void* S, int Hs, int Ws, void* L, int Hl, int Wl,
-                const float* pro_s, const float* pro_b, int relu, float* stats, int accumulate, hipStream_t s,
-                const ConvW* w2, const void* x2) {
-  SecondSrc q;
-  if (w2) { q.x2 = x2; q.w2 = ps.packed(w2->packU); q.Cin2 = w2->D0; }
-  q.fp8 = (w.fp8 && w.tr) ? 1 : 0;                // a ConvTranspose2d's forward
-  q.wfrag = w.fragU; q.wfrag2 = w2 ? w2->fragU : 0;
-  return op_run_up(dt(), geom(w), ps.packed(w.packU), ps.N, S, Hs, Ws, L, Hl, Wl, pro_s, pro_b, relu, stats, accumulate, s, q);
+static inline int small_size(const ConvW& w) { return conv_down_size(w.Hl, w.k, w.s, w.p); }
+int Net::run_down(const Pass& ps, const ConvW& w, MapIn L, MapOut S, hipStream_t s, const ConvW* w2, const void* x2) {
+  L.H = L.W = w.Hl; S.H = S.W = small_size(w);
+  return op_run_down(dt(), dt(), geom(w), ps.packed(w.packD), L, S, ps.N, s, second_src(ps, w, !w.tr, w.fragD, w2, x2));   // fwd: a Conv2d's
+}
+int Net::run_up(const Pass& ps, const ConvW& w, MapIn S, MapOut L, hipStream_t s, const ConvW* w2, const void* x2) {
+  S.H = S.W = small_size(w); L.H = L.W = w.Hl;
+  return op_run_up(dt(), geom(w), ps.packed(w.packU), S, L, ps.N, s, second_src(ps, w, w.tr, w.fragU, w2, x2));            // fwd: a ConvTranspose2d's
 }
 hipStream_t Net::wgrad_stream(hipStream_t s) {
   if (side_state_ == 0) {
@@ -433,20 +433,17 @@ int Net::side_wait_mark(int slot, hipStream_t s) {
   return MMVAE_OK;
 }
 
-int Net::run_wgrad(const Pass& ps, const ConvW& w, const void* P, int Hs, int Ws, const float* proP_s, const float* proP_b,
-                   const void* G, int Hl, int Wl, const float* proG_s, const float* proG_b, hipStream_t s) {
+int Net::run_wgrad(const Pass& ps, const ConvW& w, const BnSide& P, const BnSide& G, hipStream_t s, float* scratch, WgradReduceArgs* defer) {
   // (measured in round 3: a SECOND side stream with its own scratch, the weight gradients alternating between the two, is slower --
   // 7.74 vs 7.63 ms per step: the phases where the side stream lags are bandwidth-bound, two wgrad kernels at once only thrash)
-  return op_run_wgrad(dt(), geom(w), ps.N, P, Hs, Ws, proP_s, proP_b, 1, G, Hl, Wl, proG_s, proG_b, 1, ps.grads + w.off, s, ps.wscratch,
-                      w.wscale);
+  WgradOpts o;
+  o.scratch = scratch ? scratch : ps.wscratch; o.scale = w.wscale; o.defer = defer;
+  const int Hs = small_size(w);
+  return op_run_wgrad(dt(), geom(w), MapIn(P, Hs, Hs), MapIn(G, w.Hl, w.Hl), ps.grads + w.off, ps.N, s, o);
 }
 
 int Net::reduce_wgrad_parts(const Pass& ps, const ConvW& w, const float* parts, int nparts, int ntaps, hipStream_t s) {
-  WgradReduceArgs u; std::memset(&u, 0, sizeof(u));
-  u.part = parts; u.dW = ps.grads + w.off; u.Ca = w.D0; u.Cb = w.D1; u.ntaps = ntaps; u.nparts = nparts;
-  u.Ca_valid = w.D0; u.Cb_valid = w.D1; u.sA = w.D1 * ntaps; u.sB = ntaps; u.scale = w.wscale;
-  for (int t = 0; t < ntaps; ++t) u.tap_off[t] = t;
-  return launch_wgrad_reduce(u, s);
+  return launch_wgrad_reduce(reduce_args(parts, nparts, ps.grads + w.off, w.D0, w.D1, ntaps, w.wscale), s);
 }
 
 // SyncBN: sum the partial rows locally, let the host's collective sum the row over the ranks (stream-ordered), and hand the
@@ -565,14 +562,7 @@ int Net::join_backward(const Pass& ps, const Block& B, const BnSide& sc, const v
 // ------------------------------------------------------------------------------------------------ weight re-packs per entry point
 // (recorded by launch_pack() while a batch is open; see pack_batch_begin/flush)
 int Net::packs_enc_fwd(const Pass& ps, hipStream_t s) {
-  {
-    const int cpad = dt() == DT_F32 ? 4 : 8;
-    PackArgs pa; std::memset(&pa, 0, sizeof(pa));
-    pa.src = ps.params + stem.off; pa.dst = ps.packed(stem_pack);
-    pa.cols = 32; pa.K = cpad; pa.K_valid = cfg.in_ch; pa.ntaps = 25; pa.s_col = 25 * cfg.in_ch; pa.s_k = 25; pa.scale = 1.f;
-    for (int t = 0; t < 25; ++t) pa.tap_off[t] = t;
-    MM_TRY(launch_pack(dt(), pa, s));
-  }
+  MM_TRY(op_pack_stem(dt(), ps.params + stem.off, cfg.in_ch, ps.packed(stem_pack), s));
   for (const Block& B : enc) {
     MM_TRY(pack_down(ps, B.c1, s));
     MM_TRY(pack_down(ps, B.c2, s));
@@ -601,15 +591,8 @@ int Net::packs_enc_bwd(const Pass& ps, hipStream_t s) {
     MM_TRY(pack_up(ps, B.c1, s));
     if (!B.identity) MM_TRY(pack_up(ps, B.cs, s));
   }
-  if (enc[0].r.bwd_c2_dgrad_stream) {
-    // dx[n,h,w,ci] = sum_{kh,kw,co} dy[n, h+1-kh, w+1-kw, co] W[co][ci][kh][kw]: a forward 3x3 conv over dy with weights [ci][tap' = 8 - tap][co]
-    const ConvW& w = enc[0].c2;
-    PackArgs pf; std::memset(&pf, 0, sizeof(pf));
-    pf.src = ps.params + w.off; pf.dst = ps.packed(l1c2_flip);
-    pf.cols = 32; pf.K = 32; pf.ntaps = 9; pf.s_col = 9; pf.s_k = 32 * 9; pf.scale = w.wscale;
-    for (int t = 0; t < 9; ++t) pf.tap_off[t] = 8 - t;
-    MM_TRY(launch_pack(dt(), pf, s));
-  }
+  if (const ConvW& w = enc[0].c2; enc[0].r.bwd_c2_dgrad_stream)      // its data gradient as a forward 3x3 conv over dy
+    MM_TRY(op_pack_flipped3(dt(), ps.params + w.off, ps.packed(l1c2_flip), 32, 32, s, w.wscale));
   return MMVAE_OK;
 }
 
@@ -673,66 +656,53 @@ int Net::encoder_fwd(int N, const float* x, const float* params, float* bnbuf, l
   } else {
     // stem Conv2d(in_channels -> 32, k5 s2 p2) (model.py:94): the planar image (in_channels <= 4 planes) is staged as a zero-padded
     // VE-channel NHWC patch in LDS and runs through the MFMA patch-tile kernel; BatchNorm statistics come out of its epilogue.
-    const int cpad = dt() == DT_F32 ? 4 : 8;
-    GatherArgs a; std::memset(&a, 0, sizeof(a));
-    a.x = base + P.x_t; a.w = ps.packed(stem_pack); a.y = base + P.y0; a.stats = stats;
-    a.x_planar = 2; a.x_planes = cfg.in_ch;
-    a.N = N; a.Hi = S; a.Wi = S; a.Cin = cpad; a.Ho = H1; a.Wo = W1; a.Cout = 32; a.SI = 2; a.SO = 1;
-    a.nphase = 1; a.phases[0] = Phase{0, 0, H1, W1, 25, 0, 0};
-    for (int kh = 0; kh < 5; ++kh) for (int kw = 0; kw < 5; ++kw) a.taps[kh * 5 + kw] = Tap{kh - 2, kw - 2};
-    np = launch_gather_gemm(dt(), dt(), a, s);
+    np = op_run_stem(dt(), ps.packed(stem_pack), base + P.x_t, cfg.in_ch, S, MapOut(base + P.y0, H1, W1, stats), N, s);
   }
   MM_TRY(np);
   MM_TRY(bn_fwd(ps, bn0, np, (double)N * H1 * W1, s));
-  const void* xin = base + P.y0;
-  const float* xs = ps.rows(bn0).scale;
-  const float* xb = ps.rows(bn0).shift;
+  BnSide in{base + P.y0, ps.rows(bn0).affine()};      // the block input under its prologue (the stem's BatchNorm + ReLU; none behind a join)
   if (cfg.blocks > 1) MM_TRY(fill_consts(ps, s));
   for (size_t i = 0; i < enc.size(); ++i) {
     Block& B = enc[i];
     const double cnt = (double)N * B.Hout * B.Wout;
-    const BnRows r1 = ps.rows(B.b1);
-    const BnSide s2 = ps.rows(B.b2).side(base + B.y2), sc = ps.shortcut(B, xin);
+    const BnSide s1 = ps.rows(B.b1).side(base + B.y1), s2 = ps.rows(B.b2).side(base + B.y2), sc = ps.shortcut(B, in);
+    float* const stats_sc = stats ? stats + kPartialFloats : nullptr;
     // shortcut branch (conv + its BatchNorm) on the side stream, concurrently with conv1 -> bn1 -> conv2 -> bn2 -- unless one kernel takes conv1 with it
     const bool stream1 = B.r.fwd_c1_cs_stream, stream2 = B.r.fwd_c2_stream, fork = !B.identity && !stream1;
     if (stream1) {
-      np = launch_conv3_stream(dt(), 2, xin, ps.packed(B.c1.packD), ps.packed(B.cs.packD), base + B.y1,
-                               base + B.ys, xs, xb, 1, stats, stats ? stats + kPartialFloats : nullptr, N, B.Hout, s);
+      np = launch_conv3_stream(dt(), 2, MapIn(in, B.Hin, B.Win), ps.packed(B.c1.packD), ps.packed(B.cs.packD),
+                               MapOut(base + B.y1, B.Hout, B.Wout, stats), MapOut(base + B.ys, B.Hout, B.Wout, stats_sc), N, s);
       MM_TRY(np);
       MM_TRY(bn_fwd(ps, B.bs, np, cnt, s, kPartialFloats, B.cs.wscale));
       MM_TRY(bn_fwd(ps, B.b1, np, cnt, s, 0, B.c1.wscale));
     } else if (!B.identity) {
       if (fork) MM_TRY(side_fork(s));
       hipStream_t ss = fork ? wgrad_stream(s) : s;
-      np = run_down(ps, B.cs, xin, B.Hin, B.Win, base + B.ys, B.Hout, B.Wout, xs, xb, 1, stats ? stats + kPartialFloats : nullptr, 0, dt(), ss);
+      np = run_down(ps, B.cs, in, MapOut(base + B.ys, stats_sc), ss);
       MM_TRY(np);
       MM_TRY(bn_fwd(ps, B.bs, np, cnt, ss, kPartialFloats, B.cs.wscale));
     }
     if (!stream1) {
-      np = run_down(ps, B.c1, xin, B.Hin, B.Win, base + B.y1, B.Hout, B.Wout, xs, xb, 1, stats, 0, dt(), s);
+      np = run_down(ps, B.c1, in, MapOut(base + B.y1, stats), s);
       MM_TRY(np);
       MM_TRY(bn_fwd(ps, B.b1, np, cnt, s, 0, B.c1.wscale));
     }
     if (stream2)
-      np = launch_conv3_stream(dt(), 1, base + B.y1, ps.packed(B.c2.packD), nullptr, base + B.y2, nullptr, r1.scale, r1.shift, 1, stats,
-                               nullptr, N, B.Hout, s);
+      np = launch_conv3_stream(dt(), 1, MapIn(s1, B.Hout, B.Wout), ps.packed(B.c2.packD), nullptr, MapOut(base + B.y2, B.Hout, B.Wout, stats),
+                               MapOut(), N, s);
     else
-      np = run_down(ps, B.c2, base + B.y1, B.Hout, B.Wout, base + B.y2, B.Hout, B.Wout, r1.scale, r1.shift, 1, stats, 0, dt(), s);
+      np = run_down(ps, B.c2, s1, MapOut(base + B.y2, stats), s);
     MM_TRY(np);
     MM_TRY(bn_fwd(ps, B.b2, np, cnt, s, 0, B.c2.wscale));
     if (fork) MM_TRY(side_join(s));
     MM_TRY(launch_join_fwd(dt(), s2, sc, base + B.out, (long)N * B.Hout * B.Wout, B.C, s));
-    xin = base + B.out; xs = xb = nullptr;
+    in = BnSide{base + B.out};
   }
   // global average pool + the two 1x1 heads (model.py:123-128) as ONE k=Hf,s=Hf conv whose taps share W/(Hf*Wf)
-  const int nt = Hf * Wf;
   for (int h = 0; h < (cfg.need_logvar ? 2 : 1); ++h) {
-    GatherArgs a; std::memset(&a, 0, sizeof(a));
-    a.x = xin; a.w = ps.packed(h == 0 ? head_pack_mu : head_pack_lv); a.y = h == 0 ? mu : logvar;
-    a.N = N; a.Hi = Hf; a.Wi = Wf; a.Cin = 256; a.Ho = 1; a.Wo = 1; a.Cout = cfg.z; a.SI = Hf; a.SO = 1;
-    a.nphase = 1; a.phases[0] = Phase{0, 0, 1, 1, nt, 0, 0};
-    for (int kh = 0; kh < Hf; ++kh) for (int kw = 0; kw < Wf; ++kw) a.taps[kh * Wf + kw] = Tap{kh, kw};
-    MM_TRY(launch_gather_gemm(dt(), DT_F32, a, s));
+    const ConvW& hw = h == 0 ? head_mu : head_lv;
+    const MapOut latent(h == 0 ? mu : logvar, 1, 1);      // f32 [N][1][1][z]
+    MM_TRY(op_run_down(dt(), DT_F32, ConvGeom{hw.D0, hw.D1, Hf, Hf, 0}, ps.packed(h == 0 ? head_pack_mu : head_pack_lv), MapIn(in.y, Hf, Wf), latent, N, s));
   }
   return MMVAE_OK;
 }
@@ -754,11 +724,11 @@ int Net::encoder_bwd(int N, const float* d_mu, const float* d_logvar, const floa
   // ---- heads: dh = [d_mu | d_logvar] in T
   MM_TRY(launch_concat2_to_t(dt(), d_mu, cfg.need_logvar ? d_logvar : nullptr, N, cfg.z, cfg.need_logvar ? cfg.z : 0, base + P.dh, s));
   {
-    WgradArgs a; std::memset(&a, 0, sizeof(a));
-    a.P = base + P.dh; a.G = base + enc.back().out; a.dW = grads + head_mu.off; a.proP_relu = a.proG_relu = 0;
-    a.N = N; a.Hp = 1; a.Wp = 1; a.Ca = Ch; a.Hg = Hf; a.Wg = Wf; a.Cb = 256; a.Cb_valid = 256;
-    a.stride = Hf; a.pad = 0; a.ksz = Hf; a.sA = 256; a.sB = 1; a.ntaps = nt; a.scale = 1.0f / nt;
-    a.scratch = ps.wscratch;
+    // both heads' weight gradient as the k=Hf,s=Hf conv's, every tap adding into the one 1x1 weight (the average pool)
+    WgradArgs a;
+    wgrad_args(a, ConvGeom{Ch, 256, Hf, Hf, 0}, N, MapIn(base + P.dh, 1, 1), MapIn(base + enc.back().out, Hf, Wf), grads + head_mu.off, ps.wscratch,
+               1.0f / nt);
+    a.sA = 256; a.sB = 1; std::fill_n(a.tap_off, nt, 0);
     MM_TRY(side_fork(s));
     MM_TRY(launch_wgrad(dt(), a, wgrad_stream(s)));
     // the stem's input-only work (patch gram matrix / im2col) early, off the tail of the critical path
@@ -783,11 +753,8 @@ int Net::encoder_bwd(int N, const float* d_mu, const float* d_logvar, const floa
   for (int i = ne - 1; i >= 0; --i) {
     Block& B = enc[i];
     const long npix = (long)N * B.Hout * B.Wout;
-    const void* xin = i == 0 ? base + P.y0 : base + enc[i - 1].out;
-    const float* xs = i == 0 ? r0.scale : nullptr;
-    const float* xb = i == 0 ? r0.shift : nullptr;
-    const BnRows r1 = ps.rows(B.b1);
-    const BnSide sc = ps.shortcut(B, xin);
+    const BnSide in = i == 0 ? BnSide{base + P.y0, r0.affine()} : BnSide{base + enc[i - 1].out};      // the block input under its prologue
+    const BnSide s1 = ps.rows(B.b1).side(base + B.y1), sc = ps.shortcut(B, in);
     // dy1 / dy2 / dys alternate between two sets, so this block only has to wait for the weight gradients of the block
     // before the previous one (the side stream may lag one block behind)
     // The two blocks visited first (small tensors) own private sets: with a deferred decoder join the side stream may still be
@@ -810,41 +777,42 @@ int Net::encoder_bwd(int N, const float* d_mu, const float* d_logvar, const floa
     // AFTER the block's other weight gradient has been enqueued -- under the stem backward's load a 19 MB reduce takes 120 us instead of
     // 10, and it sat in front of the last big kernel of the side stream
     WgradReduceArgs late; late.nparts = 0;
+    const void *const dy1 = base + dy1o, *const dy2 = base + dy2o, *const dys = base + dyso;
     if (B.r.bwd_c2_late_reduce && wsm != s)
-      MM_TRY(op_run_wgrad(dt(), geom(B.c2), N, base + dy2o, B.Hout, B.Wout, nullptr, nullptr, 1, base + B.y1, B.Hout, B.Wout, r1.scale,
-                          r1.shift, 1, grads + B.c2.off, wsm, reinterpret_cast<float*>(base + P.wscratch2), B.c2.wscale, &late));
+      MM_TRY(run_wgrad(ps, B.c2, BnSide{dy2}, s1, wsm, reinterpret_cast<float*>(base + P.wscratch2), &late));
     else
-      MM_TRY(run_wgrad(ps, B.c2, base + dy2o, B.Hout, B.Wout, nullptr, nullptr, base + B.y1, B.Hout, B.Wout, r1.scale, r1.shift, wsm));
+      MM_TRY(run_wgrad(ps, B.c2, BnSide{dy2}, s1, wsm));
     const bool pair = B.r.bwd_pair_wgrad;     // (encoder.layer1: the shortcut's weight gradient rides on conv1's pass over the block input, below)
-    if (!B.identity && !pair) MM_TRY(run_wgrad(ps, B.cs, base + dyso, B.Hout, B.Wout, nullptr, nullptr, xin, B.Hin, B.Win, xs, xb, wsm));
+    if (!B.identity && !pair) MM_TRY(run_wgrad(ps, B.cs, BnSide{dys}, in, wsm));
     int np1 = 0;                         // rows of bn1's backward sums when the data-gradient pass has left them in `part`
     if (B.r.bwd_c2_dgrad_stream) {
       // encoder.layer1.conv2: the data gradient as a per-wave stream over dy2 (conv3_stream_kernel) with bn1's backward sums from the same pass
-      np1 = launch_conv3_stream_bwd(dt(), base + dy2o, ps.packed(l1c2_flip), base + P.da1, base + B.y1, r1.scale, r1.shift, part, N, B.Hout, s);
+      np1 = launch_conv3_stream_bwd(dt(), MapIn(dy2, B.Hout, B.Wout), ps.packed(l1c2_flip), s1, MapOut(base + P.da1, B.Hout, B.Wout, part), N, s);
       MM_TRY(np1);
     } else
-      MM_TRY(run_up(ps, B.c2, base + dy2o, B.Hout, B.Wout, base + P.da1, B.Hout, B.Wout, nullptr, nullptr, 0, nullptr, 0, s));
+      MM_TRY(run_up(ps, B.c2, dy2, base + P.da1, s));
     MM_TRY(bn_relu_backward(ps, B.b1, base + P.da1, base + B.y1, base + dy1o, npix, s, np1));      // bn1 + relu backward
     // conv1 (3x3) and the 1x1 s2 shortcut: weight gradients, then d_xin = dgrad(conv1) + dgrad(shortcut)
     MM_TRY(side_fork(s));
     int taken = 0;
     if (pair) {
-      taken = op_run_wgrad_pair(dt(), geom(B.c1), geom(B.cs), N, base + dy1o, base + dyso, B.Hout, B.Wout, xin, B.Hin, B.Win, xs, xb, 1,
-                                grads + B.c1.off, grads + B.cs.off, wsm, ps.wscratch, B.c1.wscale, B.cs.wscale);
+      WgradOpts o;
+      o.scratch = ps.wscratch; o.scale = B.c1.wscale; o.scale2 = B.cs.wscale;
+      taken = op_run_wgrad_pair(dt(), geom(B.c1), geom(B.cs), MapIn(dy1, B.Hout, B.Wout), dys, MapIn(in, B.Hin, B.Win), grads + B.c1.off,
+                                grads + B.cs.off, N, wsm, o);
       MM_TRY(taken);
-      if (!taken) MM_TRY(run_wgrad(ps, B.cs, base + dyso, B.Hout, B.Wout, nullptr, nullptr, xin, B.Hin, B.Win, xs, xb, wsm));
+      if (!taken) MM_TRY(run_wgrad(ps, B.cs, BnSide{dys}, in, wsm));
     }
-    if (!taken) MM_TRY(run_wgrad(ps, B.c1, base + dy1o, B.Hout, B.Wout, nullptr, nullptr, xin, B.Hin, B.Win, xs, xb, wsm));
+    if (!taken) MM_TRY(run_wgrad(ps, B.c1, BnSide{dy1}, in, wsm));
     if (late.nparts > 0) MM_TRY(launch_wgrad_reduce(late, wsm));
     MM_TRY(side_mark(i));
     if (i == 0 && R.stem_dg_fused) {
       // the gradient of the stem's output is never a tensor: stem_bwd_kernel<DG> recomputes it row by row from dy1 / dys (below)
       stem_dy1 = dy1o; stem_dys = dyso;
     } else if (B.identity)     // d_xin already holds the shortcut's share: the main path's data gradient is added to it
-      MM_TRY(run_up(ps, B.c1, base + dy1o, B.Hout, B.Wout, base + P.g[cur ^ 1], B.Hin, B.Win, nullptr, nullptr, 0, nullptr, 1, s));
+      MM_TRY(run_up(ps, B.c1, dy1, MapOut::add(base + P.g[cur ^ 1]), s));
     else                // one kernel: the 1x1 stride-2 shortcut's data gradient is a second source of the 3x3 conv's (phase (0,0))
-      MM_TRY(run_up(ps, B.c1, base + dy1o, B.Hout, B.Wout, base + P.g[cur ^ 1], B.Hin, B.Win, nullptr, nullptr, 0, nullptr, 0, s, &B.cs,
-                    base + dyso));
+      MM_TRY(run_up(ps, B.c1, dy1, base + P.g[cur ^ 1], s, &B.cs, dys));
     cur ^= 1;
   }
   // ---- stem: bn0 + relu backward and the 5x5 weight gradient
@@ -874,20 +842,18 @@ int Net::encoder_bwd(int N, const float* d_mu, const float* d_logvar, const floa
   MM_TRY(bn_relu_backward(ps, bn0, base + P.g[cur], base + P.y0, base + P.dy1[1], (long)N * H1 * W1, s));
   MM_TRY(side_fork(s));
   hipStream_t wsm = wgrad_stream(s);
-  WgradArgs a; std::memset(&a, 0, sizeof(a));
-  a.P = base + P.dy1[1]; a.dW = grads + stem.off; a.scratch = ps.wscratch;
-  a.N = N; a.Hp = H1; a.Wp = W1; a.Ca = 32; a.scale = 1.f;
+  const MapIn dy(base + P.dy1[1], H1, W1);
+  WgradArgs a;
   if (cfg.in_ch > 1) {
     // in_channels > 1 (main.py:555): G = the image as NHWC with 16 zero-padded channels, the generic 25-tap weight gradient
     MM_TRY(launch_planar_to_nhwc16(dt(), static_cast<const void*>(base + P.x_t), dt(), base + P.col, N, cfg.in_ch, cfg.S * cfg.S, wsm));
-    a.G = base + P.col; a.Hg = cfg.S; a.Wg = cfg.S; a.Cb = 16; a.Cb_valid = cfg.in_ch;
-    a.stride = 2; a.pad = 2; a.ksz = 5; a.sA = 25 * cfg.in_ch; a.sB = 25; a.ntaps = 25;
-    for (int t = 0; t < 25; ++t) a.tap_off[t] = t;
+    wgrad_args(a, ConvGeom{32, 16, 5, 2, 2}, N, dy, MapIn(base + P.col, cfg.S, cfg.S), grads + stem.off, ps.wscratch);
+    a.Cb_valid = cfg.in_ch; a.sA = 25 * cfg.in_ch;
   } else {
     // im2col of the 1-channel image (25 taps padded to 32 columns) + the MFMA weight-gradient kernel as a 1x1 conv
     if (wsm == s) MM_TRY(launch_stem_im2col(dt(), base + P.x_t, base + P.col, N, cfg.S, cfg.S, H1, W1, wsm));   // else: done early
-    a.G = base + P.col; a.Hg = H1; a.Wg = W1; a.Cb = 32; a.Cb_valid = 25;
-    a.stride = 1; a.pad = 0; a.ksz = 1; a.sA = 25; a.sB = 1; a.ntaps = 1;
+    wgrad_args(a, ConvGeom{32, 32, 1, 1, 0}, N, dy, MapIn(base + P.col, H1, W1), grads + stem.off, ps.wscratch);
+    a.Cb_valid = 25; a.sA = 25;
   }
   MM_TRY(launch_wgrad(dt(), a, wsm));
   return side_join(s);
@@ -910,50 +876,47 @@ int Net::decoder_fwd(int N, const float* encv, const float* params, float* bnbuf
   if (!training) MM_TRY(fold_bn_eval(ps, 1, s));
   MM_TRY(launch_convert(DT_F32, dt(), encv, base + P.enc_t, (long)N * cfg.z, s));
   // stem ConvTranspose2d(z -> 128, k2) on the 1x1 latent (model.py:159-161,182)
-  int np = run_up(ps, dstem, base + P.enc_t, 1, 1, base + P.y0d, 2, 2, nullptr, nullptr, 0, stats, 0, s);
+  int np = run_up(ps, dstem, base + P.enc_t, MapOut(base + P.y0d, stats), s);
   MM_TRY(np);
   MM_TRY(bn_fwd(ps, dbn0, np, (double)N * 4, s, 0, dstem.wscale));
-  const void* xin = base + P.y0d;
-  const float* xs = ps.rows(dbn0).scale;
-  const float* xb = ps.rows(dbn0).shift;
+  BnSide in{base + P.y0d, ps.rows(dbn0).affine()};      // the block input under its prologue (see encoder_fwd)
   const int nd = (int)dec.size();
   if (cfg.blocks > 1) {
     // the first block of a deeper decoder has an identity shortcut: it needs the stem's activation as a tensor
     MM_TRY(fill_consts(ps, s));
-    MM_TRY(launch_affine_act(dt(), BnSide{base + P.y0d, {xs, xb}}, 1, base + P.act0d, (long)N * 4, 128, s));
-    xin = base + P.act0d; xs = xb = nullptr;
+    MM_TRY(launch_affine_act(dt(), in, 1, base + P.act0d, (long)N * 4, 128, s));
+    in = BnSide{base + P.act0d};
   }
   int c1_done = 0;                 // rows of bn1 statistics the previous block's join kernel left for this block's conv1 (0: conv1 not done)
   for (int i = 0; i < nd; ++i) {
     Block& B = dec[i];
     const double cnt = (double)N * B.Hout * B.Wout;
-    const BnRows r1 = ps.rows(B.b1);
-    const BnSide s2 = ps.rows(B.b2).side(base + B.y2), sc = ps.shortcut(B, xin);
+    const BnSide s1 = ps.rows(B.b1).side(base + B.y1), s2 = ps.rows(B.b2).side(base + B.y2), sc = ps.shortcut(B, in);
     // a ConvTranspose2d forward: the per-wave stream (conv_fstream.hip) where routed -- on the up5 route statistics only, nothing in eval mode -- else the up conv
-    auto convT = [&](const ConvW& w, bool stream, const void* x, long y, const float* pro_s, const float* pro_b, float* st, hipStream_t q) {
+    auto convT = [&](const ConvW& w, bool stream, const BnSide& x, long y, float* st, hipStream_t q) {
       const bool stats_only = B.r.fwd_stats_only;
       if (stats_only && !st) return 1;
-      if (stream) return launch_convT4_stream(dt(), x, ps.packed(w.packU), stats_only ? nullptr : base + y, pro_s, pro_b, 1, st, N, B.Hin, q,
-                                              (R.store8 && i == nd - 1) ? 1 : 0);
-      return run_up(ps, w, x, B.Hin, B.Win, base + y, B.Hout, B.Wout, pro_s, pro_b, 1, st, 0, q);
+      if (stream) return launch_convT4_stream(dt(), MapIn(x, B.Hin, B.Win), ps.packed(w.packU), MapOut(stats_only ? nullptr : base + y, B.Hout, B.Wout, st),
+                                              N, q, (R.store8 && i == nd - 1) ? 1 : 0);
+      return run_up(ps, w, x, MapOut(base + y, st), q);
     };
     // upsample (shortcut) branch on the side stream, concurrently with conv1 -> bn1 -> conv2 -> bn2
     if (!B.identity) {
       MM_TRY(side_fork(s));
       hipStream_t ss = wgrad_stream(s);
-      np = convT(B.cs, B.r.fwd_cs_stream, xin, B.ys, xs, xb, stats ? stats + kPartialFloats : nullptr, ss);
+      np = convT(B.cs, B.r.fwd_cs_stream, in, B.ys, stats ? stats + kPartialFloats : nullptr, ss);
       MM_TRY(np);
       MM_TRY(bn_fwd(ps, B.bs, np, cnt, ss, kPartialFloats, B.cs.wscale));
     }
     // (conv1 already done: the previous block's join kernel computed it from the joined row it had in LDS -- join_conv1_fwd below)
-    np = c1_done > 0 ? c1_done : run_down(ps, B.c1, xin, B.Hin, B.Win, base + B.y1, B.Hin, B.Win, xs, xb, 1, stats, 0, dt(), s);
+    np = c1_done > 0 ? c1_done : run_down(ps, B.c1, in, MapOut(base + B.y1, stats), s);
     c1_done = 0;
     MM_TRY(np);
     MM_TRY(bn_fwd(ps, B.b1, np, (double)N * B.Hin * B.Win, s, 0, B.c1.wscale));
     if (B.identity)    // 3x3 Conv2d, shape preserving
-      np = run_down(ps, B.c2, base + B.y1, B.Hin, B.Win, base + B.y2, B.Hout, B.Wout, r1.scale, r1.shift, 1, stats, 0, dt(), s);
+      np = run_down(ps, B.c2, s1, MapOut(base + B.y2, stats), s);
     else
-      np = convT(B.c2, B.r.fwd_c2_stream, base + B.y1, B.y2, r1.scale, r1.shift, stats, s);
+      np = convT(B.c2, B.r.fwd_c2_stream, s1, B.y2, stats, s);
     MM_TRY(np);
     MM_TRY(bn_fwd(ps, B.b2, np, cnt, s, 0, B.c2.wscale));
     if (!B.identity) MM_TRY(side_join(s));
@@ -964,17 +927,17 @@ int Net::decoder_fwd(int N, const float* encv, const float* params, float* bnbuf
       MM_TRY(c1_done);
     } else
     MM_TRY(launch_join_fwd(dt(), s2, sc, base + B.out, (long)N * B.Hout * B.Wout, B.C, s));
-    xin = base + B.out; xs = xb = nullptr;
+    in = BnSide{base + B.out};
   }
   // tail conv (+bias) and the output BatchNorm (model.py:193)
   float* r_raw = reinterpret_cast<float*>(base + P.r_raw);
   if (R.tail_fwd != TAIL_GATHER) {
-    const Block& B = dec.back();     // (the join left to this kernel: xin is still the block's input)
-    const BnSide s1 = ps.rows(B.b1).side(base + B.y1), s2 = ps.rows(B.b2).side(base + B.y2), sc = ps.shortcut(B, xin);
+    const Block& B = dec.back();     // (the join left to this kernel: `in` is still the block's input)
+    const BnSide s1 = ps.rows(B.b1).side(base + B.y1), s2 = ps.rows(B.b2).side(base + B.y2), sc = ps.shortcut(B, in);
     if (R.tail_fwd == TAIL_UP5)
       // the join + tail conv with both branch outputs recomputed from the ConvTranspose2d inputs (0.34 GB) instead of read back (1.34 GB),
       // and (training) stored from here for the backward pass
-      np = launch_up5_tail_fwd(s1, ps.packed(B.c2.packU), BnSide{xin, {xs, xb}}, ps.packed(B.cs.packU), s2.fwd, sc.fwd, params + tail.off,
+      np = launch_up5_tail_fwd(s1, ps.packed(B.c2.packU), in, ps.packed(B.cs.packU), s2.fwd, sc.fwd, params + tail.off,
                                params + tail_bias, r_raw, stats, N, s, stats ? base + B.y2 : nullptr, stats ? base + B.ys : nullptr);
     else if (R.tail_fwd == TAIL_STREAM)
       np = launch_tail_fwd_stream(dt(), s2, sc, params + tail.off, params + tail_bias, r_raw, stats, N, Sd, Sd, s, R.store8 ? 1 : 0);
@@ -982,11 +945,9 @@ int Net::decoder_fwd(int N, const float* encv, const float* params, float* bnbuf
       np = launch_tail_join_fwd(dt(), s2, sc, params + tail.off, params + tail_bias, r_raw, stats, N, Sd, Sd, s);
   } else {
     // Conv2d(16 -> out_ch, k3 p1, bias): GEMM rows padded to 16 in LDS, epilogue stores the out_ch real rows as NCHW f32
-    GatherArgs a; std::memset(&a, 0, sizeof(a));
-    a.x = xin; a.w = ps.packed(tail_pack_f); a.y = r_raw; a.bias = params + tail_bias; a.stats = stats; a.y_planes = cfg.out_ch;
-    a.N = N; a.Hi = Sd; a.Wi = Sd; a.Cin = 16; a.Ho = Sd; a.Wo = Sd; a.Cout = 16; a.SI = 1; a.SO = 1;
-    a.nphase = 1; a.phases[0] = Phase{0, 0, Sd, Sd, 9, 0, 0};
-    for (int kh = 0; kh < 3; ++kh) for (int kw = 0; kw < 3; ++kw) a.taps[kh * 3 + kw] = Tap{kh - 1, kw - 1};
+    GatherArgs a;
+    down_args(a, ConvGeom{16, 16, 3, 1, 1}, N, Sd, Sd, Sd, Sd);
+    a.x = in.y; a.w = ps.packed(tail_pack_f); a.y = r_raw; a.bias = params + tail_bias; a.stats = stats; a.y_planes = cfg.out_ch;
     np = launch_gather_gemm(dt(), DT_F32, a, s);
   }
   MM_TRY(np);
@@ -1034,11 +995,9 @@ int Net::decoder_bwd(int N, const float* d_recon, const float* params, float* gr
     MM_TRY(launch_bn_bwd_apply_nchw(d_recon, r_raw, ro.coef(), d_raw, N, cfg.out_ch, HW, s));
   if (!R.tail_wg_in_reduce) {      // (else the forward did not store the joined activation: the join-backward reduce pass below recomputes it)
     // dW[oc][ci][kh][kw]: P = d_raw (planar f32, out_ch planes staged as 16 zero-padded channels), G = the last up-block's output
-    WgradArgs a; std::memset(&a, 0, sizeof(a));
-    a.P = d_raw; a.P_planar = 1; a.P_planes = cfg.out_ch; a.G = base + dec.back().out; a.dW = grads + tail.off; a.scratch = ps.wscratch;
-    a.N = N; a.Hp = Sd; a.Wp = Sd; a.Ca = 16; a.Ca_valid = cfg.out_ch; a.Hg = Sd; a.Wg = Sd; a.Cb = 16; a.Cb_valid = 16;
-    a.stride = 1; a.pad = 1; a.ksz = 3; a.sA = 16 * 9; a.sB = 9; a.ntaps = 9; a.scale = 1.f;
-    for (int t = 0; t < 9; ++t) a.tap_off[t] = t;
+    WgradArgs a;
+    wgrad_args(a, ConvGeom{16, 16, 3, 1, 1}, N, MapIn(d_raw, Sd, Sd), MapIn(base + dec.back().out, Sd, Sd), grads + tail.off, ps.wscratch);
+    a.P_planar = 1; a.P_planes = cfg.out_ch; a.Ca_valid = cfg.out_ch;
     MM_TRY(side_fork(s));
     MM_TRY(launch_wgrad(dt(), a, wgrad_stream(s)));
   }
@@ -1057,13 +1016,12 @@ int Net::decoder_bwd(int N, const float* d_recon, const float* params, float* gr
     Block& B = dec[i];
     const bool jg = B.r.bwd_join_grad;     // join-gradient form: g[cur] is already masked by this block's join ReLU (the block above did it)
     const long npi = (long)N * B.Hin * B.Win;
-    // (blocks > 1: block 0 has an identity shortcut and reads the stem's materialised activation)
-    const void* xin = i == 0 ? (cfg.blocks > 1 ? base + P.act0d : base + P.y0d) : base + dec[i - 1].out;
-    const float* xs = (i == 0 && cfg.blocks <= 1) ? r0.scale : nullptr;
-    const float* xb = (i == 0 && cfg.blocks <= 1) ? r0.shift : nullptr;
-    const BnRows r1 = ps.rows(B.b1);
-    const BnSide s1 = r1.side(base + B.y1), s2 = ps.rows(B.b2).side(base + B.y2), sc = ps.shortcut(B, xin), in{xin, {xs, xb}};
+    // the block input under its prologue: the stem's BatchNorm + ReLU for block 0 -- unless (blocks > 1) it has an identity shortcut and reads the
+    // stem's materialised activation
+    const BnSide in = i > 0 ? BnSide{base + dec[i - 1].out} : cfg.blocks > 1 ? BnSide{base + P.act0d} : BnSide{base + P.y0d, r0.affine()};
+    const BnSide s1 = ps.rows(B.b1).side(base + B.y1), s2 = ps.rows(B.b2).side(base + B.y2), sc = ps.shortcut(B, in);
     const int ds = i & 1;          // dy set of this block (see encoder_bwd)
+    const void *const dy1 = base + P.dy1[ds], *const dy2 = base + P.dy2[ds], *const dys = base + P.dys[ds];
     if (i + 2 <= nd - 1) MM_TRY(side_wait_mark(i + 2, s));
     const bool from_tail = R.tail_bwd_fused && i == nd - 1;
     // an identity shortcut's gradient is the masked incoming gradient itself: it goes straight into the block-input gradient
@@ -1111,49 +1069,51 @@ int Net::decoder_bwd(int N, const float* d_recon, const float* params, float* gr
     int np_b1 = 0;                       // rows of bn1's backward sums when the fused pass has left them in `part`
     if (B.identity) {
       // conv2 (3x3 Conv2d): wgrad(P = dy2, G = a1 with BN+ReLU prologue); dgrad -> d_a1
-      MM_TRY(run_wgrad(ps, B.c2, base + P.dy2[ds], B.Hout, B.Wout, nullptr, nullptr, base + B.y1, B.Hin, B.Win, r1.scale, r1.shift, wsm));
-      MM_TRY(run_up(ps, B.c2, base + P.dy2[ds], B.Hout, B.Wout, base + P.da1, B.Hin, B.Win, nullptr, nullptr, 0, nullptr, 0, s));
+      MM_TRY(run_wgrad(ps, B.c2, BnSide{dy2}, s1, wsm));
+      MM_TRY(run_up(ps, B.c2, dy2, base + P.da1, s));
     } else {
       // conv2 (ConvT k4 s2): wgrad(P = a1 small side with BN+ReLU prologue, G = dy2 large side); dgrad = strided conv -> d_a1; fused: ONE pass over dy
-      float* wsc2 = reinterpret_cast<float*>(base + P.wscratch2);
-      if (!fuse_c2)
-        MM_TRY(run_wgrad(ps, B.c2, base + B.y1, B.Hin, B.Win, r1.scale, r1.shift, base + P.dy2[ds], B.Hout, B.Wout, nullptr, nullptr, wsm));
-      if (!fuse_cs) MM_TRY(run_wgrad(ps, B.cs, xin, B.Hin, B.Win, xs, xb, base + P.dys[ds], B.Hout, B.Wout, nullptr, nullptr, wsm));
+      if (!fuse_c2) MM_TRY(run_wgrad(ps, B.c2, s1, BnSide{dy2}, wsm));
+      if (!fuse_cs) MM_TRY(run_wgrad(ps, B.cs, in, BnSide{dys}, wsm));
       if (fuse_c2) {
         // ... and bn1's backward sums come out of the same pass (the data gradient is in registers, y1 is the pass's P operand)
-        const int rcf = op_run_bwd_fused(dt(), geom(B.c2), N, base + B.y1, B.Hin, B.Win, r1.scale, r1.shift, 1,
-                                         jg ? base + P.g[cur] : base + P.dy2[ds], B.Hout, B.Wout, ps.packed(B.c2.packD), base + P.da1, nullptr,
-                                         nullptr, grads + B.c2.off, s, wsc2, B.c2.wscale, B.C == 16 ? part : nullptr, nullptr, 1.f, jg ? &s2 : nullptr);
+        WgradOpts o;
+        o.scratch = reinterpret_cast<float*>(base + P.wscratch2); o.scale = B.c2.wscale; o.bn_part = B.C == 16 ? part : nullptr; o.jg = jg ? &s2 : nullptr;
+        const int rcf = op_run_bwd_fused(dt(), geom(B.c2), ps.packed(B.c2.packD), MapIn(s1, B.Hin, B.Win), MapIn(jg ? base + P.g[cur] : dy2, B.Hout, B.Wout),
+                                         SecondSrc(), base + P.da1, grads + B.c2.off, N, s, o);
         if (rcf <= 0) { if (rcf == 0) set_error("decoder_bwd: fused backward of %s not taken", "conv2"); return rcf < 0 ? rcf : MMVAE_ERR_UNSUPPORTED; }
         if (B.C == 16) np_b1 = rcf;
       } else
-        MM_TRY(run_down(ps, B.c2, base + P.dy2[ds], B.Hout, B.Wout, base + P.da1, B.Hin, B.Win, nullptr, nullptr, 0, nullptr, 0, dt(), s));
+        MM_TRY(run_down(ps, B.c2, dy2, base + P.da1, s));
     }
-    MM_TRY(bn_relu_backward(ps, B.b1, base + P.da1, base + B.y1, base + P.dy1[ds], npi, s, np_b1));
+    MM_TRY(bn_relu_backward(ps, B.b1, base + P.da1, s1.y, base + P.dy1[ds], npi, s, np_b1));
     // conv1 (1x1): wgrad(P = dy1, G = xin); upsample (ConvT): wgrad(P = xin, G = dys)
     MM_TRY(side_fork(s));
     // (with the fused shortcut pass below the 1x1 conv's weight gradient comes out of that pass: dy1 and the block input are its rows)
-    if (!fuse_cs) MM_TRY(run_wgrad(ps, B.c1, base + P.dy1[ds], B.Hin, B.Win, nullptr, nullptr, xin, B.Hin, B.Win, xs, xb, wsm));
+    if (!fuse_cs) MM_TRY(run_wgrad(ps, B.c1, BnSide{dy1}, in, wsm));
     MM_TRY(side_mark(i));
     if (B.identity)     // d_xin already holds the shortcut's share: the 1x1 conv's data gradient is added to it
-      MM_TRY(run_up(ps, B.c1, base + P.dy1[ds], B.Hin, B.Win, base + P.g[cur ^ 1], B.Hin, B.Win, nullptr, nullptr, 0, nullptr, 1, s));
+      MM_TRY(run_up(ps, B.c1, dy1, MapOut::add(base + P.g[cur ^ 1]), s));
     else if (fuse_cs) {  // shortcut ConvT: weight gradient + data gradient + the 1x1 conv's share (dy1 (x) w1) and ITS weight gradient, one pass over dys
-      const int rcf = op_run_bwd_fused(dt(), geom(B.cs), N, xin, B.Hin, B.Win, xs, xb, 1, jg ? base + P.g[cur] : base + P.dys[ds], B.Hout, B.Wout,
-                                       ps.packed(B.cs.packD), base + P.g[cur ^ 1], base + P.dy1[ds], ps.packed(B.c1.packU), grads + B.cs.off, s,
-                                       reinterpret_cast<float*>(base + P.wscratch2), B.cs.wscale, nullptr, grads + B.c1.off, B.c1.wscale, jg ? &sc : nullptr);
+      SecondSrc x2;
+      x2.x2 = dy1; x2.w2 = ps.packed(B.c1.packU);
+      WgradOpts o;
+      o.scratch = reinterpret_cast<float*>(base + P.wscratch2); o.scale = B.cs.wscale; o.dW2 = grads + B.c1.off; o.scale2 = B.c1.wscale; o.jg = jg ? &sc : nullptr;
+      const int rcf = op_run_bwd_fused(dt(), geom(B.cs), ps.packed(B.cs.packD), MapIn(in, B.Hin, B.Win), MapIn(jg ? base + P.g[cur] : dys, B.Hout, B.Wout),
+                                       x2, base + P.g[cur ^ 1], grads + B.cs.off, N, s, o);
       if (rcf <= 0) { if (rcf == 0) set_error("decoder_bwd: fused backward of %s not taken", "upsample"); return rcf < 0 ? rcf : MMVAE_ERR_UNSUPPORTED; }
     } else              // one kernel: the 1x1 conv's data gradient (dy1, already on this block's input grid) is a second source of the shortcut's
-      MM_TRY(run_down(ps, B.cs, base + P.dys[ds], B.Hout, B.Wout, base + P.g[cur ^ 1], B.Hin, B.Win, nullptr, nullptr, 0, nullptr, 0, dt(), s,
-                      &B.c1, base + P.dy1[ds]));
+      MM_TRY(run_down(ps, B.cs, dys, base + P.g[cur ^ 1], s, &B.c1, dy1));
     cur ^= 1;
   }
   // ---- decoder stem
   if (dec.size() >= 2) MM_TRY(side_wait_mark(1, s));   // the stem uses dy set 1 (block index -1)
   MM_TRY(bn_relu_backward(ps, dbn0, base + P.g[cur], base + P.y0d, base + P.dy1[1], (long)N * 4, s));
   MM_TRY(side_fork(s));
-  MM_TRY(run_wgrad(ps, dstem, base + P.enc_t, 1, 1, nullptr, nullptr, base + P.dy1[1], 2, 2, nullptr, nullptr, wgrad_stream(s)));
+  const void* const dy0 = base + P.dy1[1];
+  MM_TRY(run_wgrad(ps, dstem, BnSide{base + P.enc_t}, BnSide{dy0}, wgrad_stream(s)));
   if (d_enc) {
-    MM_TRY(run_down(ps, dstem, base + P.dy1[1], 2, 2, base + P.dh, 1, 1, nullptr, nullptr, 0, nullptr, 0, dt(), s));
+    MM_TRY(run_down(ps, dstem, dy0, base + P.dh, s));
     MM_TRY(launch_convert(dt(), DT_F32, base + P.dh, d_enc, (long)N * cfg.z, s));
   }
   if (!defer_join_) MM_TRY(side_join(s));

@@ -4,6 +4,7 @@
 // the activation workspace are caller-provided device pointers.
 // Each entry point binds those pointers once into a Net::Pass; the helpers take the Pass and the call sites name only what varies
 // (layer, operands, stream).  BatchNorm scratch rows and packed weights are reached by name: Pass::rows(), Pass::shortcut(), Pass::packed().
+// A conv's operands are one argument per tensor (MapIn / MapOut, kernels.hpp); a block's input travels as one BnSide (`in`: the tensor under its prologue).
 // Which kernel takes each launch is settled with the plan: Net::settle_routes(N) fills a BlockRoute per block and a NetRoute for the boundary layers and
 // checks that forward and backward fit each other; the entry points only read the fields (ANDed with what depends on the run: side stream, training, d_enc).
 #pragma once
@@ -157,8 +158,8 @@ class Net {
     const float* zeros() const { return ones() + 256; }
     // A block's shortcut operand at its join: the shortcut conv's output under its BatchNorm (B.ys, B.bs), or -- identity shortcut
     // (model.py:40,52) -- the block input itself under a unit BatchNorm (scale 1, shift 0; backward A = 1, B = C = 0)
-    BnSide shortcut(const Block& B, const void* xin) const {
-      if (B.identity) return BnSide{xin, {ones(), zeros()}, {ones(), zeros(), zeros()}};
+    BnSide shortcut(const Block& B, const BnSide& in) const {
+      if (B.identity) return BnSide{in.y, {ones(), zeros()}, {ones(), zeros(), zeros()}};
       return rows(B.bs).side(base + B.ys);
     }
   };
@@ -193,15 +194,15 @@ class Net {
   int packs_dec_bwd(const Pass& ps, bool need_denc, hipStream_t s);
   int pack_down(const Pass& ps, const ConvW& w, hipStream_t s);
   int pack_up(const Pass& ps, const ConvW& w, hipStream_t s);
+  // The layer's launch on its own maps: square, w.Hl on the large side and conv_down_size(w.Hl, k, s, p) on the small side -- the operands come
+  // without sizes and leave with these.  L / S: the large- / small-side tensor (ConvW above).
   // w2 / x2 (optional): the 1x1 conv whose "up" form over x2 (a tensor on the small-side grid) is added in the same kernel
-  int run_down(const Pass& ps, const ConvW& w, const void* L, int Hl, int Wl, void* S, int Hs, int Ws,
-               const float* pro_s, const float* pro_b, int relu, float* stats, int accumulate, int out_dt, hipStream_t s,
-               const ConvW* w2 = nullptr, const void* x2 = nullptr);
-  int run_up(const Pass& ps, const ConvW& w, const void* S, int Hs, int Ws, void* L, int Hl, int Wl,
-             const float* pro_s, const float* pro_b, int relu, float* stats, int accumulate, hipStream_t s,
-             const ConvW* w2 = nullptr, const void* x2 = nullptr);
-  int run_wgrad(const Pass& ps, const ConvW& w, const void* P, int Hs, int Ws, const float* proP_s, const float* proP_b,
-                const void* G, int Hl, int Wl, const float* proG_s, const float* proG_b, hipStream_t s);
+  SecondSrc second_src(const Pass& ps, const ConvW& w, bool fwd, bool frag, const ConvW* w2, const void* x2) const;
+  int run_down(const Pass& ps, const ConvW& w, MapIn L, MapOut S, hipStream_t s, const ConvW* w2 = nullptr, const void* x2 = nullptr);
+  int run_up(const Pass& ps, const ConvW& w, MapIn S, MapOut L, hipStream_t s, const ConvW* w2 = nullptr, const void* x2 = nullptr);
+  // P / G: the small- / large-side operand under its BatchNorm + ReLU prologue, if it has one; scratch: ps.wscratch unless given
+  int run_wgrad(const Pass& ps, const ConvW& w, const BnSide& P, const BnSide& G, hipStream_t s, float* scratch = nullptr,
+                WgradReduceArgs* defer = nullptr);
   // sum of the partial images [D0][D1][ntaps] a fused backward pass left at `parts` -> w's weight gradient
   int reduce_wgrad_parts(const Pass& ps, const ConvW& w, const float* parts, int nparts, int ntaps, hipStream_t s);
   // decoder_bwd leaves its weight gradients running on the side stream; encoder_bwd (or join()) orders them before the caller's stream
