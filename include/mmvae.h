@@ -481,6 +481,32 @@ MMVAE_API size_t mmvae_nearest_frames_scratch_bytes(int M, int64_t F, int D, int
 MMVAE_API int mmvae_nearest_frames(const uint8_t* queries, int M, const uint8_t* frames, int64_t F, int D, const uint8_t* lut, int k,
                                    int32_t* out_dist, int64_t* out_index, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ------------------------------------------------------------------ set-to-set k-NN and ball counts (sample-quality scores)
+ * Every row of a [Na][D] against every row of b [Nb][D]: dense device uint8, 16-byte aligned.  d(i, j) = sum_{t<D} (a[i][t] - b[j][t])^2
+ * in exact integer arithmetic (D * 255^2 <= 1 065 369 600 fits int32); no floating point is used anywhere.  Up to two results per row
+ * of a:
+ *   the k nearest (k in 1..8): the columns are ordered by the pair (d, j) ascending -- equal distances fall to the lower index -- and the
+ *     first k go to out_dist[i][0..k) (int32) and out_index[i][0..k) (int64).  k = 0 with out_dist = out_index = NULL: no selection.
+ *   the ball count: with col_radius (int32 [Nb], every entry >= 0) and out_count (int32 [Na]),
+ *     out_count[i] = #{ j : d(i, j) <= col_radius[j] }, the comparison inclusive and exact.  Both pointers or neither.
+ * A call asks for at least one of the two.  exclude_diagonal != 0 removes the pairs (i, i) from both results (leave-one-out when a and b
+ * are the same set); it requires k <= Nb - 1.
+ * Every output element is written exactly once, none outside the [Na][k] / [Na] arrays, nothing outside scratch_bytes of `scratch`
+ * (16-byte aligned device memory of at least mmvae_knn_cross_scratch_bytes(Na, Nb, D, k, want_count) bytes, a function of the shape
+ * alone; 0 for a shape the call refuses; want_count != 0 when out_count is given).  Determinism: a block owns 128 rows of a and a
+ * contiguous range of columns; its partial k-best lists are keyed (d << 32) | j and merged by key, its partial counts are summed as
+ * integers in a fixed order.  No floating-point atomics: the same bits every run, whatever the grid and however the columns are split.
+ * Capturable: no allocation, no host read, no synchronisation; three launches on `stream`.
+ * Supported: 1 <= Na, Nb <= 2^20, 0 <= k <= 8, D a multiple of 16 in [16, 16384].  A non-positive Na, Nb or D, a negative k, k above the
+ * available columns (Nb, or Nb - 1 with exclude_diagonal), a NULL or misaligned a, b or scratch, col_radius without out_count or the
+ * reverse, out_dist / out_index not both given with k > 0 or not both NULL with k = 0, nothing asked for: MMVAE_ERR_ARG; a too-small
+ * scratch: MMVAE_ERR_WORKSPACE; Na or Nb > 2^20, k > 8, any other D: MMVAE_ERR_UNSUPPORTED.  On an error nothing is enqueued and
+ * mmvae_last_error() names the offending value.  A negative col_radius entry is not an error of the call: that column is in no ball. */
+MMVAE_API size_t mmvae_knn_cross_scratch_bytes(int64_t Na, int64_t Nb, int D, int k, int want_count);
+MMVAE_API int mmvae_knn_cross(const uint8_t* a, int64_t Na, const uint8_t* b, int64_t Nb, int D, int k, int exclude_diagonal,
+                              int32_t* out_dist, int64_t* out_index, const int32_t* col_radius, int32_t* out_count, void* scratch,
+                              size_t scratch_bytes, void* stream);
+
 /* ------------------------------------------------------------------ per-tensor histograms of a flat buffer (wandb.hook_torch, main.py:456)
  * 64-bin histograms and exact statistics of T segments of one flat f32 device buffer -- every parameter's gradient, weight or Adam
  * moment in one call.  segments: T pairs (offset, numel) of int64, in elements of `flat`; any alignment, gaps and numel = 0 allowed.

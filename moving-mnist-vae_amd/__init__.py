@@ -14,6 +14,7 @@ from .monitor import TensorHistograms, make_histogram_callback, tensor_histogram
 from .panels import (column, gray_lut, latent_slide, make_plot_callback, neighbour_sheet, plot_neighbours, plot_pixelcnn, plot_pixelvae,  # noqa: F401
                      plot_vae, render_sheet, sample_from_reconstruction, scatter_panel, scatter_plot, scatter_tone, write_png_gray)
 from .quality import frame_quality, reconstruction_quality  # noqa: F401
+from .samples import ball_counts, cross_neighbours, sample_frames, sample_quality, sample_quality_to_host  # noqa: F401
 
 
 def __getattr__(name):

@@ -86,6 +86,8 @@ PROTOTYPES = {
     "mmvae_posterior_mixture_bwd": (c_int, [P, c_int, P, P, c_int, c_int, P, P, P, P, P, P, P, P, c_size_t, P]),
     "mmvae_nearest_frames_scratch_bytes": (c_size_t, [c_int, c_int64, c_int, c_int]),
     "mmvae_nearest_frames": (c_int, [P, c_int, P, c_int64, c_int, P, c_int, P, P, P, c_size_t, P]),
+    "mmvae_knn_cross_scratch_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int, c_int]),
+    "mmvae_knn_cross": (c_int, [P, c_int64, P, c_int64, c_int, c_int, c_int, P, P, P, P, P, c_size_t, P]),
     "mmvae_tensor_hist_chunks": (c_int64, [P, c_int, c_int64, P, c_int64]),
     "mmvae_tensor_hist_scratch_bytes": (c_size_t, [c_int, c_int64]),
     "mmvae_tensor_hist": (c_int, [P, c_int64, P, P, c_int, P, P, c_int64, P, P, P, P, P, c_size_t, P]),
@@ -148,6 +150,8 @@ LATENT_STATS_ROWS, LATENT_STATS_MAX_D = 6, 512                                  
 MIXTURE_MAX_D, MIXTURE_MAX_N, MIXTURE_MIN_CHUNK = 512, 1 << 20, 64           # mmvae_posterior_mixture: widest latent, most samples / bank rows, fewest rows of a bank chunk
 MIXTURE_BWD_MAX_N = 16384                                                        # mmvae_posterior_mixture_bwd: most samples / bank rows
 NEAREST_MAX_M, NEAREST_MAX_K, NEAREST_MAX_D = 64, 8, 16384                       # mmvae_nearest_frames: queries, neighbours, bytes per plane
+KNN_CROSS_MAX_N, KNN_CROSS_MAX_K, KNN_CROSS_MAX_D = 1 << 20, 8, 16384                # mmvae_knn_cross: rows a side, neighbours, bytes per row
+KNN_CROSS_TILE, KNN_CROSS_TARGET_BLOCKS, KNN_CROSS_MAX_RANGES = 128, 2048, 128       # its block tile and column split (knn_cross.hip: make_plan)
 CLIPGEN_MAX_G, CLIPGEN_MAX_T, CLIPGEN_MAX_K, CLIPGEN_MAX_D, CLIPGEN_DIRECTIONS = 32, 32, 4, 1 << 24, 4096       # MMVAE_CLIPGEN_*
 
 
@@ -183,6 +187,14 @@ def lib():
         fn.argtypes = args
     _lib = l
     return l
+
+
+def knn_cross_ranges(Na: int, Nb: int) -> int:
+    """Contiguous column ranges mmvae_knn_cross cuts ``b`` into at this shape (make_plan of knn_cross.hip); every row of ``a`` gets two
+    partial results per range, merged by key."""
+    tiles = lambda n: (n + KNN_CROSS_TILE - 1) // KNN_CROSS_TILE
+    want = (KNN_CROSS_TARGET_BLOCKS + tiles(Na) - 1) // tiles(Na)
+    return min(want, KNN_CROSS_MAX_RANGES, tiles(Nb))
 
 
 def build_hash() -> str:

@@ -389,6 +389,15 @@ int mmvae_nearest_frames(const uint8_t* queries, int M, const uint8_t* frames, i
   return launch_nearest_frames(queries, M, frames, (long)F, D, lut, k, out_dist, reinterpret_cast<long long*>(out_index), scratch, scratch_bytes,
                                stream_of(st));
 }
+// ---- set-to-set k-NN and ball counts (arguments are checked in the launcher)
+size_t mmvae_knn_cross_scratch_bytes(int64_t Na, int64_t Nb, int D, int k, int want_count) {
+  return knn_cross_scratch_bytes((long)Na, (long)Nb, D, k, want_count);
+}
+int mmvae_knn_cross(const uint8_t* a, int64_t Na, const uint8_t* b, int64_t Nb, int D, int k, int exclude_diagonal, int32_t* out_dist,
+                    int64_t* out_index, const int32_t* col_radius, int32_t* out_count, void* scratch, size_t scratch_bytes, void* st) {
+  return launch_knn_cross(a, (long)Na, b, (long)Nb, D, k, exclude_diagonal, out_dist, reinterpret_cast<long long*>(out_index), col_radius,
+                          out_count, scratch, scratch_bytes, stream_of(st));
+}
 // ---- per-tensor histograms of a flat buffer (arguments are checked in the launcher)
 int64_t mmvae_tensor_hist_chunks(const int64_t* segments, int T, int64_t chunk_elems, int64_t* chunks, int64_t capacity) {
   return tensor_hist_chunks(reinterpret_cast<const long long*>(segments), T, (long long)chunk_elems, reinterpret_cast<long long*>(chunks),

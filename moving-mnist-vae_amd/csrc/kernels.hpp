@@ -499,6 +499,13 @@ int launch_posterior_mixture_bwd(const float* z, int N, const float* mu, const f
 size_t nearest_frames_scratch_bytes(int M, long F, int D, int k);
 int launch_nearest_frames(const unsigned char* queries, int M, const unsigned char* frames, long F, int D, const unsigned char* lut, int k,
                           int* out_dist, long long* out_index, void* scratch, size_t scratch_bytes, hipStream_t s);
+// set-to-set exact k-NN and ball counts (knn_cross.hip): every row of a [Na][D] uint8 against every row of b [Nb][D] uint8, the k smallest
+// (d, j) per row of a (k = 0: none) and / or #{ j : d(i, j) <= col_radius[j] } (col_radius and out_count both NULL: none);
+// exclude_diagonal drops the pairs (i, i).  The scratch size is a function of the shape alone (0 for a shape the launcher refuses);
+// both check their arguments before anything is enqueued.
+size_t knn_cross_scratch_bytes(long Na, long Nb, int D, int k, int want_count);
+int launch_knn_cross(const unsigned char* a, long Na, const unsigned char* b, long Nb, int D, int k, int exclude_diagonal, int* out_dist,
+                     long long* out_index, const int* col_radius, int* out_count, void* scratch, size_t scratch_bytes, hipStream_t s);
 // 64-bin histograms and exact statistics of T segments (offset, numel) of a flat f32 buffer (tensor_hist.hip), work cut into chunks
 // (segment, start, length).  seg_host / chunk_host are checked before anything is enqueued, seg_dev / chunk_dev are what the kernels read.
 long long tensor_hist_chunks(const long long* segments, int T, long long chunk_elems, long long* chunks, long long capacity);

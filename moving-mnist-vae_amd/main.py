@@ -41,9 +41,11 @@ from .decomposition import (LatentPenalty, _decompose, decomposition_to_host, el
                             posterior_mixture)
 from .model import VAE
 from .monitor import TensorHistograms, make_histogram_callback, tensor_histograms  # noqa: F401
-from .panels import (column, gray_lut, latent_slide, make_plot_callback, neighbour_sheet, plot_neighbours, plot_pixelcnn, plot_pixelvae,  # noqa: F401
+from .panels import (_plot_setup, column, gray_lut, latent_slide, make_plot_callback, neighbour_sheet, plot_neighbours, plot_pixelcnn, plot_pixelvae,  # noqa: F401
                      plot_vae, render_sheet, sample_from_reconstruction, scatter_panel, scatter_plot, scatter_tone, write_png_gray)
 from .quality import frame_quality, reconstruction_quality  # noqa: F401
+from . import samples as _samples
+from .samples import ball_counts, cross_neighbours, sample_frames, sample_quality, sample_quality_to_host  # noqa: F401
 
 
 def prepare_batch(model, batch, device, args, data_mean, data_std):
@@ -122,8 +124,11 @@ def train(model, data_loader, optimizer, device, args, epoch=0, data_mean=0, dat
     return losses, nlls, kls, mmds
 
 
+_SAMPLE_QUALITY_K = 3                              # the k of evaluate(sample_quality=n): Naeem et al.'s and sample_quality's default
+
+
 def evaluate(model, data_loader, device, args, data_mean=0, data_std=1, iw_samples=0, weighted=False, generator=None,
-             return_per_image=False, latent_stats=False, quality=False, centres=None, decomposition=False) -> dict:
+             return_per_image=False, latent_stats=False, quality=False, centres=None, decomposition=False, sample_quality=0) -> dict:
     """Held-out evaluation of the HIP model (the reference builds a test loader, main.py:497, and never reads it): one eval-mode pass
     over ``data_loader`` under ``torch.no_grad()``; the model's train / eval mode is restored afterwards and no parameter or buffer
     changes.  Batches are prepared as in ``train``.  Per-image terms come from ``model.per_image_terms`` (and ``model.iw_bound``
@@ -154,9 +159,21 @@ def evaluate(model, data_loader, device, args, data_mean=0, data_std=1, iw_sampl
     device-to-host copy; ``per_image`` gains 'log_qz'.  Known limits: ``mi <= log_m`` by construction (each sample's own posterior is in
     the bank), so a value near ``log_m`` means saturated, not measured; all figures are Monte-Carlo estimates from one sample per image.
     A PixelCNN on its own has ``decomposition`` None; a model built with ``require_rsample=False`` has no q(z|x) density and raises
-    ValueError, as ``iw_bound`` does.  Without the flag nothing changes, keys or bits."""
+    ValueError, as ``iw_bound`` does.  Without the flag nothing changes, keys or bits.
+    ``sample_quality=n`` (n > 0, a plain one-channel VAE) adds ``samples``: {'precision', 'recall', 'density', 'coverage', 'accuracy',
+    'accuracy_real', 'accuracy_fake', 'n_real', 'n_fake', 'k'} of ``n`` decodings of z ~ N(0, I) (``sample_frames``, drawn through
+    ``generator`` AFTER the pass over the loader, so no other entry depends on the argument) against every frame of the loader, both as
+    the grey bytes of the sheets (the input column of ``recon``, the ``normal_sampling`` column; ``centres`` as for ``quality``), by
+    ``sample_quality`` with k = 3, which see for the definitions and the two limits.  The frames are kept on the device as uint8
+    (n_images * S * S bytes); the seven scores join the single device-to-host copy.  Without the argument nothing changes, launch for
+    launch."""
     if not hasattr(model, "per_image_terms"):
         raise TypeError("evaluate() drives the HIP VAE of this package (it needs model.per_image_terms)")
+    n_samples = int(sample_quality or 0)
+    if n_samples < 0:
+        raise ValueError(f"evaluate(sample_quality={n_samples}): the number of samples cannot be negative")
+    if n_samples and (model.only_pixelcnn or model.pixelcnn is not None or model.in_channels != 1):
+        raise ValueError("evaluate(sample_quality=n) needs a plain one-channel VAE (PixelCNN / PixelVAE draw with model.sample_pixels)")
     latent = not model.only_pixelcnn
     want_dec = bool(decomposition) and latent
     if want_dec and not model.require_rsample:
@@ -171,6 +188,9 @@ def evaluate(model, data_loader, device, args, data_mean=0, data_std=1, iw_sampl
         kept.update(mse=[], ssim=[])
     bank = ([], [], [])                            # mu, logvar, encoding of every batch (f32, on the device), with `decomposition`
     n_images = 0
+    real_bytes = []                                # the loader's frames as the recon sheet's input column, with `sample_quality`
+    if n_samples:
+        lo, hi, _ = _plot_setup(model, data_mean, data_std, centres, None, None)
     model.eval()
     try:
         with torch.no_grad():
@@ -205,6 +225,9 @@ def evaluate(model, data_loader, device, args, data_mean=0, data_std=1, iw_sampl
                     q = reconstruction_quality(model, image, reconstruction, data_mean, data_std, centres)
                     sums[3] += q["mse"].sum()
                     sums[4] += q["ssim"].sum()
+                if n_samples:
+                    S = image.shape[-1]
+                    real_bytes.append(render_sheet([column("image", image.detach().float().reshape(N, S, S), lo=lo, hi=hi)], N).view(N, S, S))
                 n_images += N
                 if return_per_image:
                     kept["nll"].append(nll)
@@ -219,7 +242,13 @@ def evaluate(model, data_loader, device, args, data_mean=0, data_std=1, iw_sampl
         model.train(was_training)
     if n_images == 0:
         raise ValueError("evaluate(): the data loader yielded no batch")
-    s_nll, s_kl, s_iw, *s_quality = (v / n_images for v in sums.tolist())               # the one device -> host copy
+    n_sums = sums.numel()
+    if n_samples:
+        fake = _samples.sample_frames(model, n_samples, data_mean, data_std, centres, generator)
+        scores = _samples.sample_quality(torch.cat(real_bytes), fake, k=_SAMPLE_QUALITY_K)
+        sums = torch.cat([sums, torch.stack([scores[key] for key in _samples.SAMPLE_QUALITY_KEYS])])
+    host = sums.tolist()                                                                # the one device -> host copy
+    s_nll, s_kl, s_iw, *s_quality = (v / n_images for v in host[:n_sums])
     latent_out = None
     if want_latent:
         a = acc.cpu().numpy()                                                           # ... and the accumulator's
@@ -236,6 +265,8 @@ def evaluate(model, data_loader, device, args, data_mean=0, data_std=1, iw_sampl
     if quality:
         s_mse, s_ssim = s_quality
         out["quality"] = {"mse": s_mse, "psnr": float("inf") if s_mse == 0.0 else 10.0 * float(np.log10(65025.0 / s_mse)), "ssim": s_ssim}
+    if n_samples:
+        out["samples"] = dict(zip(_samples.SAMPLE_QUALITY_KEYS, host[n_sums:]), n_real=n_images, n_fake=n_samples, k=_SAMPLE_QUALITY_K)
     if return_per_image:
         out["per_image"] = {k: (torch.cat(v) if v else None) for k, v in kept.items()}
     if latent_stats:
