@@ -5,12 +5,13 @@ with ``importlib.import_module("moving-mnist-vae_amd")``.  Importing the package
 a GPU; constructing / running the model does, and fails loudly when the HIP library is absent.
 """
 from .data import (GeneratedClips, MovingMNISTClips, QuantiserFit, choose_transformer, clips_from_npz_array, fit_quantiser,  # noqa: F401
-                   generate_batch, generate_clips, load_idx_images, load_kmeans_file, nearest_frames, pixel_histogram, quantise_frames,
+                   generate_batch, generate_clips, load_idx_images, load_kmeans_file, pixel_histogram, quantise_frames,
                    resize_frames, resize_quantise_frames, save_kmeans_file, save_moving_mnist_files, velocity_table)
 from .decomposition import elbo_decomposition, latent_penalty, make_latent_penalty, posterior_mixture  # noqa: F401
 from .main import (checkpoint_variant, evaluate, generate, generate_only_pixelcnn, latent_stats, load_checkpoint, save_checkpoint,  # noqa: F401
                    select_model, train)
 from .monitor import TensorHistograms, make_histogram_callback, tensor_histograms  # noqa: F401
+from .neighbours import nearest_frames  # noqa: F401
 from .panels import (column, gray_lut, latent_slide, make_plot_callback, neighbour_sheet, plot_neighbours, plot_pixelcnn, plot_pixelvae,  # noqa: F401
                      plot_vae, render_sheet, sample_from_reconstruction, scatter_panel, scatter_plot, scatter_tone, write_png_gray)
 from .quality import frame_quality, reconstruction_quality  # noqa: F401

@@ -1,6 +1,6 @@
 // Set-to-set exact k-NN and ball counts: every row of a [Na][D] uint8 against every row of b [Nb][D] uint8 (mmvae_knn_cross).
 //
-//   d(i, j) = sum_t (a[i][t] - b[j][t])^2 in exact integers.  As in neighbours.hip, with x' = x ^ 0x80 read as int8 on both sides,
+//   d(i, j) = sum_t (a[i][t] - b[j][t])^2 in exact integers.  With x' = x ^ 0x80 read as int8 on both sides,
 //   d = |a'|^2 + |b'|^2 - 2 a'.b', and the cross term is a tiled int8 GEMM on v_mfma_i32_16x16x64_i8; every term stays below 2^31.
 //
 // Three launches:
@@ -8,38 +8,30 @@
 //   kc_sweep_kernel  a block of four waves owns a tile of kTile = 128 rows of `a` and a contiguous range of 128-column tiles of `b`
 //                    (dealt out so that the blocks of one XCD share tiles in its L2, see the kernel).  Per column tile it walks D in chunks of 128 bytes: every thread
 //                    loads 4 + 4 16-byte pieces into registers (the next chunk's loads are in flight during this chunk's products), turns
-//                    them to signed bytes (zeros past D) and stores them to LDS in the operand order of neighbours.hip: fragment
-//                    (16-row tile t, 64-byte k step u) holds, for lane l, bytes [64 u + 16 (l >> 4), +16) of row 16 t + (l & 15) -- the same
-//                    lane -> (row, k) map for A and B, so the k order inside a step, whatever the hardware makes of it, is the same on
-//                    both sides.  Stores and loads are lane-contiguous 16-byte accesses: no bank conflicts.  A wave owns a 64 x 64
-//                    quarter of the block tile, 4 x 4 accumulator tiles: per k step it reads 4 A and 4 B fragments for 16 MFMAs
-//                    (the M = 64 scan of neighbours.hip reads one B fragment per 4).  C/D: col = l & 15, row = 4 (l >> 4) + reg.
+//                    them to signed bytes (zeros past D) and stores them to LDS in the operand fragment order (knn_select.hpp), 16-row
+//                    tile t and k step u at [t][u][lane].  Stores and loads are lane-contiguous 16-byte accesses: no bank conflicts.
+//                    A wave owns a 64 x 64 quarter of the block tile, 4 x 4 accumulator tiles: per k step it reads 4 A and 4 B fragments
+//                    for 16 MFMAs.
 //                    Epilogue per column tile: d from the norms; the ball test d <= col_radius[j] adds to 16 per-lane counters (one per
-//                    (row tile, reg)); the selection is the one of neighbours.hip -- lane l of a wave owns row l of the wave's 64, a sorted
-//                    list of its smallest keys (d << 32) | j in LDS, the k-th in a register, one ballot per four rows rejects the common
-//                    case.  At the end of the range every wave writes one list and one count per row to scratch: `parts` = 2 x ranges
-//                    partial results per row (the two waves side by side in a block keep separate lists).
-//   kc_merge_kernel  a wave per row: k rounds of "smallest key above the last one chosen" over the row's parts x k keys (keys are distinct:
-//                    each holds its column), and the integer sum of its partial counts.
-// A list holds exactly the k smallest keys of the columns its wave saw and the merge takes the k smallest of the union; the counts are
-// integer sums: the outputs are a function of the inputs alone -- the same bits every run, for any split of the columns.
+//                    (row tile, reg)); the selection (knn_select.hpp): lane l of a wave owns row l of the wave's 64, one ballot per four
+//                    rows rejects the common case.  At the end of the range every wave writes one list and one count per row to
+//                    scratch: `parts` = 2 x ranges partial results per row (the two waves side by side in a block keep separate lists).
+//   kc_merge_kernel  a wave per row: the k merge rounds over the row's parts x k keys, and the integer sum of its partial counts.
+// Operand order, key, list and tie rule are defined in knn_select.hpp; the counts are integer sums: the same bits every run, for any
+// split of the columns.
 #include "common.hpp"
 #include "kernels.hpp"
+#include "knn_select.hpp"
 
 namespace mmvae {
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-typedef unsigned long long u64;
-
-constexpr int kMaxK = 8, kMaxD = 16384;
 constexpr long kMaxN = 1L << 20;
 constexpr int kTile = 128;                             // rows of a and columns of b in a block tile
 constexpr int kThreads = 256;
 constexpr int kTargetBlocks = 2048;                    // a few rounds of two blocks per CU: the tail round stays small
 constexpr int kMaxRanges = 128;
-constexpr u64 kNoKey = ~0ull;
 
 struct Plan {
   int row_tiles, col_tiles, ranges, parts;
@@ -72,60 +64,13 @@ __global__ __launch_bounds__(256) void kc_norm_kernel(const unsigned char* __res
   int n = 0;
   for (int off = lane * 16; off < D; off += 64 * 16) {
     uint4 v = *reinterpret_cast<const uint4*>(src + off);
-    v.x ^= 0x80808080u; v.y ^= 0x80808080u; v.z ^= 0x80808080u; v.w ^= 0x80808080u;
-    n = __builtin_amdgcn_sdot4((int)v.x, (int)v.x, n, false);
-    n = __builtin_amdgcn_sdot4((int)v.y, (int)v.y, n, false);
-    n = __builtin_amdgcn_sdot4((int)v.z, (int)v.z, n, false);
-    n = __builtin_amdgcn_sdot4((int)v.w, (int)v.w, n, false);
+    n = signed_norm16(v, n);
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
   if (lane == 0) {
     if (row < Na) an[row] = n;
     else bn[row - Na] = n;
-  }
-}
-
-__device__ __forceinline__ u64 shfl64(u64 v, int src) {
-  return ((u64)(uint32_t)__shfl((int)(v >> 32), src, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)v, src, 64);
-}
-
-// The selection step of neighbours.hip (nn_insert) for a wave that owns 64 rows: lane l owns row l, its sorted keys sit in LDS at
-// list[j * kThreads] (a column per thread), the k-th of them in `thr`.  The keys cand[nt] of (row tile rt, accumulator register r) -- the
-// row of lane group g is 16 rt + 4 g + r -- go in one per group and turn: the first lane of a group with a key below its row's `thr`
-// offers its smallest, the row's owner fetches it and shifts its list.  `thr` is fetched afresh every turn.
-template <int CNT>
-__device__ __forceinline__ void kc_insert(u64 (&cand)[CNT], int rt, int r, u64* list, u64& thr, int k) {
-  const int lane = threadIdx.x & 63, grp = lane >> 4, row = rt * 16 + grp * 4 + r;
-  const int og = (lane >> 2) & 3;                         // the lane group whose row this lane owns, if it owns one of these four rows
-  const bool owner = (lane >> 4) == rt && (lane & 3) == r;
-  for (;;) {
-    const u64 t = shfl64(thr, row);
-    u64 best = cand[0];
-#pragma unroll
-    for (int nt = 1; nt < CNT; ++nt) best = cand[nt] < best ? cand[nt] : best;
-    const bool c = best < t;
-    const u64 m = __ballot(c);
-    if (!m) break;
-    const unsigned mine = (unsigned)(m >> (16 * grp)) & 0xffffu, theirs = (unsigned)(m >> (16 * og)) & 0xffffu;
-    const u64 nk = shfl64(best, 16 * og + (theirs ? __builtin_ctz(theirs) : 0));
-    if (mine && (lane & 15) == __builtin_ctz(mine)) {     // the offered key leaves its lane (keys are distinct)
-#pragma unroll
-      for (int nt = 0; nt < CNT; ++nt) cand[nt] = cand[nt] == best ? kNoKey : cand[nt];
-    }
-    if (owner && theirs) {                                // nk is below list[k - 1]: it goes in, the last key drops out
-      u64 e[kMaxK];
-#pragma unroll
-      for (int j = 0; j < kMaxK; ++j) e[j] = list[j * kThreads];
-#pragma unroll
-      for (int j = kMaxK - 1; j > 0; --j) e[j] = e[j] < nk ? e[j] : (e[j - 1] < nk ? nk : e[j - 1]);
-      e[0] = e[0] < nk ? e[0] : nk;
-#pragma unroll
-      for (int j = 0; j < kMaxK; ++j) {
-        list[j * kThreads] = e[j];
-        thr = j == k - 1 ? e[j] : thr;
-      }
-    }
   }
 }
 
@@ -157,9 +102,8 @@ __global__ __launch_bounds__(kThreads, 2) void kc_sweep_kernel(const unsigned ch
   const int row_tile = deal_rows ? dealt : slot % fast, range = deal_rows ? slot % fast : dealt;
   if (row_tile >= row_tiles || range >= ranges) return;   // the padding of the dealt axis to a multiple of 8 (uniform over the block)
   const int row0 = row_tile * kTile + wr * 64;            // the first row of this wave's quarter
-#pragma unroll
-  for (int j = 0; j < kMaxK; ++j) s_list[j][tid] = kNoKey;
   u64* list = &s_list[0][tid];
+  knn_list_init<kThreads>(list);
   u64 thr = kNoKey;                                       // list[k - 1] of this lane's row
   int cnt[4][4];
 #pragma unroll
@@ -255,19 +199,16 @@ __global__ __launch_bounds__(kThreads, 2) void kc_sweep_kernel(const unsigned ch
           const int d = anorm + bnorm[nt] - 2 * acc[rt][nt][r];
           const bool live = i < Na && j < Nb && !(exclude_diagonal && i == j);
           cnt[rt][r] += (live && d <= rad[nt]) ? 1 : 0;
-          cand[nt] = live ? (((u64)(uint32_t)d << 32) | (u64)(uint32_t)j) : kNoKey;
+          cand[nt] = live ? knn_key(d, (uint32_t)j) : kNoKey;
           hit |= cand[nt] < last;
         }
-        if (k > 0 && __ballot(hit)) kc_insert<4>(cand, rt, r, list, thr, k);
+        if (k > 0 && __ballot(hit)) knn_insert<4, kThreads>(cand, rt, r, list, thr, k);
       }
     }
   }
   // ---- one list and one count per row of this wave's quarter; part = 2 range + wave column
   const long part = (long)range * 2 + wc;
-  if (k > 0 && row0 + lane < Na) {
-    u64* dst = lists + (part * Na + row0 + lane) * (long)k;
-    for (int j = 0; j < k; ++j) dst[j] = list[j * kThreads];
-  }
+  if (k > 0 && row0 + lane < Na) knn_list_store<kThreads>(lists + (part * Na + row0 + lane) * (long)k, list, k);
   if (counts) {
 #pragma unroll
     for (int rt = 0; rt < 4; ++rt)
@@ -290,19 +231,10 @@ __global__ __launch_bounds__(256) void kc_merge_kernel(const u64* __restrict__ l
   if (i >= Na) return;
   u64 prev = 0;
   for (int j = 0; j < k; ++j) {
-    u64 best = kNoKey;
-    for (int e = lane; e < parts * k; e += 64) {
-      const u64 v = lists[((long)(e / k) * Na + i) * k + e % k];
-      if ((j == 0 || v > prev) && v < best) best = v;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const u64 other = ((u64)(uint32_t)__shfl_xor((int)(best >> 32), o, 64) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)best, o, 64);
-      if (other < best) best = other;
-    }
+    const u64 best = wave_min64(knn_merge_pick(lists, parts, Na, i, k, j, prev, lane, 64));
     if (lane == 0) {
-      out_dist[(long)i * k + j] = (int)(best >> 32);
-      out_index[(long)i * k + j] = (long long)(best & 0xffffffffull);
+      out_dist[(long)i * k + j] = knn_key_dist(best);
+      out_index[(long)i * k + j] = knn_key_index(best);
     }
     prev = best;
   }
@@ -319,12 +251,10 @@ __global__ __launch_bounds__(256) void kc_merge_kernel(const u64* __restrict__ l
 int check_shape(const char* who, long Na, long Nb, int D, int k) {
   if (Na < 1) { set_error("%s: Na=%ld must be positive", who, Na); return MMVAE_ERR_ARG; }
   if (Nb < 1) { set_error("%s: Nb=%ld must be positive", who, Nb); return MMVAE_ERR_ARG; }
-  if (D < 1) { set_error("%s: D=%d must be positive", who, D); return MMVAE_ERR_ARG; }
-  if (k < 0) { set_error("%s: k=%d must not be negative", who, k); return MMVAE_ERR_ARG; }
+  if (const int rc = knn_check_signs(who, D, k, 0)) return rc;
   if (Na > kMaxN) { set_error("%s: Na=%ld unsupported (1..%ld rows)", who, Na, kMaxN); return MMVAE_ERR_UNSUPPORTED; }
   if (Nb > kMaxN) { set_error("%s: Nb=%ld unsupported (1..%ld rows)", who, Nb, kMaxN); return MMVAE_ERR_UNSUPPORTED; }
-  if (k > kMaxK) { set_error("%s: k=%d unsupported (0..%d neighbours)", who, k, kMaxK); return MMVAE_ERR_UNSUPPORTED; }
-  if (D % 16 != 0 || D > kMaxD) { set_error("%s: D=%d unsupported (a multiple of 16 in 16..%d)", who, D, kMaxD); return MMVAE_ERR_UNSUPPORTED; }
+  if (const int rc = knn_check_limits(who, D, k, 0)) return rc;
   if (k > Nb) { set_error("%s: k=%d exceeds Nb=%ld", who, k, Nb); return MMVAE_ERR_ARG; }
   return 0;
 }
@@ -339,7 +269,7 @@ size_t knn_cross_scratch_bytes(long Na, long Nb, int D, int k, int want_count) {
 
 int launch_knn_cross(const unsigned char* a, long Na, const unsigned char* b, long Nb, int D, int k, int exclude_diagonal, int* out_dist,
                      long long* out_index, const int* col_radius, int* out_count, void* scratch, size_t scratch_bytes, hipStream_t s) {
-  const int rc = check_shape("knn_cross", Na, Nb, D, k);
+  int rc = check_shape("knn_cross", Na, Nb, D, k);
   if (rc != 0) return rc;
   if (exclude_diagonal && k > Nb - 1) { set_error("knn_cross: k=%d exceeds the Nb-1=%ld columns left without the diagonal", k, Nb - 1); return MMVAE_ERR_ARG; }
   if ((col_radius != nullptr) != (out_count != nullptr)) {
@@ -351,21 +281,13 @@ int launch_knn_cross(const unsigned char* a, long Na, const unsigned char* b, lo
     return MMVAE_ERR_ARG;
   }
   if (k == 0 && !out_count) { set_error("knn_cross: k=0 and no out_count: nothing is asked for"); return MMVAE_ERR_ARG; }
-  if (!a || !b || !scratch) { set_error("knn_cross: NULL %s", !a ? "a" : !b ? "b" : "scratch"); return MMVAE_ERR_ARG; }
-  if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)scratch) & 15) {
-    set_error("knn_cross: a=%p, b=%p and scratch=%p must be 16-byte aligned", (const void*)a, (const void*)b, scratch);
-    return MMVAE_ERR_ARG;
-  }
   const Plan p = make_plan(Na, Nb, k, out_count != nullptr);
-  if (scratch_bytes < p.total) {
-    set_error("knn_cross: scratch_bytes=%zu below the %zu this shape needs", scratch_bytes, p.total);
-    return MMVAE_ERR_WORKSPACE;
-  }
-  unsigned char* base = static_cast<unsigned char*>(scratch);
-  int* an = reinterpret_cast<int*>(base);
-  int* bn = reinterpret_cast<int*>(base + p.bn_off);
-  u64* lists = reinterpret_cast<u64*>(base + p.lists_off);
-  int* counts = out_count ? reinterpret_cast<int*>(base + p.counts_off) : nullptr;
+  rc = knn_check_buffers("knn_cross", {{"a", a}, {"b", b}, {"scratch", scratch}}, scratch_bytes, p.total);
+  if (rc != 0) return rc;
+  int* an = knn_carve<int>(scratch, 0);
+  int* bn = knn_carve<int>(scratch, p.bn_off);
+  u64* lists = knn_carve<u64>(scratch, p.lists_off);
+  int* counts = out_count ? knn_carve<int>(scratch, p.counts_off) : nullptr;
   hipLaunchKernelGGL(kc_norm_kernel, dim3((unsigned)((Na + Nb + 3) / 4)), dim3(256), 0, s, a, Na, b, Nb, D, an, bn);
   int e = check_launch("knn_cross (norms)");
   if (e != 0) return e;

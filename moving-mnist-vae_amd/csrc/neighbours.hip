@@ -8,36 +8,28 @@
 //   nn_prep_kernel   queries -> signed bytes in the A-operand fragment order [row tile][k step][lane][16 B], zero rows / zero bytes where
 //                    M_p > M or the last 64-byte k step passes D (zeros add nothing to the product), and the query norms qn[64].
 //   nn_scan_kernel   the pass over `frames`.  The 16-frame tiles are cut into contiguous, equal (+-1 tile) ranges, one per wave; a wave walks
-//                    its range in walks of up to four tiles.  A k step is 64 bytes of every frame of the tile: lane l holds bytes
-//                    [64 s + 16 (l >> 4), +16) of frame (l & 15) as the B operand and the same bytes of query row (l & 15) as A, so row and
-//                    column are l & 15 on both sides and the k order, whatever the hardware makes of it, is the same for both operands
-//                    (a sum over k does not care).  Loaded in that order an instruction would touch 64 bytes of 16 rows, half a line each;
+//                    its range in walks of up to four tiles.  A k step is 64 bytes of every frame of the tile, the frames as B and the
+//                    query rows as A.  Loaded in the operand order an instruction would touch 64 bytes of 16 rows, half a line each;
 //                    instead two k steps are read as whole 128-byte lines (8 rows an instruction) and pass through a per-wave LDS stage
 //                    into the operand order (measured: 3.8 against 3.0 TB/s at M = 6).
-//                    Frame norms come from the bytes in registers (v_dot4_i32_i8).  C/D: col = l & 15, row = 4 (l >> 4) + reg.
-//                    Selection: lane l of a wave owns query row l: a sorted list of its smallest keys (d << 32) | f in LDS, the k-th of
-//                    them in a register; one unsigned compare is the order (d, f).  The 4 x RT x CNT keys of a lane are tested against
-//                    their rows' k-th keys, one ballot per four rows rejects them (the common case); survivors go to the owners one per
-//                    16-lane group and turn.  The first k of every list go to scratch at the end, unused slots as ~0.
-//   nn_merge_kernel  a block per query: k rounds of "smallest key above the last one chosen" over all lists (keys are distinct: each
-//                    holds its frame index), then out_dist / out_index.  ~0 is never reached because F >= k.
-// A list holds exactly the k smallest keys of the frames its wave saw, whatever their order, and the merge takes the k smallest of the
-// union: the outputs are a function of the inputs alone -- the same bits every run, for any partition of the frames.
+//                    Frame norms come from the bytes in registers (v_dot4_i32_i8).
+//                    Selection (knn_select.hpp): lane l of a wave owns query row l; the 4 x RT x CNT keys of a lane are tested against
+//                    their rows' k-th keys, one ballot per four rows rejects them (the common case).  The first k of every list go
+//                    to scratch at the end, unused slots as ~0.
+//   nn_merge_kernel  a block per query: the k merge rounds over all lists, then out_dist / out_index.  ~0 is never reached because F >= k.
+// Operand order, key, list and tie rule are defined in knn_select.hpp; the same bits every run, for any partition of the frames.
 #include "common.hpp"
 #include "kernels.hpp"
+#include "knn_select.hpp"
 
 namespace mmvae {
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-typedef unsigned long long u64;
-
-constexpr int kMaxM = 64, kMaxK = 8, kMaxD = 16384;
+constexpr int kMaxM = 64;
 constexpr int kScanThreads = 256, kScanWaves = kScanThreads / 64;
 constexpr int kMaxBlocks = 512;                      // two blocks of four waves per CU
 constexpr int kNT = 4;                               // 16-frame tiles a wave carries through one walk over D
-constexpr u64 kNoKey = ~0ull;
 
 struct Plan {
   int Mp, RT, KS;                                     // query rows padded to 16, row tiles, 64-byte k steps
@@ -73,12 +65,7 @@ __global__ __launch_bounds__(256) void nn_prep_kernel(const unsigned char* __res
     uint4 v = make_uint4(0u, 0u, 0u, 0u);
     if (row < M && off < D) {
       v = *reinterpret_cast<const uint4*>(q + (long)row * D + off);
-      v.x ^= 0x80808080u; v.y ^= 0x80808080u; v.z ^= 0x80808080u; v.w ^= 0x80808080u;
-      int n = __builtin_amdgcn_sdot4((int)v.x, (int)v.x, 0, false);
-      n = __builtin_amdgcn_sdot4((int)v.y, (int)v.y, n, false);
-      n = __builtin_amdgcn_sdot4((int)v.z, (int)v.z, n, false);
-      n = __builtin_amdgcn_sdot4((int)v.w, (int)v.w, n, false);
-      atomicAdd(&norm[l & 15], n);                    // integer adds in LDS: any order, the same sum
+      atomicAdd(&norm[l & 15], signed_norm16(v, 0));  // integer adds in LDS: any order, the same sum
     }
     qs[((long)rt * KS + s) * 64 + l] = v;
   }
@@ -89,50 +76,6 @@ __global__ __launch_bounds__(256) void nn_prep_kernel(const unsigned char* __res
 // table lookup of the four bytes of a dword; the table already holds t(b) ^ 0x80
 __device__ __forceinline__ uint32_t lut4(const unsigned char* t, uint32_t w) {
   return (uint32_t)t[w & 255u] | ((uint32_t)t[(w >> 8) & 255u] << 8) | ((uint32_t)t[(w >> 16) & 255u] << 16) | ((uint32_t)t[w >> 24] << 24);
-}
-
-__device__ __forceinline__ u64 shfl64(u64 v, int src) {
-  return ((u64)(uint32_t)__shfl((int)(v >> 32), src, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)v, src, 64);
-}
-
-// The k-best lists of a wave: lane l owns query row l.  Its sorted keys sit in LDS, list[j * kScanThreads + l] for this wave's slice of
-// `list` (a column per lane: no bank conflicts, nobody else touches it), the k-th of them also in the register `thr`.
-// The keys cand[nt] of (row tile rt, accumulator register r) -- the row of lane group g is 16 rt + 4 g + r, so the four groups hold
-// four different rows -- go in, one per group and turn: the first lane of a group with a key below its row's `thr` offers its
-// smallest, the row's owner fetches it and shifts its list.  `thr` is fetched afresh every turn: an insertion may have lowered it.
-template <int CNT>
-__device__ __forceinline__ void nn_insert(u64 (&cand)[CNT], int rt, int r, u64* list, u64& thr, int k) {
-  const int lane = threadIdx.x & 63, grp = lane >> 4, row = rt * 16 + grp * 4 + r;
-  const int og = (lane >> 2) & 3;                         // the lane group whose row this lane owns, if it owns one of these four rows
-  const bool owner = (lane >> 4) == rt && (lane & 3) == r;
-  for (;;) {
-    const u64 t = shfl64(thr, row);
-    u64 best = cand[0];
-#pragma unroll
-    for (int nt = 1; nt < CNT; ++nt) best = cand[nt] < best ? cand[nt] : best;
-    const bool c = best < t;
-    const u64 m = __ballot(c);
-    if (!m) break;
-    const unsigned mine = (unsigned)(m >> (16 * grp)) & 0xffffu, theirs = (unsigned)(m >> (16 * og)) & 0xffffu;
-    const u64 nk = shfl64(best, 16 * og + (theirs ? __builtin_ctz(theirs) : 0));
-    if (mine && (lane & 15) == __builtin_ctz(mine)) {     // the offered key leaves its lane (keys are distinct)
-#pragma unroll
-      for (int nt = 0; nt < CNT; ++nt) cand[nt] = cand[nt] == best ? kNoKey : cand[nt];
-    }
-    if (owner && theirs) {                                // nk is below list[k - 1]: it goes in, the last key drops out
-      u64 e[kMaxK];
-#pragma unroll
-      for (int j = 0; j < kMaxK; ++j) e[j] = list[j * kScanThreads];
-#pragma unroll
-      for (int j = kMaxK - 1; j > 0; --j) e[j] = e[j] < nk ? e[j] : (e[j - 1] < nk ? nk : e[j - 1]);
-      e[0] = e[0] < nk ? e[0] : nk;
-#pragma unroll
-      for (int j = 0; j < kMaxK; ++j) {
-        list[j * kScanThreads] = e[j];
-        thr = j == k - 1 ? e[j] : thr;
-      }
-    }
-  }
 }
 
 template <int RT, bool LUT, int CNT, bool TAIL>
@@ -269,7 +212,7 @@ __device__ __forceinline__ void nn_unit(const unsigned char* __restrict__ frames
     const int row = rt * 16 + grp * 4 + r;
     const long f = (tile0 + nt) * 16 + col;
     const int d = qn[row] + fn[nt] - 2 * acc[rt][nt][r];
-    return row < M && f < F ? (((u64)(uint32_t)d << 32) | (u64)f) : kNoKey;
+    return row < M && f < F ? knn_key(d, (u64)f) : kNoKey;
   };
   // almost every frame fails against its row's k-th best: one compare per key and one ballot per four rows is the common path
 #pragma unroll
@@ -284,7 +227,7 @@ __device__ __forceinline__ void nn_unit(const unsigned char* __restrict__ frames
         cand[nt] = key_of(rt, nt, r);
         hit |= cand[nt] < last;
       }
-      if (__ballot(hit)) nn_insert<CNT>(cand, rt, r, list, thr, k);
+      if (__ballot(hit)) knn_insert<CNT, kScanThreads>(cand, rt, r, list, thr, k);
     }
 }
 
@@ -300,10 +243,9 @@ __global__ __launch_bounds__(kScanThreads, 2) void nn_scan_kernel(const unsigned
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);          // in a scalar register: what follows from it is uniform to the compiler too
   if (tid < kMaxM) s_qn[tid] = tid < RT * 16 ? qn_g[tid] : 0;
   if (LUT) s_tab[tid] = lut[tid] ^ 0x80;
-#pragma unroll
-  for (int j = 0; j < kMaxK; ++j) s_list[j][tid] = kNoKey;
-  __syncthreads();
   u64* list = &s_list[0][tid];
+  knn_list_init<kScanThreads>(list);
+  __syncthreads();
   u64 thr = kNoKey;                                       // list[k - 1] of this lane's row
   const long w = (long)blockIdx.x * kScanWaves + wave, nw = (long)gridDim.x * kScanWaves;
   const long t0 = w * tiles / nw, t1 = (w + 1) * tiles / nw;       // tiles < 2^27, nw <= 2048: no overflow
@@ -321,10 +263,7 @@ __global__ __launch_bounds__(kScanThreads, 2) void nn_scan_kernel(const unsigned
     }
     t += cnt;
   }
-  if (lane < M) {
-    u64* dst = lists + (w * M + lane) * (long)k;
-    for (int j = 0; j < k; ++j) dst[j] = list[j * kScanThreads];
-  }
+  if (lane < M) knn_list_store<kScanThreads>(lists + (w * M + lane) * (long)k, list, k);
 }
 
 // ---- merge.  grid M, 256 threads
@@ -334,16 +273,7 @@ __global__ __launch_bounds__(256) void nn_merge_kernel(const u64* __restrict__ l
   const int m = blockIdx.x, tid = threadIdx.x;
   u64 prev = 0;
   for (int j = 0; j < k; ++j) {
-    u64 best = kNoKey;
-    for (int i = tid; i < nlists * k; i += 256) {
-      const u64 v = lists[((long)(i / k) * M + m) * k + i % k];
-      if ((j == 0 || v > prev) && v < best) best = v;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const u64 other = ((u64)(uint32_t)__shfl_xor((int)(best >> 32), o, 64) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)best, o, 64);
-      if (other < best) best = other;
-    }
+    u64 best = wave_min64(knn_merge_pick(lists, nlists, M, m, k, j, prev, tid, 256));
     __syncthreads();                                    // the previous round's red[] has been read
     if ((tid & 63) == 0) red[tid >> 6] = best;
     __syncthreads();
@@ -351,8 +281,8 @@ __global__ __launch_bounds__(256) void nn_merge_kernel(const u64* __restrict__ l
 #pragma unroll
     for (int i = 1; i < 4; ++i) if (red[i] < best) best = red[i];
     if (tid == 0) {
-      out_dist[m * k + j] = (int)(best >> 32);
-      out_index[m * k + j] = (long long)(best & 0xffffffffull);
+      out_dist[m * k + j] = knn_key_dist(best);
+      out_index[m * k + j] = knn_key_index(best);
     }
     prev = best;
   }
@@ -369,15 +299,13 @@ void launch_scan(bool with_lut, const Plan& p, const unsigned char* frames, long
                        k, lists);
 }
 
-// the argument contract of both entry points; 0 when the shape is served
+// the shape contract of both entry points; 0 when the shape is served
 int check_shape(const char* who, int M, long F, int D, int k) {
   if (M < 1) { set_error("%s: M=%d must be positive", who, M); return MMVAE_ERR_ARG; }
   if (F < 1) { set_error("%s: F=%ld must be positive", who, F); return MMVAE_ERR_ARG; }
-  if (D < 1) { set_error("%s: D=%d must be positive", who, D); return MMVAE_ERR_ARG; }
-  if (k < 1) { set_error("%s: k=%d must be positive", who, k); return MMVAE_ERR_ARG; }
+  if (const int rc = knn_check_signs(who, D, k, 1)) return rc;
   if (M > kMaxM) { set_error("%s: M=%d unsupported (1..%d queries)", who, M, kMaxM); return MMVAE_ERR_UNSUPPORTED; }
-  if (k > kMaxK) { set_error("%s: k=%d unsupported (1..%d neighbours)", who, k, kMaxK); return MMVAE_ERR_UNSUPPORTED; }
-  if (D % 16 != 0 || D > kMaxD) { set_error("%s: D=%d unsupported (a multiple of 16 in 16..%d)", who, D, kMaxD); return MMVAE_ERR_UNSUPPORTED; }
+  if (const int rc = knn_check_limits(who, D, k, 1)) return rc;
   if (F > 2147483647L) { set_error("%s: F=%ld unsupported (at most 2^31 - 1 frames)", who, F); return MMVAE_ERR_UNSUPPORTED; }
   if (k > F) { set_error("%s: k=%d exceeds F=%ld", who, k, F); return MMVAE_ERR_ARG; }
   return 0;
@@ -392,25 +320,15 @@ size_t nearest_frames_scratch_bytes(int M, long F, int D, int k) {
 
 int launch_nearest_frames(const unsigned char* queries, int M, const unsigned char* frames, long F, int D, const unsigned char* lut, int k,
                           int* out_dist, long long* out_index, void* scratch, size_t scratch_bytes, hipStream_t s) {
-  const int rc = check_shape("nearest_frames", M, F, D, k);
+  int rc = check_shape("nearest_frames", M, F, D, k);
   if (rc != 0) return rc;
-  if (!queries || !frames || !out_dist || !out_index || !scratch) {
-    set_error("nearest_frames: NULL %s", !queries ? "queries" : !frames ? "frames" : !out_dist ? "out_dist" : !out_index ? "out_index" : "scratch");
-    return MMVAE_ERR_ARG;
-  }
-  if (((uintptr_t)queries | (uintptr_t)frames | (uintptr_t)scratch) & 15) {
-    set_error("nearest_frames: queries=%p, frames=%p and scratch=%p must be 16-byte aligned", (const void*)queries, (const void*)frames, scratch);
-    return MMVAE_ERR_ARG;
-  }
   const Plan p = make_plan(M, F, D, k);
-  if (scratch_bytes < p.total) {
-    set_error("nearest_frames: scratch_bytes=%zu below the %zu this shape needs", scratch_bytes, p.total);
-    return MMVAE_ERR_WORKSPACE;
-  }
-  unsigned char* base = static_cast<unsigned char*>(scratch);
-  uint4* qs = reinterpret_cast<uint4*>(base);
-  int* qn = reinterpret_cast<int*>(base + p.qn_off);
-  u64* lists = reinterpret_cast<u64*>(base + p.lists_off);
+  rc = knn_check_buffers("nearest_frames", {{"queries", queries}, {"frames", frames}, {"out_dist", out_dist}, {"out_index", out_index},
+                                            {"scratch", scratch}}, scratch_bytes, p.total);
+  if (rc != 0) return rc;
+  uint4* qs = knn_carve<uint4>(scratch, 0);
+  int* qn = knn_carve<int>(scratch, p.qn_off);
+  u64* lists = knn_carve<u64>(scratch, p.lists_off);
   hipLaunchKernelGGL(nn_prep_kernel, dim3((unsigned)p.RT), dim3(256), 0, s, queries, M, D, p.KS, qs, qn);
   int e = check_launch("nearest_frames (prep)");
   if (e != 0) return e;

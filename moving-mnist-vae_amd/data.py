@@ -179,75 +179,6 @@ def pixel_histogram(frames_u8, clip_index=None):
     return counts
 
 
-def _nearest_args(queries, frames, k, lut, what):
-    """Every check of ``nearest_frames`` (nothing is launched here): returns (queries (M, D), frames (F, D), k, lut on the device or
-    None, (H, W)), both planes dense and 16-byte aligned."""
-    from . import _lib as L
-    if isinstance(frames, MovingMNISTClips):
-        frames = frames.clips
-    for t, name in ((queries, "queries"), (frames, "frames")):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
-            raise ValueError(f"{what}: {name} must be a uint8 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
-    if frames.dim() < 2:
-        raise ValueError(f"{what}: frames must have shape [..., H, W], got {tuple(frames.shape)}")
-    H, W = int(frames.shape[-2]), int(frames.shape[-1])
-    D = H * W
-    if queries.dim() == 4 and queries.shape[1] == 1:
-        queries = queries[:, 0]
-    if queries.dim() not in (2, 3):
-        raise ValueError(f"{what}: queries must have shape [M, H, W], [M, 1, H, W] or [M, H*W], got {tuple(queries.shape)}")
-    M = int(queries.shape[0])
-    if (tuple(queries.shape[1:]) != (H, W)) if queries.dim() == 3 else (int(queries.shape[1]) != D):
-        raise ValueError(f"{what}: query planes {tuple(queries.shape[1:])} do not match the frames' {H} x {W}")
-    F = frames.numel() // D if D else 0
-    k = int(k)
-    if not 1 <= k <= L.NEAREST_MAX_K:
-        raise ValueError(f"{what}: k={k} unsupported (1..{L.NEAREST_MAX_K})")
-    if not 1 <= M <= L.NEAREST_MAX_M:
-        raise ValueError(f"{what}: M={M} queries unsupported (1..{L.NEAREST_MAX_M})")
-    if D % 16 or not 16 <= D <= L.NEAREST_MAX_D:
-        raise ValueError(f"{what}: D={D} bytes per plane unsupported (a multiple of 16 in 16..{L.NEAREST_MAX_D})")
-    if not k <= F <= 2 ** 31 - 1:
-        raise ValueError(f"{what}: F={F} frames for k={k} (k..2^31 - 1)")
-    if lut is not None:
-        lut = torch.as_tensor(lut)
-        if lut.dtype != torch.uint8 or lut.numel() != 256:
-            raise ValueError(f"{what}: lut is 256 uint8 values")
-    if not frames.is_cuda or not queries.is_cuda:
-        raise ValueError(f"{what} expects queries and frames on the GPU")
-    if queries.device != frames.device:
-        raise ValueError(f"{what}: queries on {queries.device}, frames on {frames.device}")
-    q, f = queries.detach().reshape(M, D).contiguous(), frames.detach().reshape(F, D).contiguous()
-    q, f = (t if t.data_ptr() % 16 == 0 else t.clone() for t in (q, f))
-    if lut is not None:
-        lut = lut.detach().reshape(-1).to(f.device).contiguous()
-    return q, f, k, lut, (H, W)
-
-
-def _nearest_launch(q, f, k, lut):
-    (M, D), F = q.shape, f.shape[0]
-    nbytes = lib().mmvae_nearest_frames_scratch_bytes(M, F, D, k)
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=f.device)
-    dist = torch.empty((M, k), dtype=torch.int32, device=f.device)
-    index = torch.empty((M, k), dtype=torch.int64, device=f.device)
-    call("mmvae_nearest_frames", f.device, ptr(q), M, ptr(f), F, D, ptr(lut), k, ptr(dist), ptr(index), ptr(scratch), nbytes)
-    return dist, index
-
-
-def nearest_frames(queries, frames, k=5, lut=None):
-    """The ``k`` nearest training frames of every query, exactly, in one pass over the resident uint8 data (mmvae_nearest_frames): did
-    the model learn to draw, or did it memorise?  ``frames``: a uint8 device tensor [..., H, W] whose leading axes are flattened to F
-    frames, or a ``MovingMNISTClips`` (its ``.clips``).  ``queries``: uint8 on the same device, [M, H, W], [M, 1, H, W] or [M, H*W].
-    The distance is the sum of squared byte differences, ``sum (q - t(x))^2`` in exact integers, with ``t = lut[.]`` applied to the
-    FRAMES only (``lut``: None or 256 uint8 values on any device -- ``fit.lut`` of a ``QuantiserFit`` compares class labels,
-    ``gray_lut(Q, centres)[fit.lut]`` dequantised greys; the queries are already in that space).  Returns ``(dist, index)``: int32 and
-    int64 (M, k) device tensors, nearest first, equal distances to the lower index; ``index`` addresses ``frames.reshape(-1, H*W)``
-    (for clips ``divmod(index, 20)`` is (clip, frame)).  M <= 64, k <= 8, H*W a multiple of 16 up to 16384, k <= F.  Everything is
-    checked before anything is launched (ValueError); no host read inside the call; the same bits every run."""
-    q, f, k, lut, _ = _nearest_args(queries, frames, k, lut, "nearest_frames")
-    return _nearest_launch(q, f, k, lut)
-
-
 class QuantiserFit:
     """What ``fit_quantiser`` returns.  ``centres``: (q,) f64, ASCENDING, on the ToTensor scale [0, 1] -- label k is the k-th darkest
     cluster (scikit-learn's label order is arbitrary, and ``data_mean`` / ``data_std``, statistics of the labels, follow the order:

@@ -35,12 +35,13 @@ import numpy as np
 import torch
 
 from .data import (KMEANS_FILE_NOTE, GeneratedClips, MovingMNISTClips, QuantiserFit, choose_transformer, clips_from_npz_array,  # noqa: F401
-                   fit_quantiser, generate_batch, generate_clips, load_idx_images, load_kmeans_file, nearest_frames, pixel_histogram,
+                   fit_quantiser, generate_batch, generate_clips, load_idx_images, load_kmeans_file, pixel_histogram,
                    quantise_frames, resize_frames, resize_quantise_frames, save_kmeans_file, save_moving_mnist_files, velocity_table)
 from .decomposition import (LatentPenalty, _decompose, decomposition_to_host, elbo_decomposition, latent_penalty, make_latent_penalty,  # noqa: F401
                             posterior_mixture)
 from .model import VAE
 from .monitor import TensorHistograms, make_histogram_callback, tensor_histograms  # noqa: F401
+from .neighbours import nearest_frames  # noqa: F401
 from .panels import (_plot_setup, column, gray_lut, latent_slide, make_plot_callback, neighbour_sheet, plot_neighbours, plot_pixelcnn, plot_pixelvae,  # noqa: F401
                      plot_vae, render_sheet, sample_from_reconstruction, scatter_panel, scatter_plot, scatter_tone, write_png_gray)
 from .quality import frame_quality, reconstruction_quality  # noqa: F401

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .neighbours import _nearest_args, _nearest_launch
 
 _COLUMN_KEYS = ("kind", "tensor", "lut", "uniforms", "lo", "hi")
 _COLUMN_KINDS = ("labels", "argmax", "sample", "image")
@@ -316,7 +317,6 @@ def neighbour_sheet(queries, frames, k=5, lut=None, display_lut=None):
     labels (``gray_lut(Q, centres)``); every column then goes through the 'labels' kind.  Without it the compared bytes are shown as
     greys ('image' columns with lo = 0, hi = 255: the byte itself).  Square planes of side <= 64, ``k <= 7`` (a sheet has 8 columns);
     otherwise as ``nearest_frames``.  Everything is checked before anything is launched; a violation raises ValueError."""
-    from .data import _nearest_args, _nearest_launch
     if not 1 <= int(k) <= L.PANEL_MAX_COLS - 1:
         raise ValueError(f"neighbour_sheet: k={int(k)} unsupported (1..{L.PANEL_MAX_COLS - 1}: a sheet has {L.PANEL_MAX_COLS} columns)")
     if display_lut is not None:

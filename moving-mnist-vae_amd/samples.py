@@ -10,100 +10,10 @@ operations; ``sample_frames`` draws the samples as the very bytes the ``normal_s
 import torch
 
 from . import _lib as L
-from .data import MovingMNISTClips
+from .neighbours import _cross_args, _cross_launch, _lut256, _rows_u8, ball_counts, cross_neighbours  # noqa: F401
 from .panels import _decoder_column, _draw, _fit_planes, _plot_mode, _plot_setup, render_sheet
 
 SAMPLE_QUALITY_KEYS = ("precision", "recall", "density", "coverage", "accuracy", "accuracy_real", "accuracy_fake")
-
-
-def _rows_u8(t, name, what):
-    """One side of a sweep, checked on its own: the uint8 tensor as (N, D) rows (not yet made dense)."""
-    if isinstance(t, MovingMNISTClips):
-        t = t.clips.reshape(-1, t.clips.shape[-2] * t.clips.shape[-1])
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
-        raise ValueError(f"{what}: {name} must be a uint8 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
-    if t.dim() == 4 and t.shape[1] == 1:
-        t = t[:, 0]
-    if t.dim() not in (2, 3):
-        raise ValueError(f"{what}: {name} must have shape [N, H, W], [N, 1, H, W] or [N, H*W], got {tuple(t.shape)}")
-    return t.detach().reshape(t.shape[0], t.shape[1] if t.dim() == 2 else t.shape[1] * t.shape[2])
-
-
-def _cross_args(a, b, k, exclude_self, radius, what):
-    """Every check of a sweep (nothing is launched here): returns (a (Na, D), b (Nb, D), radius int32 (Nb,) or None), the planes dense
-    and 16-byte aligned."""
-    a, b = _rows_u8(a, "a", what), _rows_u8(b, "b", what)
-    (Na, D), (Nb, Db) = a.shape, b.shape
-    if D != Db:
-        raise ValueError(f"{what}: rows of {D} bytes in a do not match rows of {Db} bytes in b")
-    if not 0 <= k <= L.KNN_CROSS_MAX_K:
-        raise ValueError(f"{what}: k={k} unsupported (1..{L.KNN_CROSS_MAX_K})")
-    for n, name in ((Na, "Na"), (Nb, "Nb")):
-        if not 1 <= n <= L.KNN_CROSS_MAX_N:
-            raise ValueError(f"{what}: {name}={n} rows unsupported (1..{L.KNN_CROSS_MAX_N})")
-    if D % 16 or not 16 <= D <= L.KNN_CROSS_MAX_D:
-        raise ValueError(f"{what}: D={D} bytes per row unsupported (a multiple of 16 in 16..{L.KNN_CROSS_MAX_D})")
-    avail = Nb - 1 if exclude_self else Nb
-    if k > avail:
-        raise ValueError(f"{what}: k={k} exceeds the {avail} columns available (Nb={Nb}{', self excluded' if exclude_self else ''})")
-    if radius is not None:
-        if not isinstance(radius, torch.Tensor) or radius.dtype not in (torch.int32, torch.int64):
-            raise ValueError(f"{what}: radius must be an int32 or int64 tensor, got {getattr(radius, 'dtype', type(radius).__name__)}")
-        if radius.dim() != 1 or radius.shape[0] != Nb:
-            raise ValueError(f"{what}: radius of shape {tuple(radius.shape)} for Nb={Nb} columns")
-    if a.device != b.device or (radius is not None and radius.device != b.device):
-        raise ValueError(f"{what}: a on {a.device}, b on {b.device}" + ("" if radius is None else f", radius on {radius.device}"))
-    if radius is not None and bool((radius.detach() < 0).any()):            # the one device -> host read of ball_counts
-        raise ValueError(f"{what}: a radius is negative (squared distances are not)")
-    if not a.is_cuda:
-        raise ValueError(f"{what} expects its tensors on the GPU")
-    a, b = (t.contiguous() for t in (a, b))
-    a, b = (t if t.data_ptr() % 16 == 0 else t.clone() for t in (a, b))
-    return a, b, radius
-
-
-def _radius_i32(radius):
-    """Checked squared-distance radii as the int32 the kernel compares against.  No distance exceeds D * 255^2 < 2^31, so larger radii
-    are clamped to the int32 maximum without changing any comparison."""
-    return radius.detach().clamp(max=2 ** 31 - 1).to(torch.int32).contiguous()
-
-
-def _cross_launch(a, b, k, exclude_self, radius):
-    """mmvae_knn_cross on checked arguments: (dist, index) or (None, None), and the counts or None."""
-    (Na, D), Nb, dev = a.shape, b.shape[0], a.device
-    nbytes = L.lib().mmvae_knn_cross_scratch_bytes(Na, Nb, D, k, int(radius is not None))
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    dist = torch.empty((Na, k), dtype=torch.int32, device=dev) if k else None
-    index = torch.empty((Na, k), dtype=torch.int64, device=dev) if k else None
-    count = torch.empty((Na,), dtype=torch.int32, device=dev) if radius is not None else None
-    L.call("mmvae_knn_cross", dev, L.ptr(a), Na, L.ptr(b), Nb, D, k, int(bool(exclude_self)), L.ptr(dist), L.ptr(index), L.ptr(radius),
-           L.ptr(count), L.ptr(scratch), nbytes)
-    return dist, index, count
-
-
-def cross_neighbours(a, b, k=1, exclude_self=False):
-    """The ``k`` nearest rows of ``b`` for every row of ``a``, exactly (mmvae_knn_cross): a tiled int8 GEMM over all Na x Nb pairs, no
-    Na x Nb matrix anywhere.  ``a``, ``b``: uint8 device tensors [N, H, W], [N, 1, H, W] or [N, H*W], or a ``MovingMNISTClips`` (its
-    ``.clips``, flattened to frames).  The distance is the sum of squared byte differences in exact integers.  Returns ``(dist, index)``:
-    int32 and int64 (Na, k) device tensors, nearest first, equal distances to the lower index of ``b``.  ``exclude_self=True`` leaves the
-    pairs (i, i) out -- leave-one-out when ``a`` and ``b`` are the same set; a duplicate of row i at another index stays, at distance 0.
-    Na, Nb <= 2^20, 1 <= k <= 8, H*W a multiple of 16 up to 16384, k <= Nb (Nb - 1 with ``exclude_self``).  Everything is checked before
-    anything is launched (ValueError); no host read inside the call; the same bits every run."""
-    k = int(k)
-    if k < 1:
-        raise ValueError(f"cross_neighbours: k={k} unsupported (1..{L.KNN_CROSS_MAX_K})")
-    a, b, _ = _cross_args(a, b, k, exclude_self, None, "cross_neighbours")
-    dist, index, _ = _cross_launch(a, b, k, exclude_self, None)
-    return dist, index
-
-
-def ball_counts(a, b, radius, exclude_self=False):
-    """For every row i of ``a``, in how many balls of ``b`` it lies: ``#{ j : d(i, j) <= radius[j] }`` as an int32 (Na,) device tensor
-    (mmvae_knn_cross without a selection).  ``radius``: int32 or int64 device tensor (Nb,) of SQUARED distances, each >= 0 (checked:
-    one device -> host read); the comparison is inclusive and exact.  ``a``, ``b``, ``exclude_self`` and the limits as in
-    ``cross_neighbours``."""
-    a, b, radius = _cross_args(a, b, 0, exclude_self, radius, "ball_counts")
-    return _cross_launch(a, b, 0, exclude_self, _radius_i32(radius))[2]
 
 
 def _ratio(num, den):
@@ -137,16 +47,14 @@ def sample_quality(real, fake, k=3, lut=None):
     if k < 1:
         raise ValueError(f"{what}: k={k} unsupported (1..{L.KNN_CROSS_MAX_K})")
     if lut is not None:
-        lut = torch.as_tensor(lut)
-        if lut.dtype != torch.uint8 or lut.numel() != 256:
-            raise ValueError(f"{what}: lut is 256 uint8 values")
-    R, F = _rows_u8(real, "real", what), _rows_u8(fake, "fake", what)
+        lut = _lut256(lut, what)
+    R, F = _rows_u8(real, "real", what)[0], _rows_u8(fake, "fake", what)[0]
     for t, name in ((R, "real"), (F, "fake")):
         if t.shape[0] < k + 1:
             raise ValueError(f"{what}: k={k} neighbours inside {name} need more than k rows, got {t.shape[0]}")
     R, F, _ = _cross_args(R, F, k, False, None, what)
     if lut is not None:
-        R = lut.detach().reshape(-1).to(R.device)[R.long()]
+        R = lut.to(R.device)[R.long()]
     nr, nf = R.shape[0], F.shape[0]
     d_rr = _cross_launch(R, R, k, True, None)[0]
     d_ff = _cross_launch(F, F, k, True, None)[0]

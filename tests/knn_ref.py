@@ -1,30 +1,35 @@
-"""CPU references of the set-to-set sweep (mmvae_knn_cross) and of the sample-quality scores built on it.  Everything is exact: the
-distances are integers far below 2^53 formed in float64, the scores are ratios of two exact integers formed in float64."""
+"""CPU references of both exact k-NN entry points (mmvae_nearest_frames, mmvae_knn_cross) and of the sample-quality scores built on the
+sweep.  Everything is exact: the distances are integers far below 2^53 formed in float64, the scores are ratios of two exact integers
+formed in float64."""
 import numpy as np
 import torch
 
 I64_MAX = torch.iinfo(torch.int64).max
 
 
-def dist_matrix(a, b):
-    """int64 (Na, Nb): |a|^2 + |b|^2 - 2 a b^T in float64 (every value and partial sum stays far below 2^53, so it is exact)."""
+def dist_matrix(a, b, lut=None, chunk=8192):
+    """int64 (Na, Nb): |a|^2 + |t(b)|^2 - 2 a t(b)^T in float64 (every value and partial sum stays far below 2^53, so it is exact),
+    ``chunk`` rows of ``b`` at a time.  ``lut`` (256 uint8) is t, applied to ``b`` only; every leading axis of ``b`` is flattened."""
     a = a.reshape(a.shape[0], -1).cpu().double()
-    b = b.reshape(b.shape[0], -1).cpu().double()
-    return ((a * a).sum(1)[:, None] + (b * b).sum(1)[None, :] - 2.0 * (a @ b.T)).to(torch.int64)
+    b, an, parts = b.reshape(-1, a.shape[1]).cpu(), (a * a).sum(1)[:, None], []
+    for lo in range(0, b.shape[0], chunk):
+        c = (b[lo:lo + chunk] if lut is None else lut.cpu()[b[lo:lo + chunk].long()]).double()
+        parts.append((an + (c * c).sum(1)[None, :] - 2.0 * (a @ c.T)).to(torch.int64))
+    return torch.cat(parts, dim=1)
 
 
-def _masked(a, b, exclude_diagonal):
-    d = dist_matrix(a, b)
+def _masked(a, b, exclude_diagonal, lut=None, chunk=8192):
+    d = dist_matrix(a, b, lut, chunk)
     if exclude_diagonal:
         n = min(d.shape)
         d[torch.arange(n), torch.arange(n)] = I64_MAX
     return d
 
 
-def knn_cross_ref(a, b, k, exclude_diagonal=False):
+def knn_cross_ref(a, b, k, exclude_diagonal=False, lut=None, chunk=8192):
     """(dist int32 (Na, k), index int64 (Na, k)): the diagonal set to the int64 maximum when excluded, a STABLE sort along the columns
     (equal distances keep the lower index first), the first k."""
-    sd, idx = torch.sort(_masked(a, b, exclude_diagonal), dim=1, stable=True)
+    sd, idx = torch.sort(_masked(a, b, exclude_diagonal, lut, chunk), dim=1, stable=True)
     return sd[:, :k].to(torch.int32).contiguous(), idx[:, :k].contiguous()
 
 
@@ -34,12 +39,13 @@ def ball_counts_ref(a, b, radius, exclude_diagonal=False):
     return (d <= radius.cpu().to(torch.int64)[None, :]).sum(1).to(torch.int32)
 
 
-def knn_cross_brute(a, b, k, exclude_diagonal=False, radius=None):
-    """The definition itself: an int64 double loop.  (dist, index, count or None)."""
-    a, b = a.reshape(a.shape[0], -1).tolist(), b.reshape(b.shape[0], -1).tolist()
+def knn_cross_brute(a, b, k, exclude_diagonal=False, radius=None, lut=None):
+    """The definition itself: an int64 double loop, then the k smallest (d, j) pairs.  (dist, index, count or None)."""
+    a = a.reshape(a.shape[0], -1).tolist()
+    b, t = b.reshape(-1, len(a[0])).tolist(), list(range(256)) if lut is None else lut.tolist()
     dist, index, count = [], [], []
     for i, ra in enumerate(a):
-        pairs = [(sum((x - y) ** 2 for x, y in zip(ra, rb)), j) for j, rb in enumerate(b) if not (exclude_diagonal and i == j)]
+        pairs = [(sum((x - t[y]) ** 2 for x, y in zip(ra, rb)), j) for j, rb in enumerate(b) if not (exclude_diagonal and i == j)]
         best = sorted(pairs)[:k]
         dist.append([p[0] for p in best])
         index.append([p[1] for p in best])

@@ -4,9 +4,13 @@ before anything is enqueued, so made-up device addresses are never used), and th
 import importlib
 import os
 import re
+import sys
 
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from knn_ref import knn_cross_brute, knn_cross_ref, tie_case  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_ARG, ERR_WORKSPACE, ERR_UNSUPPORTED = -1, -3, -4
@@ -16,49 +20,19 @@ def _L():
     return importlib.import_module("moving-mnist-vae_amd._lib")
 
 
-# ================================================================ the reference
+# ================================================================ the reference (tests/knn_ref.py), under the names the GPU tests import
 def nearest_ref(queries, frames, k, lut=None, chunk=8192):
-    """(dist int32 (M, k), index int64 (M, k)) on the CPU: |q|^2 + |t(f)|^2 - 2 q t(f)^T in float64 (every value stays far below 2^53,
-    so the arithmetic is exact), cast to int64, a STABLE sort along the frames (equal distances keep the lower index first), the first
-    k.  ``lut`` (256 uint8) is applied to the frames only."""
-    q = queries.reshape(queries.shape[0], -1).cpu()
-    D = q.shape[1]
-    f = frames.reshape(-1, D).cpu()
-    qd = q.double()
-    qn = (qd * qd).sum(1)
-    parts = []
-    for lo in range(0, f.shape[0], chunk):
-        c = f[lo:lo + chunk]
-        if lut is not None:
-            c = lut.cpu()[c.long()]
-        c = c.double()
-        parts.append((qn[:, None] + (c * c).sum(1)[None, :] - 2.0 * (qd @ c.T)).to(torch.int64))
-    d = torch.cat(parts, dim=1)
-    sd, idx = torch.sort(d, dim=1, stable=True)
-    return sd[:, :k].to(torch.int32).contiguous(), idx[:, :k].contiguous()
+    return knn_cross_ref(queries, frames, k, lut=lut, chunk=chunk)
 
 
 def nearest_brute(queries, frames, k, lut=None):
-    """The definition itself: an int64 double loop, then the k smallest (d, f) pairs."""
-    q = queries.reshape(queries.shape[0], -1).tolist()
-    f = frames.reshape(-1, len(q[0])).tolist()
-    t = list(range(256)) if lut is None else lut.tolist()
-    dist, index = [], []
-    for row in q:
-        pairs = sorted((sum((a - t[b]) ** 2 for a, b in zip(row, fr)), j) for j, fr in enumerate(f))[:k]
-        dist.append([p[0] for p in pairs])
-        index.append([p[1] for p in pairs])
-    return torch.tensor(dist, dtype=torch.int32), torch.tensor(index, dtype=torch.int64)
+    return knn_cross_brute(queries, frames, k, lut=lut)[:2]
 
 
 @pytest.mark.parametrize("with_lut", [False, True])
 def test_reference_matches_the_brute_force_loop(with_lut):
-    g = torch.Generator().manual_seed(4)
-    q = torch.randint(0, 256, (5, 16), dtype=torch.uint8, generator=g)
-    f = torch.randint(0, 256, (37, 16), dtype=torch.uint8, generator=g)
-    f[20], f[3], f[30] = f[11], q[2], q[2]                 # a tie between two frames, a query's copy at two indices
-    f[5:9] = torch.tensor([0, 255] * 8, dtype=torch.uint8)  # four identical frames
-    lut = torch.randperm(256, generator=g).to(torch.uint8) if with_lut else None
+    q, f = tie_case()                                       # a tie between two frames, four identical frames, a query's copy at two indices
+    lut = torch.randperm(256, generator=torch.Generator().manual_seed(4)).to(torch.uint8) if with_lut else None
     if with_lut:
         f[3], f[30] = 0, 0
         q[2] = lut[0]
@@ -197,11 +171,11 @@ def test_python_surface_refuses_before_any_launch(pkg):
 
 
 def test_new_names_are_exported(pkg):
-    data = importlib.import_module("moving-mnist-vae_amd.data")
+    neighbours = importlib.import_module("moving-mnist-vae_amd.neighbours")
     panels = importlib.import_module("moving-mnist-vae_amd.panels")
     main = importlib.import_module("moving-mnist-vae_amd.main")
-    assert callable(data.nearest_frames) and callable(panels.neighbour_sheet) and callable(panels.plot_neighbours)
-    for name, home in (("nearest_frames", data), ("neighbour_sheet", panels), ("plot_neighbours", panels)):
+    assert callable(neighbours.nearest_frames) and callable(panels.neighbour_sheet) and callable(panels.plot_neighbours)
+    for name, home in (("nearest_frames", neighbours), ("neighbour_sheet", panels), ("plot_neighbours", panels)):
         assert getattr(pkg, name) is getattr(home, name) and getattr(main, name) is getattr(home, name), name
     import inspect
     assert inspect.signature(pkg.nearest_frames).parameters["k"].default == 5
